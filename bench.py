@@ -4,10 +4,14 @@ discriminator + all losses + grad clip + Adam, D phase and G phase) on 4 s @ 22.
 piano/violin pairs, B=8 clips per GPU (BASELINE.json configs[1]; weak scaling to configs[2]).
 
     python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
+    python bench.py --full                             (+ roofline, cpu_baseline and the extras)
+    python bench.py --dump-outputs DIR                 (+ DIR/<name>.npy: the losses the last timed step returned)
 
-Prints ONE JSON line (rank 0).  Inputs are synthetic and resident in HBM before the timed
-region.  `roofline` is measured live with device events around every launch of the dominant
-GEMM kernel; `cpu_baseline` times the CPU oracle (a port of the reference step) on the host.
+Prints ONE JSON line (rank 0).  Inputs are synthetic, seeded and resident in HBM before the
+timed region.  A plain run sets up, warms up, times the steps and prints the line; --full adds
+`roofline` (measured live with device events around every launch of the dominant GEMM kernel),
+`cpu_baseline` (the CPU oracle, a port of the reference step, timed on the host) and the extras
+(autoregressive decode, the f32 parity mode, the mixed-length stream).
 """
 import argparse
 import json
@@ -26,6 +30,46 @@ import torch.distributed as dist
 CLIP_SECONDS = 4.0
 PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}      # dense MFMA peaks, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+
+
+def snapshot_state(tr):
+    """--dump-outputs: the trainer's whole mutable state (parameters, Adam moments and step counters, module buffers: the list its
+    own graph capture restores), copied at set-up, before any step, where it is the seeded initial state of every run."""
+    return [(t, t.clone()) for t in tr._mutable_state()]
+
+
+def restore_state(snap):
+    with torch.no_grad():
+        for t, saved in snap:
+            t.copy_(saved)
+
+
+def timed_steps(n, step, barrier, reset=None):
+    """Wall time of step(0) .. step(n - 1), ended by a device barrier.  reset, when given, runs before the last step with the
+    clock stopped: --dump-outputs restores the initial state there, so that the step whose outputs are written starts from
+    the same state in every run (the f32 atomics of the step sum in a different order each run, and over many Adam steps
+    those rounding differences grow into different parameters)."""
+    total, t0 = 0.0, time.perf_counter()
+    for k in range(n):
+        if reset is not None and k == n - 1:
+            barrier()
+            total += time.perf_counter() - t0
+            reset()
+            barrier()
+            t0 = time.perf_counter()
+        step(k)
+    barrier()
+    return total + time.perf_counter() - t0
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs: what the last timed step returned to its caller -- the loss scalars of Trainer.step() -- as float32
+    DIR/loss_<name>.npy.  The parameters it updated are not written: from the restored initial state that step is Adam's
+    first, which moves every parameter by +-lr with the sign of its gradient, and for gradients near zero that sign is set
+    by the summation order of the atomics, which differs from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in tr.losses.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), v.detach().float().reshape(1).cpu().numpy())
 
 
 def _cpu_model():
@@ -252,7 +296,7 @@ def ar_decode_cpu(B, S, frames, clip_s, reps=3):
             "cpu_model": _cpu_model(), "kind": "port", "sample": f"oracle eval pipeline, B={B} S={S}, median of {reps}"}
 
 
-def mixed_bench(args, tr, dev, rank, world, barrier, steps=None, warmup=None):
+def mixed_bench(args, tr, dev, rank, world, barrier, steps=None, warmup=None, reset=None):
     """BASELINE configs[4]: variable-length curriculum batches.  Seven length buckets (2..8 s); every step takes one bucket's
     batch of B clips (resident waveforms -> STFT + CQT front end -> step); each bucket owns its front-end buffers and its
     captured graph, so after the first visit every step is a replay.  value = true audio seconds / wall time."""
@@ -277,10 +321,8 @@ def mixed_bench(args, tr, dev, rank, world, barrier, steps=None, warmup=None):
     for k in range(max(warmup, len(buckets))):         # every bucket captured once before timing
         run(k)
     barrier()
-    t0 = time.perf_counter()
-    secs = sum(run(k) for k in range(steps))
-    barrier()
-    dt = time.perf_counter() - t0
+    dt = timed_steps(steps, run, barrier, reset)
+    secs = sum(buckets[k % len(buckets)][0] for k in range(steps))
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -318,10 +360,15 @@ def main():
                     help="new_decoder.Decoder (north star) or SimpleDecoder_TransformerOnly.Decoder (SURVEY 8(f)1, 182 M parameters)")
     ap.add_argument("--single-stream", action="store_true", help="capture the three encoder branches on one stream (A/B of the fork/join capture)")
     ap.add_argument("--no-overlap-d", action="store_true", help="run the discriminator phase in line instead of beside the decoder forward (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, cpu_baseline and the extras (one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without roofline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the sub-objects of the default run: autoregressive_decode (configs[3], B=8 and B=1), parity_mode (f32) and mixed (configs[4])")
+                    help="--full without its sub-objects autoregressive_decode (configs[3], B=8 and B=1), parity_mode (f32) and mixed (configs[4])")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the losses the last one returned as DIR/<name>.npy; that step starts from "
+                         "the seeded initial state (restored with the clock stopped), so runs with the same arguments agree")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -367,8 +414,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    snap = snapshot_state(tr) if args.dump_outputs else None
+    reset = (lambda: restore_state(snap)) if snap is not None else None
     if args.mixed:
-        res = mixed_bench(args, tr, dev, rank, world, barrier)
+        res = mixed_bench(args, tr, dev, rank, world, barrier, reset=reset)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(tr, args.dump_outputs)
         if rank == 0:
             print(json.dumps(res))
         if world > 1:
@@ -378,15 +429,13 @@ def main():
     for _ in range(args.warmup):
         tr.step(x, labels)
     barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        tr.step(x, labels)
-    barrier()
-    dt = time.perf_counter() - t0
+    dt = timed_steps(args.steps, lambda k: tr.step(x, labels), barrier, reset)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(tr, args.dump_outputs)          # before the --full legs, which step the same trainer again
     losses = {k: float(v) for k, v in tr.losses.items()}
     ms = dt / args.steps * 1e3
     value = world * args.batch * clip_seconds / (dt / args.steps)
@@ -404,7 +453,8 @@ def main():
                       "grad_exchange": ("three buckets (decoder, content, style) all-reduced while the backward pass goes on" if (tr._matched and tr.cfg.bucketed) else "one all-reduce per optimiser group after backward") if world > 1 else None,
                       "dp_semantics": ("global-batch (sync-BN + gathered losses: loss-matched to the single-process step)" if args.loss_matched and world > 1 else "per-rank BN and batch-coupled losses")},
            "losses": losses}
-    extras = rank == 0 and world == 1 and args.decoder == "new" and not args.no_extras
+    full = rank == 0 and world == 1 and args.full
+    extras = full and args.decoder == "new" and not args.no_extras
     if rank == 0 and world == 1 and args.infer and args.decoder == "new":
         out["autoregressive_decode"] = ar_decode_bench(tr, x, labels, args.sections)
     elif extras:
@@ -413,7 +463,7 @@ def main():
         b1 = ar_decode_bench(tr, x[:1].contiguous(), labels[:1], args.sections, cpu_reps=2, eager=False)
         out["autoregressive_decode"]["batch_1"] = {k: b1[k] for k in ("ms_per_batch", "ms_per_batch_recompute_graph", "ms_per_batch_kv_cache_graph",
                                                                         "stft_frames_per_s", "audio_seconds_per_s", "batch", "sections", "cpu", "speedup_vs_cpu")}
-    if rank == 0 and world == 1:
+    if full:
         if not args.no_roofline:
             out["roofline"] = kernel_roofline(tr, x, labels, args.dtype)
             # whole step against the MFMA peak: SURVEY 8(d)'s 41.74 GFLOP per section forward + backward (3x convention)

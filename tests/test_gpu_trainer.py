@@ -368,6 +368,7 @@ def test_collectives_inside_the_captured_step_one_rank():
     then replays one graph, like a single GPU).  One-rank rehearsal on this box: a 1-rank NCCL group, the collective path
     forced on (AST_FORCE_COLLECTIVES=1): the probe must accept, the step must be ONE graph, and three steps must give the
     losses of a plain single-GPU trainer (an all-reduce over one rank is the identity)."""
+    import gc
     import torch.distributed as dist
     ast_amd.set_compute_dtype(torch.bfloat16)
     x, labels = train.synthetic_batch(2, 2, "cuda:0")
@@ -402,6 +403,11 @@ def test_collectives_inside_the_captured_step_one_rank():
         from ast_amd import ops as _ops
         _ops.set_sync_bn(1)
         os.environ.pop("AST_FORCE_COLLECTIVES", None)
+        # the captured graphs hold RCCL kernel plans of the communicator: release them (and the trainers owning them) while it
+        # is alive, and only then destroy it -- the other order frees the communicator under live graphs
+        tr = trm = graphs = graphs_m = None
+        gc.collect()
+        torch.cuda.synchronize()
         dist.destroy_process_group()
 
 

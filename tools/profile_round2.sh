@@ -4,11 +4,11 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02; mkdir -p $O
-timeout -k 10 400 python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json || exit 1
+timeout -k 10 400 python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json || exit 1
 echo "default done"; cut -c1-200 $O/bench_default.json
-timeout -k 10 200 python bench.py --dtype f32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f32.json || exit 1
-timeout -k 10 300 python bench.py --infer --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_infer_s2.json || exit 1
-timeout -k 10 300 python bench.py --infer --sections 4 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_infer_s4.json || exit 1
+timeout -k 10 200 python bench.py --full --dtype f32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_f32.json || exit 1
+timeout -k 10 300 python bench.py --full --infer --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_infer_s2.json || exit 1
+timeout -k 10 300 python bench.py --full --infer --sections 4 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_infer_s4.json || exit 1
 timeout -k 10 300 python bench.py --mixed --steps 28 --warmup 7 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_mixed.json || exit 1
 echo "benches done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_graph -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline > $O/prof_graph.log 2>&1 || exit 1

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03; mkdir -p $O
-timeout -k 10 500 python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 500 python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json || { tail -5 $O/bench_default.err; exit 1; }
 echo "default done"; cut -c1-300 $O/bench_default.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_graph -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline --no-extras > $O/prof_graph.log 2>&1 || exit 1
 f=$(ls $O/prof_graph/*/*kernel_trace.csv | head -1); python3 tools/timeline.py $f 80 > $O/graph_timeline.txt; python3 tools/timeline_tail.py $f 1200 > $O/graph_timeline_tail.txt
