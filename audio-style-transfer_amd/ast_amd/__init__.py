@@ -6,9 +6,26 @@ hand-written HIP kernels behind the C-ABI of include/ast_hip.h.  There is no CPU
 or ATen fallback: without libast_hip.so and a GPU the ops raise.
 """
 from . import config  # noqa: F401
-from .config import set_compute_dtype  # noqa: F401
+from .config import set_compute_dtype, set_deterministic  # noqa: F401
 from .style_encoder import StyleEncoder, SinusoidalPositionalEncoding, initialize_weights  # noqa: F401
 from .content_encoder import ContentEncoder  # noqa: F401
 from .new_decoder import Decoder, compute_comprehensive_loss  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401
 from .losses import infoNCE_loss, margin_loss, adversarial_loss, disentanglement_loss  # noqa: F401
+
+
+class deterministic:
+    """Context manager: deterministic mode inside the block (config.set_deterministic), the previous setting restored after it.
+    `with ast_amd.deterministic(): ...`  /  `with ast_amd.deterministic(False): ...`"""
+
+    def __init__(self, flag=True):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.prev = config.deterministic
+        config.set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        config.deterministic = self.prev
+        return False

@@ -116,6 +116,21 @@ _SIGS = {
     "ast_wgrad_rep": ([vp, vp, vp, C.POINTER(Gather), i32, i32, vp], i32),
     "ast_wgrad_slab": ([vp, vp, vp, C.POINTER(Gather), i32, i32, C.POINTER(i32), vp], i32),
     "ast_slab_sum": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), i32, vp], i32),
+    # deterministic forms (include/ast_hip.h)
+    "ast_ordered_sum": ([vp, i64, i32, i32, vp, i32, vp], i32),
+    "ast_igemm_ws_floats_det": ([C.POINTER(Gather), i32], C.c_long),
+    "ast_sumsq_det": ([vp, i64, vp, vp, i32, vp], i32),
+    "ast_colsum_acc_det": ([vp, i64, i32, i32, vp, i32, vp, i32, vp], i32),
+    "ast_chan_stats_det": ([vp, vp, i32, i32, i32, i32, vp, i32, vp], i32),
+    "ast_norm_bwd_sums_det": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp], i32),
+    "ast_layernorm_bwd_det": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
+    "ast_add_drop_ln_bwd_det": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp], i32),
+    "ast_recon_loss_total_det": ([vp, vp, i64, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, C.c_long, vp, vp, vp], i32),
+    "ast_weight_grads_flush_det": ([vp, vp, i32, vp, C.c_long, vp], i32),
+    "ast_bigk_gemm_det_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_bigk_gemm_det": ([vp, vp, vp, vp, i32, i32, i32, vp, C.c_long, vp], i32),
+    "ast_bign_dgrad_det_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_bign_dgrad_det": ([vp, vp, vp, i32, i32, i32, i32, vp, C.c_long, vp], i32),
     "ast_tok_max_ops": ([], i32),
     "ast_tok_program": ([vp, i32, i32, i32, vp, vp, vp, vp], i32),
 }

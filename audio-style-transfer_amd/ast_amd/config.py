@@ -70,3 +70,27 @@ wgrad_defer_streams = int(_os.environ.get("AST_WGRAD_DEFER_STREAMS", "1"))   # s
 # on paper the last bank runs alone for a quarter of the phase, in the replay every extra cross-stream wait costs more than it buys.
 wgrad_defer_pool = _os.environ.get("AST_WGRAD_DEFER_POOL", "0") != "0"
 wgrad_defer_lend = float(_os.environ.get("AST_WGRAD_DEFER_LEND", "1.0"))       # fraction of the helper's spare capacity that is used
+
+# Deterministic mode (AST_DETERMINISTIC=1, set_deterministic, the deterministic() context manager, TrainConfig.deterministic):
+# every kernel that sums partials across workgroups stores them into slots indexed by workgroup / tile / row and reduces the slots
+# in a fixed order instead of adding them with f32 atomics in arrival order, so two runs of the same train step on one GPU give
+# bit-identical losses, parameters, moments and buffers.  Off by default: the default kernels and launches are unchanged.
+# Not available with the token programs (tok_programs != 0) or data parallelism (world > 1): both raise ValueError.
+deterministic = _os.environ.get("AST_DETERMINISTIC", "0") not in ("", "0")
+
+
+def check_deterministic_supported(flag, world=1):
+    """ValueError for a combination deterministic mode cannot honour (before anything is launched)."""
+    if not flag:
+        return
+    if tok_programs != 0:
+        raise ValueError("deterministic mode: the token programs (AST_TOK_PROGRAMS != 0) add floats with atomics; set AST_TOK_PROGRAMS=0")
+    if world > 1:
+        raise ValueError("deterministic mode covers one GPU (world == 1); data parallelism is not supported")
+
+
+def set_deterministic(flag):
+    global deterministic
+    flag = bool(flag)
+    check_deterministic_supported(flag)
+    deterministic = flag

@@ -67,7 +67,7 @@ class WeightBank:
         return t
 
     def _signature(self, training):
-        return (training,) + tuple((w.data_ptr(), w.device, fn(), (None if w.grad is None else w.grad.data_ptr()) if training else 0)
+        return (training, config.deterministic) + tuple((w.data_ptr(), w.device, fn(), (None if w.grad is None else w.grad.data_ptr()) if training else 0)
                                    for w, _, fn, *_ in self.specs)
 
     def _build(self, training):
@@ -81,6 +81,9 @@ class WeightBank:
         # their staging; ast_wgrad_rep spreads the workgroups over them and the flush sums the copies.
         # With config.wgrad_slabs the small weights get that many copies instead and every pixel slice of the weight-gradient launch
         # STORES into its own (ast_wgrad_slab); ast_slab_sum adds them into copy 0 in _flush, and the descriptor shows ONE copy.
+        # Deterministic mode: EVERY convolution weight takes the slab form (plain stores, slices summed in index order), with as many
+        # copies as keep its slab region under 32 MB (the launch cuts its pixels into at most that many slices).
+        det = config.deterministic
         sizes, reps, slabs = [], [], []
         for (w, kind, *_rest) in self.specs:
             if kind == "linear":
@@ -89,13 +92,21 @@ class WeightBank:
                 co, ci = (w.shape[0], w.shape[1]) if kind == "conv" else (w.shape[1], w.shape[0])
                 one = pad8(co) * w.shape[2] * w.shape[3] * pad8(ci)
                 small = one <= (1 << 18)
-                if small and config.wgrad_slabs > 1:
+                if det:
+                    r, sl = max(2, min(128, (1 << 23) // one)), True
+                elif small and config.wgrad_slabs > 1:
                     r, sl = config.wgrad_slabs, True
                 else:
                     r, sl = (config.wgrad_replicas if (config.wgrad_replicas > 1 and small) else 1), False
                 sizes.append(one * r); reps.append(r); slabs.append(sl)
-        if training and (getattr(self, "dw_arena", None) is None or self.dw_arena.device != dev or self.dw_arena.numel() < max(1, sum(sizes))):
-            self.dw_arena = torch.zeros(max(1, sum(sizes)), dtype=torch.float32, device=dev)
+        if training:
+            # one arena per mode: a graph captured in the other mode keeps reading its own (deterministic slabs are larger)
+            arenas = self.__dict__.setdefault("_arenas", {})
+            akey = (det, str(dev))
+            a = arenas.get(akey)
+            if a is None or a.numel() < max(1, sum(sizes)):
+                a = arenas[akey] = torch.zeros(max(1, sum(sizes)), dtype=torch.float32, device=dev)
+            self.dw_arena = a
         off = 0
         for e, (w, kind, dtype_fn, u, v, bias, rows), sz, rep, slab in zip(self.entries, self.specs, sizes, reps, slabs):
             dt = dtype_fn()
@@ -184,10 +195,16 @@ class WeightBank:
         if not any(b is self for b in _DeferPool.banks):
             _DeferPool.banks.append(self)
 
+    def slab_used(self, pw):
+        """Copies of pw's slab region already written in this backward pass: a weight used k times gets k consecutive groups of
+        copies, one per use in the order of the weight-gradient launches, and _sum_slabs adds them all in index order."""
+        return next((n for p, n in self._slab_recs if p is pw), 0)
+
     def note_slab(self, pw, slices):
-        if any(p is pw for p, _ in self._slab_recs):
-            raise NotImplementedError("a convolution weight was used twice in one backward pass: its slab-mode gradient does not "
-                                      "accumulate (set AST_WGRAD_SLABS=0 for the atomic replicas)")
+        for i, (p, n) in enumerate(self._slab_recs):
+            if p is pw:
+                self._slab_recs[i] = (pw, n + slices)
+                return
         self._slab_recs.append((pw, slices))
 
     def _sum_slabs(self):
@@ -205,6 +222,11 @@ class WeightBank:
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             if self._slab_recs:
                 self._sum_slabs()
+            if config.deterministic:           # spectral-norm inner products through per-tile partials summed in tile order
+                ws = ops.det_ws(self.ntiles, self.d_tiles.device)
+                check(lib().ast_weight_grads_flush_det(ptr(self.d_train), ptr(self.d_tiles), self.ntiles, ptr(ws), ws.numel(), stream()),
+                      "ast_weight_grads_flush_det")
+                return
             check(lib().ast_weight_grads_flush_t(ptr(self.d_train), ptr(self.d_tiles), self.ntiles, stream()),
                   "ast_weight_grads_flush_t")
 

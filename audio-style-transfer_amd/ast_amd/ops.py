@@ -98,10 +98,11 @@ _ws_cache = {}
 
 
 def _ws_need(g, dt):
-    key = (id(g), dt)          # Gather objects are interned by the lru-cached geometry builders
+    det = config.deterministic
+    key = (id(g), dt, det)     # Gather objects are interned by the lru-cached geometry builders
     v = _ws_cache.get(key)
     if v is None:
-        v = int(lib().ast_igemm_ws_floats(g, dt))
+        v = int(lib().ast_igemm_ws_floats_det(g, dt) if det else lib().ast_igemm_ws_floats(g, dt))
         if v < 0:
             check(-1, "ast_igemm_ws_floats")
         _ws_cache[key] = v
@@ -166,8 +167,9 @@ def stat_arena_reset(device):
 
 
 def stats_fusable(g, dt):
-    """True when ast_igemm can add the BatchNorm statistics of its output in the epilogue (plans that do not split K)."""
-    return _ws_need(g, dt) == 0
+    """True when ast_igemm can add the BatchNorm statistics of its output in the epilogue (plans that do not split K).
+    Never in deterministic mode: the epilogue adds its sums with atomics (the separate slotted pass runs instead)."""
+    return _ws_need(g, dt) == 0 and not config.deterministic
 
 
 class BNLink:
@@ -185,7 +187,7 @@ def in_stats_fusable(g, dt):
     import ctypes
     out = (ctypes.c_int32 * 5)()
     check(lib().ast_igemm_plan(g, dt, ctypes.byref(out)), "ast_igemm_plan")
-    return out[2] != 0 and _ws_need(g, dt) == 0
+    return out[2] != 0 and _ws_need(g, dt) == 0 and not config.deterministic
 
 
 def _igemm(src, wgt, bias, dst, g, flags=0, stats=None, bn=None, per_image=False):
@@ -201,6 +203,9 @@ def _igemm(src, wgt, bias, dst, g, flags=0, stats=None, bn=None, per_image=False
         if stats is not None:                   # [slots][Cd][2] table filled by the epilogue (flags bit 3); never with split-K
             assert need == 0 and flags == 0
             ws, need, flags = stats, stats.numel(), (8 | 64 if per_image else 8 | _slot_flags(stats.numel() // (2 * g.Cd)))
+        elif config.deterministic:                 # the atomic-free kernel instantiations (flags bit 12)
+            ws = det_ws(need, src.device) if need > 0 else None         # one slab per K slice, summed in order by the finish pass
+            flags |= 4096
         else:
             ws = _clean_scratch(need, src.device) if need > 0 else None    # persistent, handed back zeroed by the finish pass
             flags |= 4 if need > 0 else 0
@@ -242,9 +247,15 @@ def _wgrad_launch(dy, src, dwp, g, replicas=1, pw=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     if pw is not None and pw.slab:                 # dwp holds `replicas` copies: one per pixel slice, plain stores; the bank sums them
+                                                   # (deterministic mode: every convolution weight, WeightBank._build)
         import ctypes
         slices = ctypes.c_int32(0)
-        check(lib().ast_wgrad_slab(ptr(dy), ptr(src), ptr(dwp), g, dcode(src.dtype), int(replicas), ctypes.byref(slices), stream()), "ast_wgrad_slab")
+        used = pw.bank.slab_used(pw)               # a weight used again in this backward: its next group of copies
+        if used >= replicas:
+            raise ValueError(f"a convolution weight was used more often in one backward pass than its {replicas} slab copies allow")
+        base = dwp.data_ptr() + 4 * used * (dwp.numel() // replicas)
+        check(lib().ast_wgrad_slab(ptr(dy), ptr(src), base, g, dcode(src.dtype), int(replicas - used), ctypes.byref(slices), stream()),
+              "ast_wgrad_slab")
         pw.bank.note_slab(pw, int(slices.value))
     elif replicas > 1:                             # dwp holds `replicas` zeroed copies; the bank's flush sums them
         check(lib().ast_wgrad_rep(ptr(dy), ptr(src), ptr(dwp), g, dcode(src.dtype), int(replicas), stream()), "ast_wgrad_rep")
@@ -297,7 +308,13 @@ class PackedWeight:
         if self.bias is None:
             return
         g = acc_grad(self.bias)
-        check(lib().ast_colsum_acc(ptr(dy2d), dy2d.numel() // self.Cop, self.Cop, self.Co, g.data_ptr() + 4 * self.b_off,
+        rows = dy2d.numel() // self.Cop
+        if config.deterministic:
+            ns = det_slots(rows)
+            check(lib().ast_colsum_acc_det(ptr(dy2d), rows, self.Cop, self.Co, g.data_ptr() + 4 * self.b_off, dcode(dy2d.dtype),
+                                           ptr(det_ws(ns * self.Co, dy2d.device)), ns, stream()), "ast_colsum_acc_det")
+            return
+        check(lib().ast_colsum_acc(ptr(dy2d), rows, self.Cop, self.Co, g.data_ptr() + 4 * self.b_off,
                                    dcode(dy2d.dtype), stream()), "ast_colsum_acc")
 
 
@@ -489,6 +506,10 @@ class LinearFn(torch.autograd.Function):
                 check(lib().ast_skinny_gemm(ptr(dy), ptr(pw.wb), None, ptr(dx), rows, pw.Ci, pw.Cop, pw.Cop, pw.Cip, 0, stream()),
                       "ast_skinny_gemm")
             return dx, None, None, None
+        if config.deterministic:
+            # not on the train step's path (every linear there takes the skinny form): its gradient staging adds with atomics
+            raise RuntimeError("LinearFn: the non-skinny weight gradient (> 64 token rows, spectral norm or unpadded channels) has no "
+                               "deterministic form")
         g, _ = gather_direct(rows, 1, 1, pw.Cip, pw.Cop, 1, 1, 0)
         dwp = torch.zeros((pw.Cop, 1, pw.Cip), dtype=torch.float32, device=x.device)
         _wgrad(dy, x, dwp, g)
@@ -517,7 +538,10 @@ class BigLinearFn(torch.autograd.Function):
             raise RuntimeError(f"BigLinearFn: {rows} token rows > {SKINNY_MAX_ROWS}")
         y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
         ctx.big_in = K > N
-        if ctx.big_in:
+        if ctx.big_in and config.deterministic:     # per-K-chunk slabs added in chunk order
+            ws = det_ws(lib().ast_bigk_gemm_det_ws_floats(rows, N, K), x.device)
+            check(lib().ast_bigk_gemm_det(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, ptr(ws), ws.numel(), stream()), "ast_bigk_gemm_det")
+        elif ctx.big_in:
             check(lib().ast_bigk_gemm(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, N, stream()), "ast_bigk_gemm")
         else:
             check(lib().ast_skinny_gemm(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, 0, stream()), "ast_skinny_gemm")
@@ -539,7 +563,11 @@ class BigLinearFn(torch.autograd.Function):
             if ctx.big_in:
                 raise NotImplementedError("BigLinearFn: input gradient of the huge-input linear (its input is data on the reference's path)")
             dx = torch.empty_like(x)
-            check(lib().ast_bign_dgrad(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, stream()), "ast_bign_dgrad")
+            if config.deterministic:                # per-n-chunk slabs added in chunk order
+                ws = det_ws(lib().ast_bign_dgrad_det_ws_floats(rows, N, K), x.device)
+                check(lib().ast_bign_dgrad_det(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel(), stream()), "ast_bign_dgrad_det")
+            else:
+                check(lib().ast_bign_dgrad(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, stream()), "ast_bign_dgrad")
         return dx, None, None
 
 
@@ -630,11 +658,40 @@ def _clean_scratch(n, device, tag=None):
     return t
 
 
+def det_slots(rows, per=1):
+    """Deterministic mode: the fixed number of workgroup slots a reduction over `rows` uses (a function of the shape only)."""
+    return max(1, min(512 // per, (int(rows) + 255) // 256))
+
+
+def det_ws(n, device):
+    """Deterministic mode: f32 scratch for slot tables.  Every slot is written by the launch that reads it, so the contents never
+    matter (no zeroing); one buffer per (size, stream), as _clean_scratch."""
+    return _clean_scratch(max(1, int(n)), device, tag="det")
+
+
 def _stats(x):
     N, H, W, C = x.shape
     sums = stat_table(N * C * 2, x.device)
+    if config.deterministic:
+        ns = det_slots(H * W, N)
+        check(lib().ast_chan_stats_det(ptr(x), ptr(sums), N, H * W, C, dcode(x.dtype), ptr(det_ws(N * ns * C * 2, x.device)), ns, stream()),
+              "ast_chan_stats_det")
+        return sums
     check(lib().ast_chan_stats(ptr(x), ptr(sums), N, H * W, C, dcode(x.dtype), 1, stream()), "ast_chan_stats")
     return sums
+
+
+def _bwd_sums(dy, y, x, r, sums3, N, HW, C, relu, dt, scale1, shift1, scale2, shift2):
+    """ast_norm_bwd_sums_pre into a zeroed table, or its deterministic form (which overwrites the table).  The optional operands
+    may be tensors, raw device pointers or None."""
+    y, r, scale1, shift1, scale2, shift2 = (t if (t is None or isinstance(t, int)) else ptr(t) for t in (y, r, scale1, shift1, scale2, shift2))
+    if config.deterministic:
+        ns = det_slots(HW, N)
+        check(lib().ast_norm_bwd_sums_det(ptr(dy), y, ptr(x), r, ptr(sums3), N, HW, C, int(relu), dt, scale1, shift1,
+                                          scale2, shift2, ptr(det_ws(N * ns * C * 3, dy.device)), ns, stream()), "ast_norm_bwd_sums_det")
+        return
+    check(lib().ast_norm_bwd_sums_pre(ptr(dy), y, ptr(x), r, ptr(sums3), N, HW, C, int(relu), dt, 1,
+                                      scale1, shift1, scale2, shift2, stream()), "ast_norm_bwd_sums")
 
 
 class _SyncBN:
@@ -747,8 +804,7 @@ class BatchNormActFn(torch.autograd.Function):
                 tab3, rows = link.table, link.slots
             else:
                 tab3, rows = stat_table(N * C * 3, x.device), N
-                check(lib().ast_norm_bwd_sums_pre(ptr(dy), None, ptr(x), None, ptr(tab3), N, H * W, C, int(ctx.relu), dcode(x.dtype), 1,
-                                                  ptr(scale), ptr(shift), None, None, stream()), "ast_norm_bwd_sums")
+                _bwd_sums(dy, None, x, None, tab3, N, H * W, C, ctx.relu, dcode(x.dtype), scale, shift, None, None)
             dx = torch.empty_like(x)
             check(lib().ast_bn_apply_bwd(ptr(dy), ptr(x), None, ptr(dx), None, ptr(tab3), rows, N * H * W, ptr(gamma), ptr(mean), ptr(rstd),
                                          ptr(acc_grad(gamma)), ptr(acc_grad(beta)), None, None, None, None, None, ptr(scale), ptr(shift), None, None,
@@ -764,9 +820,8 @@ class BatchNormActFn(torch.autograd.Function):
             gsum = None
         else:
             sums3 = _clean_scratch(N * C * 3, x.device)
-            check(lib().ast_norm_bwd_sums_pre(ptr(dy), ptr(y), ptr(x), None, ptr(sums3), N, H * W, C, int(ctx.relu),
-                                              dcode(x.dtype), 1, ptr(scale) if pre else None, ptr(shift) if pre else None, None, None,
-                                              stream()), "ast_norm_bwd_sums")
+            _bwd_sums(dy, y, x, None, sums3, N, H * W, C, ctx.relu, dcode(x.dtype), scale if pre else None, shift if pre else None,
+                      None, None)
             gsum = _global_sums(sums3, N * C * 3) if _SyncBN.active else None
             # gamma/beta gradients come from the LOCAL sums (the gradient all-reduce averages them over ranks)
             check(lib().ast_norm_bwd_finalize(ptr(sums3), 1, N, H * W, C, gamma.numel(), ptr(gamma), ptr(mean), ptr(rstd),
@@ -831,8 +886,7 @@ class ResTailFn(torch.autograd.Function):
         dev = c2.device
         if ctx.fused:
             tab3 = stat_table(N * C * 3, dev)
-            check(lib().ast_norm_bwd_sums_pre(ptr(dy), None, ptr(c2), ptr(ds), ptr(tab3), N, H * W, C, 1, dcode(c2.dtype), 1,
-                                              ptr(s1), ptr(f1), ptr(s2), ptr(f2), stream()), "ast_norm_bwd_sums")
+            _bwd_sums(dy, None, c2, ds, tab3, N, H * W, C, 1, dcode(c2.dtype), s1, f1, s2, f2)
             dc2, dds = torch.empty_like(c2), torch.empty_like(ds)
             check(lib().ast_bn_apply_bwd(ptr(dy), ptr(c2), ptr(ds), ptr(dc2), ptr(dds), ptr(tab3), N, N * H * W, ptr(g1), ptr(m1), ptr(r1),
                                          ptr(acc_grad(g1)), ptr(acc_grad(b1)), ptr(g2), ptr(m2), ptr(r2), ptr(acc_grad(g2)), ptr(acc_grad(b2)),
@@ -840,8 +894,7 @@ class ResTailFn(torch.autograd.Function):
             return dc2, dds, None, None, None, None, None, None, None, None, None
         sums3 = _clean_scratch(N * C * 3, dev)
         coef = (ptr(s1), ptr(f1), ptr(s2), ptr(f2)) if pre else (None, None, None, None)
-        check(lib().ast_norm_bwd_sums_pre(ptr(dy), ptr(y), ptr(c2), ptr(ds), ptr(sums3), N, H * W, C, 1, dcode(c2.dtype),
-                                          1, *coef, stream()), "ast_norm_bwd_sums")
+        _bwd_sums(dy, y, c2, ds, sums3, N, H * W, C, 1, dcode(c2.dtype), *coef)
         k1 = torch.empty((C, 3), dtype=torch.float32, device=dev)
         k2 = torch.empty((N, C, 3), dtype=torch.float32, device=dev)
         gsum = _global_sums(sums3, N * C * 3) if _SyncBN.active else None
@@ -879,6 +932,11 @@ class LayerNormFn(torch.autograd.Function):
         rows, D = x2.shape
         dy2 = dy.contiguous().view(rows, D)
         dx = torch.empty_like(x2)
+        if config.deterministic:               # gamma / beta gradients from per-row partials, added in row order
+            check(lib().ast_layernorm_bwd_det(ptr(dy2), ptr(x2), ptr(ctx.gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(acc_grad(ctx.gamma)),
+                                              ptr(acc_grad(ctx.beta)), rows, D, dcode(x2.dtype), ptr(det_ws(2 * rows * D, dx.device)),
+                                              stream()), "ast_layernorm_bwd_det")
+            return dx.view(ctx.shape), None, None, None
         check(lib().ast_layernorm_bwd(ptr(dy2), ptr(x2), ptr(ctx.gamma), ptr(mean), ptr(rstd), ptr(dx),
                                       ptr(acc_grad(ctx.gamma)), ptr(acc_grad(ctx.beta)), rows, D, dcode(x2.dtype),
                                       stream()), "ast_layernorm_bwd")
@@ -938,9 +996,16 @@ class AddDropLNFn(torch.autograd.Function):
             return (ds_ext if want_dx else None), ds_ext, None, None
         dsub = torch.empty_like(s)
         ln = ctx.ln
-        check(lib().ast_add_drop_ln_bwd(ptr(dy2), ptr(ds2), ptr(s), ptr(ln.weight) if dy2 is not None else None, ptr(mean), ptr(rstd),
-                                        ptr(mask), ptr(dx), ptr(dsub), ptr(acc_grad(ln.weight)) if dy2 is not None else None,
-                                        ptr(acc_grad(ln.bias)) if dy2 is not None else None, rows, D, stream()), "ast_add_drop_ln_bwd")
+        if config.deterministic:               # gamma / beta gradients from per-row partials, added in row order
+            check(lib().ast_add_drop_ln_bwd_det(ptr(dy2), ptr(ds2), ptr(s), ptr(ln.weight) if dy2 is not None else None, ptr(mean),
+                                                ptr(rstd), ptr(mask), ptr(dx), ptr(dsub),
+                                                ptr(acc_grad(ln.weight)) if dy2 is not None else None,
+                                                ptr(acc_grad(ln.bias)) if dy2 is not None else None, rows, D,
+                                                ptr(det_ws(2 * rows * D, dsub.device)), stream()), "ast_add_drop_ln_bwd_det")
+        else:
+            check(lib().ast_add_drop_ln_bwd(ptr(dy2), ptr(ds2), ptr(s), ptr(ln.weight) if dy2 is not None else None, ptr(mean), ptr(rstd),
+                                            ptr(mask), ptr(dx), ptr(dsub), ptr(acc_grad(ln.weight)) if dy2 is not None else None,
+                                            ptr(acc_grad(ln.bias)) if dy2 is not None else None, rows, D, stream()), "ast_add_drop_ln_bwd")
         if want_dx and dx is None:
             dx = ds2
         return (dx.view(ctx.shape) if want_dx else None), dsub.view(ctx.shape), None, None
@@ -1300,12 +1365,17 @@ class ReconTotalFn(torch.autograd.Function):
         ld = tgt.stride(3)
         assert tgt.stride(2) == T * ld and tgt.stride(1) == 2 * T * ld and tgt.stride(0) == S * 2 * T * ld, \
             "target must be a [..., :F] slice of a contiguous tensor"
-        ws = torch.empty(64 * 5, dtype=torch.float32, device=out.device)          # AST_RECON_SLOTS rows of partial sums
         res = torch.empty(11, dtype=torch.float32, device=out.device)
         grad = torch.empty_like(out)
         c5, i5 = (C.c_float * 5)(*[float(c) for c in coefs]), (C.c_float * 5)(*[float(c) for c in inv])
-        check(lib().ast_recon_loss_total(ptr(out), ptr(tgt), ld, B, S, T, Fq, c5, i5, ptr(ws), ptr(res), ptr(grad), stream()),
-              "ast_recon_loss_total")
+        if config.deterministic:                   # one slot of partial sums per 256-bin workgroup, reduced in slot order
+            n = 5 * ((B * T * Fq + 255) // 256)
+            check(lib().ast_recon_loss_total_det(ptr(out), ptr(tgt), ld, B, S, T, Fq, c5, i5, ptr(det_ws(n, out.device)), n, ptr(res),
+                                                 ptr(grad), stream()), "ast_recon_loss_total_det")
+        else:
+            ws = torch.empty(64 * 5, dtype=torch.float32, device=out.device)      # AST_RECON_SLOTS rows of partial sums
+            check(lib().ast_recon_loss_total(ptr(out), ptr(tgt), ld, B, S, T, Fq, c5, i5, ptr(ws), ptr(res), ptr(grad), stream()),
+                  "ast_recon_loss_total")
         ctx.save_for_backward(grad)
         total, sums, parts = res[5], res[:5], res[6:]
         ctx.mark_non_differentiable(sums, parts)

@@ -66,6 +66,9 @@ class TrainConfig:
                                   # mode over RCCL, else f32 (env AST_GRAD_WIRE overrides)
     overlap_d: bool = True        # one GPU: discriminator phase on its own stream beside the decoder forward
     keep_grads: bool = False      # eager mode: keep a copy of the (all-reduced) generator gradient for tests
+    # bit-reproducible steps (config.deterministic): None follows the global switch at every step, True / False applies
+    # that setting to this Trainer's own eager steps and captures.  One GPU only; not with the token programs.
+    deterministic: bool | None = None
 
 
 def curriculum_gates(progress: float):
@@ -158,7 +161,12 @@ class FlatGroup:
         clip=False skips the gradient-norm pass altogether (structural: part of the graph key)."""
         if clip:
             self.gnorm_sq.zero_()
-            check(lib().ast_sumsq(ptr(self.flat_g), self.n, ptr(self.gnorm_sq), stream()), "ast_sumsq")
+            if config.deterministic:            # workgroup partials summed in order: the clip factor scales every update
+                ns = 256
+                check(lib().ast_sumsq_det(ptr(self.flat_g), self.n, ptr(self.gnorm_sq), ptr(ops.det_ws(ns, self.flat_g.device)), ns,
+                                          stream()), "ast_sumsq_det")
+            else:
+                check(lib().ast_sumsq(ptr(self.flat_g), self.n, ptr(self.gnorm_sq), stream()), "ast_sumsq")
         check(lib().ast_counter_incr(ptr(self.step), stream()), "ast_counter_incr")
         check(lib().ast_adam_dev(ptr(self.flat_p), ptr(self.flat_g), ptr(self.m), ptr(self.v), self.n, ptr(hyper), betas[0], betas[1], eps,
                                  0.0, ptr(self.step), ptr(self.gnorm_sq) if clip else None, stream()), "ast_adam_dev")
@@ -169,6 +177,7 @@ class Trainer:
         self.cfg = cfg or TrainConfig()
         self.device = torch.device(device)
         self.rank, self.world = rank, world
+        self._check_deterministic()
         torch.manual_seed(seed)                      # identical replicas on every rank
         ops._DropState.seed = 0x5EED + 1000003 * int(rank)   # ... but independent dropout masks: ranks hold different clips
         self.style, self.content = StyleEncoder(), ContentEncoder()
@@ -639,9 +648,25 @@ class Trainer:
         if side is not None:
             streams.join(torch.cuda.current_stream(), side)
 
+    def _deterministic(self):
+        return config.deterministic if self.cfg.deterministic is None else bool(self.cfg.deterministic)
+
+    def _check_deterministic(self):
+        det = self._deterministic()
+        config.check_deterministic_supported(det, self.world)
+
     def step(self, x: torch.Tensor, labels_host: torch.Tensor):
         """x: (B,S,2,287,597) f32 on the device; labels on the HOST (balanced [0]*B/2+[1]*B/2 as
         dataloader.py:143-146 builds them).  Returns a dict of detached device scalars."""
+        self._check_deterministic()
+        det = self._deterministic()
+        prev, config.deterministic = config.deterministic, det       # this step's eager launches and captures
+        try:
+            return self._step(x, labels_host)
+        finally:
+            config.deterministic = prev
+
+    def _step(self, x, labels_host):
         assert not labels_host.is_cuda, "pass labels on the host: avoids a device sync per step"
         self._sync_hyper()
         if self._dist and self._dist_in_graph is None:
@@ -753,7 +778,7 @@ class Trainer:
         c = self.cfg
         fe = tuple(t.data_ptr() for t in (self._frontend or ())) + tuple(t.data_ptr() for t in (self._frontend_cqt or ()))
         return (tuple(x.shape), tuple(labels_host.tolist()), config.compute_dtype, c.use_nce, c.use_hsic, c.use_adv, segmented,
-                tuple(c.betas), c.eps, c.max_grad_norm > 0, fe)
+                tuple(c.betas), c.eps, c.max_grad_norm > 0, fe, self._deterministic())
 
     def _mutable_state(self):
         ts = [self.G.flat_p, self.G.m, self.G.v, self.G.step, self.D.flat_p, self.D.m, self.D.v, self.D.step]

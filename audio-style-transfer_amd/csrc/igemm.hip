@@ -165,7 +165,9 @@ __device__ __forceinline__ void epi_flush(const EpiCtx<T>& ec, const ast_gather_
 // the source / weight byte deltas are then wave-uniform and live in SGPRs; per load a lane only tests one bit of a
 // per-row tap-validity mask built once, and adds the scalar delta.  (The general path costs ~7 VALU per MFMA, which
 // is what bounds the kernel: the deep layers ran at the same speed for every tile shape and K split.)
-template <typename T, int BM, int BN, int WM, int WN, int KCH, int D, int KG, bool UT>
+// DET (deterministic mode, flags bit 12): no fused statistics and split-K slices stored into their own slabs -- the instantiation
+// holds no float atomic at all (tools/det_isa_audit.py)
+template <typename T, int BM, int BN, int WM, int WN, int KCH, int D, int KG, bool UT, bool DET>
 __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ src, const T* __restrict__ wgt,
                                                      const float* __restrict__ bias, T* __restrict__ dst,
                                                      const ast_gather_t g, const int M, const int flags,
@@ -402,12 +404,12 @@ __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ s
   // flags bit 3: `ws` is a [64][Cd][2] table of per-channel (sum, sum of squares) slots and the tile adds the
   // statistics of the values it STORES (BatchNorm2d's batch statistics without a second pass over the output);
   // slot = tile index mod 64 keeps the f32 atomics off a single address per channel
-  const bool stats = (flags & 8) && !split;
+  const bool stats = !DET && (flags & 8) && !split;
   // flags bit 4: this launch is the data gradient that produces dy of a BatchNorm(+ReLU) layer whose input x (bn_x, same
   // geometry as dst) and forward coefficients are given: the tile adds the layer's backward sums (sum dz, sum dz*x, with
   // dz = dy * [fma(x, scale, shift) > 0]) of the values it stores into the [64][Cd][3] slot table `ws` -- the separate
   // pass over dy and x (ast_norm_bwd_sums) disappears.  bit 5: the layer has no ReLU (mask = 1).
-  const bool bstats = (flags & 16) && !split;
+  const bool bstats = !DET && (flags & 16) && !split;
   const bool bn_relu = !(flags & 32);
   EpiCtx<T> ec{dst, bias, ws, bn_x, bn_scale, bn_shift, HWm, rcp_hw, rcp_w, accumulate, relu, stats, bstats, bn_relu};
   float st1[TN][4], st2[TN][4];
@@ -424,8 +426,14 @@ __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ s
       for (int i = 0; i < TN; ++i) {
         const int co = bn0 + wn * WTN + i * 16 + fq * 4;
         if (co >= g.Cd) continue;
+        if constexpr (DET) {                                 // deterministic: this K slice's own slab, plain stores
+          float* wz = ws + ((size_t)blockIdx.z * M + m) * g.Cd + co;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) unsafeAtomicAdd(ws + (size_t)m * g.Cd + co + r, acc[i][j][r]);
+          for (int r = 0; r < 4; ++r) wz[r] = acc[i][j][r];
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) unsafeAtomicAdd(ws + (size_t)m * g.Cd + co + r, acc[i][j][r]);
+        }
       }
       continue;
     }
@@ -447,7 +455,7 @@ __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ s
 // in registers (TN * NKS fragments, loaded once), every wave walks `jt` pixel tiles of 16, and per tile issues its NKS
 // chunk loads (next tile's are in flight while this tile's MFMAs run), TN * NKS MFMAs, and the shared epilogue.
 // Per-lane tap decode (the 4 chunks of a K step may sit in different taps) is done once, outside the pixel loop.
-template <typename T, int TN, int NKS>
+template <typename T, int TN, int NKS, bool DET>          // DET: as igemm_kernel
 __global__ __launch_bounds__(256) void igemm_direct_kernel(const T* __restrict__ src, const T* __restrict__ wgt,
                                                            const float* __restrict__ bias, T* __restrict__ dst,
                                                            const ast_gather_t g, const int M, const int flags,
@@ -504,7 +512,7 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(const T* __restrict__
       wreg[i][ks] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(wgtR, (rowoff != OOB && woff[ks] != OOB) ? rowoff + woff[ks] : OOB, 0, 0));
   }
 
-  const bool accumulate = flags & 1, relu = flags & 2, stats = flags & 8, bstats = flags & 16, bn_relu = !(flags & 32);
+  const bool accumulate = flags & 1, relu = flags & 2, stats = !DET && (flags & 8), bstats = !DET && (flags & 16), bn_relu = !(flags & 32);
   EpiCtx<T> ec{dst, bias, ws, bn_x, bn_scale, bn_shift, HWm, rcp_hw, rcp_w, accumulate, relu, stats, bstats, bn_relu};
   float st1[TN][4], st2[TN][4];
 #pragma unroll
@@ -557,9 +565,11 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(const T* __restrict__
   if (stats || bstats) epi_flush<T, TN>(ec, g, st1, st2, tix & stat_slot_mask(flags), bn0, fr, fq, red);
 }
 
+// nslabs > 0 (deterministic mode, flags bit 12): ws holds one [M][Cd] slab per K slice, summed here in slice order and left as is
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(float* __restrict__ ws, const float* __restrict__ bias,
-                                                            T* __restrict__ dst, const ast_gather_t g, const int M, const int flags) {
+                                                            T* __restrict__ dst, const ast_gather_t g, const int M, const int flags,
+                                                            const int nslabs) {
   const int c4 = g.Cd >> 2;
   const int HWm = g.Hm * g.Wm;
   const size_t total = (size_t)M * c4;
@@ -569,8 +579,12 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(float* __restrict__ 
     const int hm = rem / g.Wm, wq = rem - hm * g.Wm;
     const size_t pix = (size_t)(n * g.Hd + hm * g.dsh + g.doh) * g.Wd + (wq * g.dsw + g.dow);
     f32x4* wp = reinterpret_cast<f32x4*>(ws + (size_t)m * g.Cd + co);
-    const f32x4 a = *wp;
-    *wp = f32x4{0.f, 0.f, 0.f, 0.f};                  // the workspace is handed back zeroed (no memset per launch)
+    f32x4 a = *wp;
+    if (nslabs > 0) {
+      for (int z = 1; z < nslabs; ++z) a += *reinterpret_cast<const f32x4*>(ws + ((size_t)z * M + m) * g.Cd + co);
+    } else {
+      *wp = f32x4{0.f, 0.f, 0.f, 0.f};                // the workspace is handed back zeroed (no memset per launch)
+    }
     float v[4] = {a[0], a[1], a[2], a[3]};
     if (bias) for (int r = 0; r < 4; ++r) v[r] += bias[co + r];
     store4<T>(dst + pix * g.Cd + co, v, flags & 1, flags & 2);
@@ -647,7 +661,7 @@ __device__ __forceinline__ void pc_store4(__amdgpu_buffer_rsrc_t r, unsigned vof
 // With WALL the weights of ALL taps of a channel slab sit in LDS beside the patch (ntaps x BN x SLB bytes), the next slab's patch
 // and weights are fetched into registers while this slab's ntaps x TM x TN x KS MFMAs run, and a slab costs two barriers
 // (hand-over of the registers to LDS) instead of ntaps.
-template <typename T, int SLB, int TM, int TN, bool WALL>
+template <typename T, int SLB, int TM, int TN, bool WALL, bool DET>          // DET: as igemm_kernel
 __global__ __launch_bounds__(256, (WALL ? 2 : (TM * TN <= 8 ? 4 : 2))) void pconv_kernel(const T* __restrict__ src, const T* __restrict__ wgt, const float* __restrict__ bias,
                                                     T* __restrict__ dst, const ast_gather_t g, const PconvPlan pp, const int flags,
                                                     float* __restrict__ ws, const unsigned src_bytes, const unsigned wgt_bytes,
@@ -885,7 +899,7 @@ __global__ __launch_bounds__(256, (WALL ? 2 : (TM * TN <= 8 ? 4 : 2))) void pcon
   // 64-bit address arithmetic), and the mode (plain / BatchNorm forward sums / backward sums) is a wave-uniform branch
   // around three straight-line bodies.  (The shared epilogue cost this kernel ~70 VALU per 4-value block and a dependent
   // bias load per block: 1 015 VALU per 144 MFMAs on the 64-channel layers.)
-  const bool accumulate = flags & 1, relu = flags & 2, stats = flags & 8, bstats = flags & 16, bn_relu = !(flags & 32);
+  const bool accumulate = flags & 1, relu = flags & 2, stats = !DET && (flags & 8), bstats = !DET && (flags & 16), bn_relu = !(flags & 32);
   const __amdgpu_buffer_rsrc_t dstR = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, dst_bytes, 0x00020000);
   f32x4 bv[TN];
   {
@@ -1076,7 +1090,8 @@ int launch_pconv(const void* src, const void* wgt, const float* bias, void* dst,
                  float* ws, const void* bn_x, const float* bn_scale, const float* bn_shift, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)pconv_kernel<T, SLB, TM, TN, WALL>, hipFuncAttributeMaxDynamicSharedMemorySize, (WALL ? 150 : 64) * 1024));
+    AST_HIP(hipFuncSetAttribute((const void*)pconv_kernel<T, SLB, TM, TN, WALL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (WALL ? 150 : 64) * 1024));
+    AST_HIP(hipFuncSetAttribute((const void*)pconv_kernel<T, SLB, TM, TN, WALL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (WALL ? 150 : 64) * 1024));
     attr_set = true;
   }
   const int tiles = g.N * pp.tiles_h * pp.tiles_w * pp.nct;
@@ -1086,8 +1101,12 @@ int launch_pconv(const void* src, const void* wgt, const float* bias, void* dst,
   // registers -- measured SLOWER, 41 -> 54 us on the 64->64-channel layer: the prefetch registers cost a wave per SIMD,
   // and what the kernel lacks is overlap between workgroups, not bandwidth)
   const int grid = (tiles + 7) / 8 * 8;
-  hipLaunchKernelGGL((pconv_kernel<T, SLB, TM, TN, WALL>), dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                     g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
+  if (flags & 4096)
+    hipLaunchKernelGGL((pconv_kernel<T, SLB, TM, TN, WALL, true>), dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
+  else
+    hipLaunchKernelGGL((pconv_kernel<T, SLB, TM, TN, WALL, false>), dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -1165,9 +1184,14 @@ int launch_direct(const void* src, const void* wgt, const float* bias, void* dst
   const int tiles = ((M + 64 * jt - 1) / (64 * jt)) * ((g.Cd + TN * 16 - 1) / (TN * 16));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  hipLaunchKernelGGL((igemm_direct_kernel<T, TN, NKS>), dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst, g,
-                     M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
-                     p.bn_shift, jt);
+  if (flags & 4096)
+    hipLaunchKernelGGL((igemm_direct_kernel<T, TN, NKS, true>), dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
+                       p.bn_shift, jt);
+  else
+    hipLaunchKernelGGL((igemm_direct_kernel<T, TN, NKS, false>), dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
+                       p.bn_shift, jt);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -1189,7 +1213,8 @@ int launch_igemm_ut(const void* src, const void* wgt, const float* bias, void* d
   static_assert(KG == 1 || (KG - 1) * (BM / 16) * (BN / 16) / 4 * 256 * 16 <= KG * 2 * (KCH / 4) * (BM + BN) * 64, "reduce buffer fits");
   static bool attr_set = false;
   if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     attr_set = true;
   }
   const int E = 16 / sizeof(T);
@@ -1199,16 +1224,21 @@ int launch_igemm_ut(const void* src, const void* wgt, const float* bias, void* d
   const int mtiles = (flags & 64) ? g.N * ((g.Hm * g.Wm + BM - 1) / BM) : (M + BM - 1) / BM;     // bit 6: image-aligned tiles
   const int tiles = mtiles * ((g.Cd + BN - 1) / BN);
   dim3 grid((tiles + 7) / 8 * 8, 1, p.nsplit);
-  if (p.nsplit > 1 && !(flags & 4)) AST_HIP(hipMemsetAsync(ws, 0, sizeof(float) * (size_t)M * g.Cd, s));
+  if (p.nsplit > 1 && !(flags & (4 | 4096))) AST_HIP(hipMemsetAsync(ws, 0, sizeof(float) * (size_t)M * g.Cd, s));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT>), grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst, g, M,
-                     flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
-                     (const T*)p.bn_x, p.bn_scale, p.bn_shift);
+  if (flags & 4096)
+    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>), grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
+                       (const T*)p.bn_x, p.bn_scale, p.bn_shift);
+  else
+    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>), grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                       g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
+                       (const T*)p.bn_x, p.bn_scale, p.bn_shift);
   if (p.nsplit > 1) {
     const size_t total = (size_t)M * (g.Cd >> 2);
     hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, s, ws, bias,
-                       (T*)dst, g, M, flags);
+                       (T*)dst, g, M, flags, (flags & 4096) ? p.nsplit : 0);
   }
   AST_CHECK_LAUNCH();
   return 0;
@@ -1233,6 +1263,17 @@ extern "C" long ast_igemm_ws_floats(const ast_gather_t* gp, int dtype) {
   }
   const IgemmPlan p = plan_igemm(*gp, M, dtype);
   return p.nsplit > 1 ? (long)M * gp->Cd : 0;
+}
+
+extern "C" long ast_igemm_ws_floats_det(const ast_gather_t* gp, int dtype) {
+  if (!gp || check_gather(gp, "ast_igemm_ws_floats_det")) return -1;
+  const int M = gp->N * gp->Hm * gp->Wm;
+  {
+    PconvPlan pp; int slb = 0, tn = 0;
+    if (plan_pconv(*gp, dtype, pp, slb, tn)) return 0;
+  }
+  const IgemmPlan p = plan_igemm(*gp, M, dtype);
+  return p.nsplit > 1 ? (long)p.nsplit * M * gp->Cd : 0;
 }
 
 extern "C" int ast_igemm_plan(const ast_gather_t* gp, int dtype, int* out5) {
@@ -1285,7 +1326,8 @@ extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias,
   // write through a bad device pointer -- a GPU fault, not an error code
   if (p.nsplit > 1) {
     if (flags & (8 | 16)) AST_FAIL("ast_igemm: fused statistics (flags 8 / 16) are not available for a split-K plan (ast_igemm_ws_floats > 0)");
-    if (!ws || ws_floats < (long)M * g.Cd) AST_FAIL("ast_igemm: this plan splits K and needs a workspace of %ld floats (ast_igemm_ws_floats), got %ld", (long)M * g.Cd, ws ? ws_floats : 0L);
+    const long need = (flags & 4096) ? (long)p.nsplit * M * g.Cd : (long)M * g.Cd;
+    if (!ws || ws_floats < need) AST_FAIL("ast_igemm: this plan splits K and needs a workspace of %ld floats (ast_igemm_ws_floats%s), got %ld", need, (flags & 4096) ? "_det" : "", ws ? ws_floats : 0L);
   }
   if ((flags & 16) && ((flags & 11) || !ws || ws_floats < (stat_slot_mask(flags) + 1L) * g.Cd * 3 || !bn_x || !bn_scale || !bn_shift))
     AST_FAIL("ast_igemm: fused BatchNorm-backward sums need plain stores, a zeroed [64][Cd][3] table and the layer's x / scale / shift");
@@ -1295,6 +1337,7 @@ extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias,
     if (!(flags & 8) || (flags & 3) || p.nsplit > 1 || direct_ok(g, p, dtype)) AST_FAIL("ast_igemm: per-image statistics (flag 64) need flag 8, plain stores and the gathered kernel (ast_igemm_plan: kch > 0, no split)");
     if (!ws || ws_floats < (long)g.N * g.Cd * 2) AST_FAIL("ast_igemm: per-image statistics need a zeroed [N][Cd][2] table");
   }
+  if ((flags & 4096) && (flags & (8 | 16 | 64))) AST_FAIL("ast_igemm: the deterministic form (flags bit 12) has no fused statistics (flags 8 / 16 / 64)");
   if (direct_ok(g, p, dtype)) { AST_DISPATCH_T(dtype, { return dispatch_direct<T>(src, wgt, bias, dst, g, M, flags, ws, p, s); }); }
 #define AST_IG(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 1>(src, wgt, bias, dst, g, M, flags, ws, p, s)
 #define AST_IG4(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 4>(src, wgt, bias, dst, g, M, flags, ws, p, s)

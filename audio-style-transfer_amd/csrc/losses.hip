@@ -11,6 +11,9 @@ constexpr float PI_F = 3.14159265358979323846f;
 // ---- compute_comprehensive_loss (new_decoder.py:348-420) ---------------------------
 // thread = one (b, t, f) complex bin, loops over the S sections so the section
 // differences stay in registers; t+-1 neighbours come from L1/L2.
+// DET (deterministic mode): workgroup b STORES its five partial sums into sums[b * 5 ..] (one slot per workgroup) instead of adding
+// them into slot b % nslots with atomics.
+template <bool DET = false>
 __global__ __launch_bounds__(1024) void recon_loss_kernel(const float* __restrict__ out, const float* __restrict__ tgt, int64_t tld,
                                                           int B, int S, int T, int Fq, float c_mse, float c_mag, float c_ph,
                                                           float c_tmp, float c_spc, float* __restrict__ sums, float* __restrict__ grad, int nslots) {
@@ -67,7 +70,11 @@ __global__ __launch_bounds__(1024) void recon_loss_kernel(const float* __restric
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const float v = block_sum(acc[k], red);
-    if (threadIdx.x == 0) unsafeAtomicAdd(sums + (blockIdx.x % nslots) * 5 + k, v);      // nslots rows of 5: few adders per address
+    if constexpr (DET) {
+      if (threadIdx.x == 0) sums[(size_t)blockIdx.x * 5 + k] = v;
+    } else {
+      if (threadIdx.x == 0) unsafeAtomicAdd(sums + (blockIdx.x % nslots) * 5 + k, v);      // nslots rows of 5: few adders per address
+    }
   }
 }
 
@@ -85,6 +92,19 @@ __global__ __launch_bounds__(64) void recon_finish_kernel(const float* __restric
   }
   __syncthreads();
   if (k == 0) out[5] = (((a.c[0] * sk[0] + a.c[1] * sk[1]) + a.c[2] * sk[2]) + a.c[3] * sk[3]) + a.c[4] * sk[4];
+}
+
+// deterministic finish over thousands of slots: wave k reduces quantity k, lane l the slots l, l + 64, ... in order, then the
+// fixed butterfly of wave_sum -- the same order on every run
+__global__ __launch_bounds__(320) void recon_finish_det_kernel(const float* __restrict__ ws, int nslots, ReconFin a, float* __restrict__ out) {
+  __shared__ float sk[5];
+  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float v = 0.f;
+  for (int i = lane; i < nslots; i += 64) v += ws[(size_t)i * 5 + k];
+  v = wave_sum(v);
+  if (lane == 0) { sk[k] = v; out[k] = v; out[6 + k] = v * a.inv[k]; }
+  __syncthreads();
+  if (threadIdx.x == 0) out[5] = (((a.c[0] * sk[0] + a.c[1] * sk[1]) + a.c[2] * sk[2]) + a.c[3] * sk[3]) + a.c[4] * sk[4];
 }
 
 // ---- InfoNCE (losses.py:9-36), one workgroup of 1024 -------------------------------
@@ -387,7 +407,7 @@ extern "C" int ast_recon_loss(const float* out, const float* tgt, int64_t tgt_ld
   // kernel's 95 us; 4608: +250 us): the same 256 K threads as 256 workgroups of 1024
   static const int max_blocks = getenv("AST_RECON_BLOCKS") ? atoi(getenv("AST_RECON_BLOCKS")) : 256;
   const int grid = (int)std::min<size_t>((total + 1023) / 1024, (size_t)std::max(1, max_blocks));
-  hipLaunchKernelGGL(recon_loss_kernel, dim3(grid), dim3(1024), 0, s, out, tgt, tgt_ld, B, S, T, Fq, c_mse, c_mag, c_phase, c_temporal,
+  hipLaunchKernelGGL(recon_loss_kernel<false>, dim3(grid), dim3(1024), 0, s, out, tgt, tgt_ld, B, S, T, Fq, c_mse, c_mag, c_phase, c_temporal,
                      c_spectral, sums, grad, 1);
   AST_CHECK_LAUNCH();
   return 0;
@@ -405,11 +425,30 @@ extern "C" int ast_recon_loss_total(const float* out, const float* tgt, int64_t 
   const size_t total = (size_t)B * T * Fq;
   if (total >= (1ull << 31)) AST_FAIL("ast_recon_loss_total: more than 2^31 bins per section");
   const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
-  hipLaunchKernelGGL(recon_loss_kernel, dim3(grid), dim3(256), 0, s, out, tgt, tgt_ld, B, S, T, Fq, coef5[0], coef5[1], coef5[2], coef5[3],
+  hipLaunchKernelGGL(recon_loss_kernel<false>, dim3(grid), dim3(256), 0, s, out, tgt, tgt_ld, B, S, T, Fq, coef5[0], coef5[1], coef5[2], coef5[3],
                      coef5[4], ws, grad, AST_RECON_SLOTS);
   ReconFin a;
   for (int k = 0; k < 5; ++k) { a.c[k] = coef5[k]; a.inv[k] = inv5[k]; }
   hipLaunchKernelGGL(recon_finish_kernel, dim3(1), dim3(64), 0, s, ws, AST_RECON_SLOTS, a, res11);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// deterministic form: one slot per workgroup (ws >= 5 * ceil(B*T*Fq / 256) floats, written completely, never zeroed), fixed-order finish
+extern "C" int ast_recon_loss_total_det(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const float* coef5,
+                                        const float* inv5, float* ws, long ws_floats, float* res11, float* grad, void* stream) {
+  if (!out || !tgt || !coef5 || !inv5 || !ws || !res11 || B <= 0 || S <= 0 || T <= 0 || Fq <= 0 || tgt_ld < Fq)
+    AST_FAIL("ast_recon_loss_total_det: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t total = (size_t)B * T * Fq;
+  if (total >= (1ull << 31)) AST_FAIL("ast_recon_loss_total_det: more than 2^31 bins per section");
+  const size_t grid = (total + 255) / 256;
+  if (grid > 65536 || ws_floats < (long)(grid * 5)) AST_FAIL("ast_recon_loss_total_det: ws needs %ld floats (at most 65536 slots)", (long)(grid * 5));
+  hipLaunchKernelGGL(recon_loss_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, out, tgt, tgt_ld, B, S, T, Fq, coef5[0], coef5[1], coef5[2],
+                     coef5[3], coef5[4], ws, grad, (int)grid);
+  ReconFin a;
+  for (int k = 0; k < 5; ++k) { a.c[k] = coef5[k]; a.inv[k] = inv5[k]; }
+  hipLaunchKernelGGL(recon_finish_det_kernel, dim3(1), dim3(320), 0, s, ws, (int)grid, a, res11);
   AST_CHECK_LAUNCH();
   return 0;
 }

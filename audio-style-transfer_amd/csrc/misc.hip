@@ -348,6 +348,30 @@ __global__ __launch_bounds__(256) void colsum_small_kernel(const T* __restrict__
     unsafeAtomicAdd(out + threadIdx.x, t);
   }
 }
+// ---- deterministic mode: per-workgroup partials stored into slots, reduced in ascending slot order ------------------------
+// out[b][i] (+)= sum_{s < nslots} parts[(b * nslots + s) * n + i], s ascending: one thread per output element, so every element is
+// summed in the same order whatever the launch's timing (the shared ordered reduce behind every *_det entry point).
+__global__ __launch_bounds__(256) void ordered_sum_kernel(const float* __restrict__ parts, size_t n, int nslots, size_t total,
+                                                          float* __restrict__ out, int accumulate) {
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < total; j += (size_t)gridDim.x * 256) {
+    const size_t b = j / n, i = j - b * n;
+    const float* p = parts + b * (size_t)nslots * n + i;
+    float a = 0.f;
+    for (int s = 0; s < nslots; ++s) a += p[(size_t)s * n];
+    out[j] = accumulate ? out[j] + a : a;
+  }
+}
+// colsum partials: slot blockIdx.y sums rows [slot * rps, (slot + 1) * rps) of column c and STORES the result (every slot row is
+// written completely, empty slices included)
+template <typename T>
+__global__ void colsum_slots_kernel(const T* __restrict__ x, size_t rows, int C, int Creal, float* __restrict__ slots, size_t rps) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= Creal) return;
+  const size_t r0 = (size_t)blockIdx.y * rps, r1 = r0 + rps < rows ? r0 + rps : rows;
+  float a = 0.f;
+  for (size_t r = r0; r < r1; ++r) a += (float)x[r * C + c];
+  slots[(size_t)blockIdx.y * Creal + c] = a;
+}
 __global__ void dropout_mask_kernel(float* __restrict__ mask, size_t n, float p, uint64_t seed, const int64_t* __restrict__ d_offset) {
   const uint64_t base = mix64(seed ^ mix64((uint64_t)(d_offset ? *d_offset : 0)));
   const float keep = 1.f / (1.f - p);
@@ -541,6 +565,26 @@ extern "C" int ast_colsum_acc(const void* x, int64_t rows, int C, int Creal, flo
                                             Creal, out, rpb));
   AST_CHECK_LAUNCH();
   return 0;
+}
+extern "C" int ast_ordered_sum(const float* parts, int64_t n, int nslots, int batches, float* out, int accumulate, void* stream) {
+  if (!parts || !out || n < 1 || nslots < 1 || nslots > AST_DET_MAX_SLOTS || batches < 1) AST_FAIL("ast_ordered_sum: bad args (n >= 1, 1..%d slots, batches >= 1)", AST_DET_MAX_SLOTS);
+  const size_t total = (size_t)n * batches;
+  hipLaunchKernelGGL(ordered_sum_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     parts, (size_t)n, nslots, total, out, accumulate ? 1 : 0);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int ast_colsum_acc_det(const void* x, int64_t rows, int C, int Creal, float* out, int dtype, float* ws, int nslots, void* stream) {
+  if (!x || !out || !ws || rows < 0 || C <= 0 || Creal < 1 || Creal > C || nslots < 1 || nslots > AST_DET_MAX_SLOTS)
+    AST_FAIL("ast_colsum_acc_det: bad args (1..%d slots)", AST_DET_MAX_SLOTS);
+  if (rows == 0) return 0;
+  const size_t rps = ((size_t)rows + nslots - 1) / nslots;
+  const int bx = Creal >= 256 ? 256 : 64;
+  dim3 grid((Creal + bx - 1) / bx, nslots);
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_slots_kernel<T>), grid, dim3(bx), 0, (hipStream_t)stream, (const T*)x, (size_t)rows, C,
+                                            Creal, ws, rps));
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, Creal, nslots, 1, out, 1, stream);
 }
 extern "C" int ast_dropout_mask(float* mask, int64_t n, float p, uint64_t seed, const int64_t* d_offset, void* stream) {
   if (!mask || n < 0 || p < 0.f || p >= 1.f) AST_FAIL("ast_dropout_mask: bad args");

@@ -12,7 +12,9 @@ namespace {
 // ---- reductions over pixels: sums[n][c][K] -------------------------------------
 // MODE 0: {x, x^2}           (K=2)   inputs: a=x
 // MODE 1: {dz, dz*x, dz*r}   (K=3)   inputs: a=dy, b=y (relu mask), c=x, d=r (may be null)
-template <typename T, int MODE>
+// DET (deterministic mode): the workgroup STORES its sums into slot row blockIdx.x of its image -- sums is then the
+// [N][gridDim.x][C][K] slot table that ast_ordered_sum reduces in slot order -- instead of adding them with atomics.
+template <typename T, int MODE, bool DET = false>
 __global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                            const T* __restrict__ c, const T* __restrict__ d,
                                                            float* __restrict__ sums, int HW, int C, int ppb, int relu,
@@ -91,7 +93,8 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ 
     for (int ch = tid; ch < U * 8; ch += 256) {
       float t = 0.f;
       for (int q = 0; q < PL; ++q) t += red[q * U * 8 + ch];
-      unsafeAtomicAdd(sums + ((size_t)n * C + ch) * K + k, t);
+      if constexpr (DET) sums[(((size_t)n * gridDim.x + blockIdx.x) * C + ch) * K + k] = t;
+      else unsafeAtomicAdd(sums + ((size_t)n * C + ch) * K + k, t);
     }
   }
 }
@@ -558,6 +561,9 @@ __global__ void layernorm_fwd_kernel(const float* __restrict__ x, const float* _
   if (lane == 0) { mean[row] = m; rstd[row] = r; }
 }
 
+// DET (deterministic mode): dgamma / dbeta point at [rows][D] partial tables and every row STORES its terms (ast_ordered_sum
+// then adds the rows in order into the parameter gradients) instead of adding them with atomics.
+template <bool DET = false>
 __global__ void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                      const float* __restrict__ rstd, float* __restrict__ dx, float* dgamma, float* dbeta,
@@ -576,8 +582,13 @@ __global__ void layernorm_bwd_kernel(const float* __restrict__ dy, const float* 
   for (int i = lane; i < D; i += 64) {
     const float xh = (xr[i] - m) * r, g = dr[i] * gamma[i];
     dx[(size_t)row * D + i] = r * (g - a - xh * b);
-    if (dgamma) unsafeAtomicAdd(dgamma + i, dr[i] * xh);
-    if (dbeta) unsafeAtomicAdd(dbeta + i, dr[i]);
+    if constexpr (DET) {
+      if (dgamma) dgamma[(size_t)row * D + i] = dr[i] * xh;
+      if (dbeta) dbeta[(size_t)row * D + i] = dr[i];
+    } else {
+      if (dgamma) unsafeAtomicAdd(dgamma + i, dr[i] * xh);
+      if (dbeta) unsafeAtomicAdd(dbeta + i, dr[i]);
+    }
   }
 }
 
@@ -614,6 +625,7 @@ __global__ void add_drop_ln_fwd_kernel(const float* __restrict__ x, const float*
 
 //   ds = ds_ext + LayerNorm_bwd(dy; s)     (either term may be absent)
 //   dx = ds,  dsub = ds * mask             (dx may alias nothing; both are plain stores)
+template <bool DET = false>                      // DET: as layernorm_bwd_kernel
 __global__ void add_drop_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ ds_ext, const float* __restrict__ s,
                                        const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
                                        const float* __restrict__ mask, float* __restrict__ dx, float* __restrict__ dsub,
@@ -635,8 +647,13 @@ __global__ void add_drop_ln_bwd_kernel(const float* __restrict__ dy, const float
     if (dy) {
       const float xh = (s[o + i] - m) * r, g = dy[o + i] * gamma[i];
       d += r * (g - a - xh * b);
-      if (dgamma) unsafeAtomicAdd(dgamma + i, dy[o + i] * xh);
-      if (dbeta) unsafeAtomicAdd(dbeta + i, dy[o + i]);
+      if constexpr (DET) {
+        if (dgamma) dgamma[o + i] = dy[o + i] * xh;
+        if (dbeta) dbeta[o + i] = dy[o + i];
+      } else {
+        if (dgamma) unsafeAtomicAdd(dgamma + i, dy[o + i] * xh);
+        if (dbeta) unsafeAtomicAdd(dbeta + i, dy[o + i]);
+      }
     }
     if (dx) dx[o + i] = d;
     dsub[o + i] = mask ? d * mask[o + i] : d;
@@ -904,7 +921,7 @@ extern "C" int ast_layernorm_bwd(const void* dy, const void* x, const float* gam
                                  void* dx, float* dgamma, float* dbeta, int rows, int D, int dtype, void* stream) {
   if (dtype != AST_F32) AST_FAIL("ast_layernorm_bwd: f32 only");
   if (!dy || !x || !gamma || !mean || !rstd || !dx || rows <= 0 || D <= 0) AST_FAIL("ast_layernorm_bwd: bad args");
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
+  hipLaunchKernelGGL(layernorm_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
                      (const float*)x, gamma, mean, rstd, (float*)dx, dgamma, dbeta, rows, D);
   AST_CHECK_LAUNCH();
   return 0;
@@ -939,8 +956,66 @@ extern "C" int ast_add_drop_ln_bwd(const float* dy, const float* ds_ext, const f
     hipLaunchKernelGGL(add_drop_ln_bwd256_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, ds_ext, s, gamma, mean, rstd,
                        mask, dx, dsub, dgamma, dbeta, rows);
   else
-    hipLaunchKernelGGL(add_drop_ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, ds_ext, s, gamma, mean, rstd,
+    hipLaunchKernelGGL(add_drop_ln_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, ds_ext, s, gamma, mean, rstd,
                        mask, dx, dsub, dgamma, dbeta, rows, D);
   AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- deterministic mode (include/ast_hip.h "Deterministic forms"): slot tables written with plain stores, reduced in slot order ----
+extern "C" int ast_ordered_sum(const float* parts, int64_t n, int nslots, int batches, float* out, int accumulate, void* stream);
+
+extern "C" int ast_chan_stats_det(const void* x, float* sums, int N, int HW, int C, int dtype, float* ws, int nslots, void* stream) {
+  if (!x || !sums || !ws || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || C > 2048 || nslots < 1 || nslots > AST_DET_MAX_SLOTS)
+    AST_FAIL("ast_chan_stats_det: bad args N=%d HW=%d C=%d slots=%d", N, HW, C, nslots);
+  hipStream_t s = (hipStream_t)stream;
+  const int ppb = (HW + nslots - 1) / nslots;
+  const float* nf = nullptr;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((chan_reduce_kernel<T, 0, true>), dim3(nslots, N), dim3(256), 0, s, (const T*)x, (const T*)nullptr,
+                                            (const T*)nullptr, (const T*)nullptr, ws, HW, C, ppb, 0, nf, nf, nf, nf));
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, (int64_t)C * 2, nslots, N, sums, 0, stream);
+}
+
+extern "C" int ast_norm_bwd_sums_det(const void* dy, const void* y, const void* x, const void* r, float* sums3, int N, int HW, int C, int relu,
+                                     int dtype, const float* scale1, const float* shift1, const float* scale2, const float* shift2, float* ws,
+                                     int nslots, void* stream) {
+  if (!dy || !x || !sums3 || !ws || (relu && !y && !scale1) || (C & 7) || C <= 0 || C > 2048 || N <= 0 || HW <= 0 || nslots < 1 ||
+      nslots > AST_DET_MAX_SLOTS)
+    AST_FAIL("ast_norm_bwd_sums_det: bad args");
+  if (scale1 && (!shift1 || (r && (!scale2 || !shift2)))) AST_FAIL("ast_norm_bwd_sums_det: incomplete pre-activation coefficients");
+  hipStream_t s = (hipStream_t)stream;
+  const int ppb = (HW + nslots - 1) / nslots;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((chan_reduce_kernel<T, 1, true>), dim3(nslots, N), dim3(256), 0, s, (const T*)dy, (const T*)y,
+                                            (const T*)x, (const T*)r, ws, HW, C, ppb, relu, scale1, shift1, scale2, shift2));
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, (int64_t)C * 3, nslots, N, sums3, 0, stream);
+}
+
+extern "C" int ast_layernorm_bwd_det(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
+                                     float* dgamma, float* dbeta, int rows, int D, int dtype, float* ws, void* stream) {
+  if (dtype != AST_F32) AST_FAIL("ast_layernorm_bwd_det: f32 only");
+  if (!dy || !x || !gamma || !mean || !rstd || !dx || !ws || rows <= 0 || rows > AST_DET_MAX_SLOTS || D <= 0)
+    AST_FAIL("ast_layernorm_bwd_det: bad args (1..%d rows)", AST_DET_MAX_SLOTS);
+  hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
+                     (const float*)x, gamma, mean, rstd, (float*)dx, dgamma ? ws : nullptr, dbeta ? ws + (size_t)rows * D : nullptr, rows, D);
+  AST_CHECK_LAUNCH();
+  if (dgamma) if (int rc = ast_ordered_sum(ws, D, rows, 1, dgamma, 1, stream)) return rc;
+  if (dbeta) if (int rc = ast_ordered_sum(ws + (size_t)rows * D, D, rows, 1, dbeta, 1, stream)) return rc;
+  return 0;
+}
+
+extern "C" int ast_add_drop_ln_bwd_det(const float* dy, const float* ds_ext, const float* s, const float* gamma, const float* mean,
+                                       const float* rstd, const float* mask, float* dx, float* dsub, float* dgamma, float* dbeta, int rows,
+                                       int D, float* ws, void* stream) {
+  if ((!dy && !ds_ext) || !dsub || rows <= 0 || rows > AST_DET_MAX_SLOTS || D <= 0) AST_FAIL("ast_add_drop_ln_bwd_det: bad args");
+  if (dy && (!s || !gamma || !mean || !rstd)) AST_FAIL("ast_add_drop_ln_bwd_det: LayerNorm state missing");
+  const bool red = dy && (dgamma || dbeta);
+  if (red && !ws) AST_FAIL("ast_add_drop_ln_bwd_det: the gamma / beta gradients need 2 * rows * D floats of ws");
+  hipLaunchKernelGGL(add_drop_ln_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, ds_ext, s, gamma, mean, rstd,
+                     mask, dx, dsub, red && dgamma ? ws : nullptr, red && dbeta ? ws + (size_t)rows * D : nullptr, rows, D);
+  AST_CHECK_LAUNCH();
+  if (red && dgamma) if (int rc = ast_ordered_sum(ws, D, rows, 1, dgamma, 1, stream)) return rc;
+  if (red && dbeta) if (int rc = ast_ordered_sum(ws + (size_t)rows * D, D, rows, 1, dbeta, 1, stream)) return rc;
   return 0;
 }

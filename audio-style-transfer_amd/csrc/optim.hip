@@ -4,6 +4,8 @@
 #include "../../include/ast_hip.h"
 
 namespace {
+// DET: the workgroup STORES its partial into out[blockIdx.x] (deterministic mode; ast_ordered_sum adds the slots in order)
+template <bool DET>
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
   __shared__ float red[17];
   float q = 0.f;
@@ -27,7 +29,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
   q += (q1 + q2) + q3;
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = x[n4 * 4 + threadIdx.x]; q += v * v; }
   q = block_sum(q, red);
-  if (threadIdx.x == 0) unsafeAtomicAdd(out, q);
+  if (threadIdx.x == 0) {
+    if constexpr (DET) out[blockIdx.x] = q;
+    else unsafeAtomicAdd(out, q);
+  }
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -110,9 +115,18 @@ extern "C" int ast_sumsq(const float* x, int64_t n, float* out, void* stream) {
   // 512 23 us, 256 21 us (5.9 TB/s) for the 31 M-parameter gradient (tools/sumsq_time.py)
   static const int max_blocks = getenv("AST_SUMSQ_BLOCKS") ? atoi(getenv("AST_SUMSQ_BLOCKS")) : 256;
   const int grid = (int)std::min<size_t>(((size_t)n / 4 + 255) / 256 + 1, (size_t)std::max(1, max_blocks));
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (size_t)n, out);
+  hipLaunchKernelGGL(sumsq_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (size_t)n, out);
   AST_CHECK_LAUNCH();
   return 0;
+}
+extern "C" int ast_ordered_sum(const float* parts, int64_t n, int nslots, int batches, float* out, int accumulate, void* stream);
+extern "C" int ast_sumsq_det(const float* x, int64_t n, float* out, float* ws, int nslots, void* stream) {
+  if (!x || !out || !ws || n < 0 || nslots < 1 || nslots > AST_DET_MAX_SLOTS) AST_FAIL("ast_sumsq_det: bad args (1..%d slots)", AST_DET_MAX_SLOTS);
+  if (n == 0) return 0;
+  if (((uintptr_t)x) & 15) AST_FAIL("ast_sumsq_det: x must be 16-byte aligned");
+  hipLaunchKernelGGL(sumsq_kernel<true>, dim3(nslots), dim3(256), 0, (hipStream_t)stream, x, (size_t)n, ws);
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, 1, nslots, 1, out, 1, stream);
 }
 extern "C" int ast_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                         const int64_t* d_step, const float* gnorm_sq, float max_norm, void* stream) {

@@ -166,6 +166,9 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
 // 4, so rows are only 8-byte aligned: lane (i, g) loads 2 floats at k = kb + 8 s + 2 g and the two MFMAs of a step
 // contract k = 2 g + e over g.  grid = (N/16, M/16, K chunks of 1024); a workgroup's 4 waves split its chunk, reduce
 // through LDS and add the 16x16 partial tile into Y with f32 atomics (Y is pre-zeroed; chunk 0 adds the bias).
+// DET (deterministic mode): K chunk z STORES its partial tile into its own [M][N] slab y + z * M * N (an ast_ordered_sum adds the
+// slabs in chunk order) instead of adding it into Y with atomics.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void bigk_gemm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias, float* __restrict__ y, int M, int N, int K,
                                                          int ldy) {
@@ -209,13 +212,18 @@ __global__ __launch_bounds__(256) void bigk_gemm_kernel(const float* __restrict_
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int n = nb + q;
-    if (n < N) unsafeAtomicAdd(y + (size_t)m * ldy + n, r[q] + ((bias && blockIdx.z == 0) ? bias[n] : 0.f));
+    if (n >= N) continue;
+    const float v = r[q] + ((bias && blockIdx.z == 0) ? bias[n] : 0.f);
+    if constexpr (DET) y[((size_t)blockIdx.z * M + m) * N + n] = v;
+    else unsafeAtomicAdd(y + (size_t)m * ldy + n, v);
   }
 }
 
 // dX[m][k] += sum_n dY[m][n] W[n][k]   (data gradient of embedding_to_stft: N = 2*287*513 contracted, K = 256 kept).
 // A workgroup owns a chunk of 512 n for ALL k: wave w keeps the k tiles 4w..4w+3 (D[k][m] = sum_n W[n][k] dY[m][n];
 // lane (i, g): A = W[nb + 4 s + g][k0 + i], 16 lanes = 64 contiguous bytes of a weight row; B = dY[m0 + i][nb + 4 s + g]).
+// DET: n chunk blockIdx.x STORES its partial into its own [M][K] slab dx + blockIdx.x * M * K (summed in chunk order afterwards)
+template <bool DET = false>
 __global__ __launch_bounds__(256) void bign_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                           float* __restrict__ dx, int M, int N, int K, int lddy) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -261,7 +269,9 @@ __global__ __launch_bounds__(256) void bign_dgrad_kernel(const float* __restrict
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k = (kt0 + t) * 16 + 4 * g + r;
-      if (k < K) unsafeAtomicAdd(dx + (size_t)m * K + k, acc[t][r]);
+      if (k >= K) continue;
+      if constexpr (DET) dx[((size_t)blockIdx.x * M + m) * K + k] = acc[t][r];
+      else unsafeAtomicAdd(dx + (size_t)m * K + k, acc[t][r]);
     }
 }
 
@@ -422,7 +432,7 @@ extern "C" int ast_bigk_gemm(const float* x, const float* w, const float* bias, 
   if ((((uintptr_t)x) | ((uintptr_t)w)) & 7) AST_FAIL("ast_bigk_gemm: operands must be 8-byte aligned");
   dim3 grid((N + 15) / 16, (M + 15) / 16, (K + 1023) / 1024);
   AST_HIP(hipMemsetAsync(y, 0, sizeof(float) * (size_t)M * ldy, (hipStream_t)stream));
-  hipLaunchKernelGGL(bigk_gemm_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, M, N, K, ldy);
+  hipLaunchKernelGGL(bigk_gemm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, M, N, K, ldy);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -431,7 +441,43 @@ extern "C" int ast_bign_dgrad(const float* dy, const float* w, float* dx, int M,
   if (!dy || !w || !dx || M < 1 || M > 64 || N < 1 || K < 1 || K > 256) AST_FAIL("ast_bign_dgrad: bad args M=%d N=%d K=%d (K <= 256)", M, N, K);
   dim3 grid((N + 511) / 512, (M + 15) / 16);
   AST_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)M * K, (hipStream_t)stream));
-  hipLaunchKernelGGL(bign_dgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, w, dx, M, N, K, lddy);
+  hipLaunchKernelGGL(bign_dgrad_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, dy, w, dx, M, N, K, lddy);
   AST_CHECK_LAUNCH();
   return 0;
+}
+
+// ---- deterministic forms (include/ast_hip.h): per-chunk slabs in ws, added in chunk order -----------------------------------
+extern "C" int ast_ordered_sum(const float* parts, int64_t n, int nslots, int batches, float* out, int accumulate, void* stream);
+
+extern "C" long ast_bigk_gemm_det_ws_floats(int M, int N, int K) {
+  if (M < 1 || M > 64 || N < 1 || K < 2) return -1;
+  return (long)((K + 1023) / 1024) * M * N;
+}
+
+extern "C" int ast_bigk_gemm_det(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, float* ws, long ws_floats,
+                                 void* stream) {
+  if (!x || !w || !y || !ws || M < 1 || M > 64 || N < 1 || K < 2 || (K & 1)) AST_FAIL("ast_bigk_gemm_det: bad args M=%d N=%d K=%d (K must be even)", M, N, K);
+  if ((((uintptr_t)x) | ((uintptr_t)w)) & 7) AST_FAIL("ast_bigk_gemm_det: operands must be 8-byte aligned");
+  const int nz = (K + 1023) / 1024;
+  if (nz > AST_DET_MAX_SLOTS || ws_floats < (long)nz * M * N) AST_FAIL("ast_bigk_gemm_det: ws needs %ld floats", (long)nz * M * N);
+  dim3 grid((N + 15) / 16, (M + 15) / 16, nz);
+  hipLaunchKernelGGL(bigk_gemm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, ws, M, N, K, N);
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, (int64_t)M * N, nz, 1, y, 0, stream);
+}
+
+extern "C" long ast_bign_dgrad_det_ws_floats(int M, int N, int K) {
+  if (M < 1 || M > 64 || N < 1 || K < 1 || K > 256) return -1;
+  return (long)((N + 511) / 512) * M * K;
+}
+
+extern "C" int ast_bign_dgrad_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, float* ws, long ws_floats,
+                                  void* stream) {
+  if (!dy || !w || !dx || !ws || M < 1 || M > 64 || N < 1 || K < 1 || K > 256) AST_FAIL("ast_bign_dgrad_det: bad args M=%d N=%d K=%d (K <= 256)", M, N, K);
+  const int nx = (N + 511) / 512;
+  if (nx > AST_DET_MAX_SLOTS || ws_floats < (long)nx * M * K) AST_FAIL("ast_bign_dgrad_det: ws needs %ld floats", (long)nx * M * K);
+  dim3 grid(nx, (M + 15) / 16);
+  hipLaunchKernelGGL(bign_dgrad_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dy, w, ws, M, N, K, lddy);
+  AST_CHECK_LAUNCH();
+  return ast_ordered_sum(ws, (int64_t)M * K, nx, 1, dx, 0, stream);
 }

@@ -359,12 +359,19 @@ __device__ __forceinline__ void tile_load_dwp(const ast_weight_desc_t& d, int co
   }
 }
 
-__global__ __launch_bounds__(256) void flush_inner_tiles_kernel(const ast_weight_desc_t* __restrict__ descs, const WTile* __restrict__ tiles) {
+// DET (deterministic mode): tile b STORES its share of the inner product into part[b] (0 for weights without spectral norm) and
+// inner_sum_det_kernel adds a weight's tiles in list order, instead of every tile adding into d.inner with an atomic.
+template <bool DET = false>
+__global__ __launch_bounds__(256) void flush_inner_tiles_kernel(const ast_weight_desc_t* __restrict__ descs, const WTile* __restrict__ tiles,
+                                                                float* __restrict__ part) {
   __shared__ float G[9 * TL * LP];
   __shared__ float red[17];
   const WTile tl = tiles[blockIdx.x];
   const ast_weight_desc_t d = descs[tl.w];
-  if (!d.dwp || !d.u) return;
+  if (!d.dwp || !d.u) {
+    if constexpr (DET) { if (threadIdx.x == 0) part[blockIdx.x] = 0.f; }
+    return;
+  }
   float q = 0.f;
   auto body = [&](auto kkc) __attribute__((always_inline)) {
     constexpr int KKC = decltype(kkc)::value;
@@ -402,7 +409,25 @@ __global__ __launch_bounds__(256) void flush_inner_tiles_kernel(const ast_weight
   else if (d.KK == 1) body(std::integral_constant<int, 1>{});
   else body(std::integral_constant<int, 0>{});
   q = block_sum(q, red);
-  if (threadIdx.x == 0 && q != 0.f) unsafeAtomicAdd(d.inner, q / d.sigma[0]);
+  if constexpr (DET) {
+    if (threadIdx.x == 0) part[blockIdx.x] = q / d.sigma[0];
+  } else {
+    if (threadIdx.x == 0 && q != 0.f) unsafeAtomicAdd(d.inner, q / d.sigma[0]);
+  }
+}
+
+// the first tile of every weight (tiles of a weight are consecutive in the list) sums that weight's partials in list order
+__global__ __launch_bounds__(256) void inner_sum_det_kernel(const ast_weight_desc_t* __restrict__ descs, const WTile* __restrict__ tiles,
+                                                            const float* __restrict__ part, int ntiles) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= ntiles) return;
+  const int w = tiles[t].w;
+  if (t > 0 && tiles[t - 1].w == w) return;
+  const ast_weight_desc_t d = descs[w];
+  if (!d.dwp || !d.u) return;
+  float v = 0.f;
+  for (int i = t; i < ntiles && tiles[i].w == w; ++i) v += part[i];
+  d.inner[0] = v;
 }
 
 __global__ __launch_bounds__(256) void flush_unpack_tiles_kernel(const ast_weight_desc_t* __restrict__ descs, const WTile* __restrict__ tiles) {
@@ -473,7 +498,18 @@ extern "C" int ast_weights_prepare_t(const ast_weight_desc_t* descs, const int* 
 extern "C" int ast_weight_grads_flush_t(const ast_weight_desc_t* descs, const void* tiles, int ntiles, void* stream) {
   if (!descs || !tiles || ntiles <= 0) AST_FAIL("ast_weight_grads_flush_t: bad args");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(flush_inner_tiles_kernel, dim3(ntiles), dim3(256), 0, s, descs, (const WTile*)tiles);
+  hipLaunchKernelGGL(flush_inner_tiles_kernel<false>, dim3(ntiles), dim3(256), 0, s, descs, (const WTile*)tiles, (float*)nullptr);
+  hipLaunchKernelGGL(flush_unpack_tiles_kernel, dim3(ntiles), dim3(256), 0, s, descs, (const WTile*)tiles);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// deterministic form of the flush: the inner products through per-tile partials (ws >= ntiles floats) summed in tile order
+extern "C" int ast_weight_grads_flush_det(const ast_weight_desc_t* descs, const void* tiles, int ntiles, float* ws, long ws_floats, void* stream) {
+  if (!descs || !tiles || !ws || ntiles <= 0 || ws_floats < ntiles) AST_FAIL("ast_weight_grads_flush_det: bad args (ws >= ntiles floats)");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(flush_inner_tiles_kernel<true>, dim3(ntiles), dim3(256), 0, s, descs, (const WTile*)tiles, ws);
+  hipLaunchKernelGGL(inner_sum_det_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, s, descs, (const WTile*)tiles, (const float*)ws, ntiles);
   hipLaunchKernelGGL(flush_unpack_tiles_kernel, dim3(ntiles), dim3(256), 0, s, descs, (const WTile*)tiles);
   AST_CHECK_LAUNCH();
   return 0;

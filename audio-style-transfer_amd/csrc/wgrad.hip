@@ -104,7 +104,8 @@ template <> struct WgradCfg<float> { static constexpr int BKP = 32, PAD = 16; };
 
 // PG pixel groups of 4 waves per workgroup, as in wgrad_halo_kernel: group pg takes every PG-th K tile of the workgroup's pixel
 // slice through its own LDS staging, partial tiles are summed through LDS, one atomic flush per workgroup.
-template <typename T, int BMW, int NCT, int PG>
+// SLAB: the slab-mode instantiation (ast_wgrad_slab): its flush is plain stores only, no float atomic in the code object
+template <typename T, int BMW, int NCT, int PG, bool SLAB>
 __global__ __launch_bounds__(256 * PG) void wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ src,
                                                      float* __restrict__ dw, const ast_gather_t g,
                                                      const int P, const int pps, const unsigned dy_bytes,
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256 * PG) void wgrad_kernel(const T* __restrict__ d
   WG_STAMP(3);
   dw += (size_t)(bz % (nrep & 0xffff)) * rep_stride;          // this pixel slice's gradient replica / slab (nrep bits 16-17: flush mode)
   flush_tile_rows<BMW, NCT, RT, CTW>(acc, reinterpret_cast<float*>(wl_all), dw, g, cd0, col0, ncols, wave, lane,
-                                     [&](int t) { return taptab[t] >> 16; }, (nrep >> 16) & 3);
+                                     [&](int t) { return taptab[t] >> 16; }, SLAB ? 2 : (nrep >> 16) & 3);
 #ifdef AST_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the atomics have been acknowledged
 #endif
@@ -334,7 +335,8 @@ int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather
   constexpr int LDS = std::max(std::max(PG * GROUP, RED), BMW * NCT * 16 * 4) + 64;
   static bool attr_set = false;
   if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, BMW, NCT, PG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, BMW, NCT, PG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, BMW, NCT, PG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     attr_set = true;
   }
   const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
@@ -352,8 +354,12 @@ int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const int total = gx * gy * nsplit;
   g_wg_slices = nsplit;
-  hipLaunchKernelGGL((wgrad_kernel<T, BMW, NCT, PG>), dim3((total + 7) / 8 * 8), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P, pps,
-                     dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  if (g_wg_slab)
+    hipLaunchKernelGGL((wgrad_kernel<T, BMW, NCT, PG, true>), dim3((total + 7) / 8 * 8), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P,
+                       pps, dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  else
+    hipLaunchKernelGGL((wgrad_kernel<T, BMW, NCT, PG, false>), dim3((total + 7) / 8 * 8), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P,
+                       pps, dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -385,7 +391,7 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int row_swz(int r) { return (((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1; }
 
-template <int NST>
+template <int NST, bool SLAB>                                       // SLAB: as wgrad_kernel
 __global__ __launch_bounds__(256, 2) void wgrad_rows_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ src, float* __restrict__ dw,
                                                             const ast_gather_t g, const int P, const int pps, const unsigned dy_bytes,
                                                             const unsigned src_bytes, const float rcp_hw, const float rcp_w, const int gx,
@@ -562,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_rows_kernel(const bf16_t* __rest
 
   // flush: column tile j of wave w = tap (kh, kw = j), source channels cs0 + 16 w + li; rows = output channels cd0 + 16 i + 4 gq + r
   dw += (size_t)(bz % (nrep & 0xffff)) * rep_stride;
-  const int mode = (nrep >> 16) & 3;
+  const int mode = SLAB ? 2 : (nrep >> 16) & 3;
   const int wts[3] = {wt0, wt1, wt2};
   if (mode == 0) {
 #pragma unroll
@@ -618,7 +624,8 @@ int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gath
   constexpr int LDS = (NST * STAGE > 64 * 192 * 4 ? NST * STAGE : 64 * 192 * 4) + 64;
   static bool attr_set = false;
   if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_rows_kernel<NST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_rows_kernel<NST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_rows_kernel<NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     attr_set = true;
   }
   const int gx = g.Cd / 64, gy = 3 * (g.Cs / 64);
@@ -634,8 +641,12 @@ int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gath
   const unsigned src_bytes = (unsigned)((size_t)P * g.Cs * 2);
   const int total = gx * gy * nsplit;
   g_wg_slices = nsplit;
-  hipLaunchKernelGGL(wgrad_rows_kernel<NST>, dim3((total + 7) / 8 * 8), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, pps,
-                     dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  if (g_wg_slab)
+    hipLaunchKernelGGL((wgrad_rows_kernel<NST, true>), dim3((total + 7) / 8 * 8), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, pps,
+                       dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  else
+    hipLaunchKernelGGL((wgrad_rows_kernel<NST, false>), dim3((total + 7) / 8 * 8), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, pps,
+                       dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -667,7 +678,7 @@ struct WHaloPlan { int PH, PW, dhmin, dwmin, tiles_h, tiles_w, ntiles, lds; };
 // through its OWN LDS staging and accumulators, and the groups' partial tiles are summed through LDS before ONE atomic flush per
 // workgroup.  Same-address f32 atomics serialise (~38 ns per workgroup per address on the 16x72 gradient of the 2.4 M-pixel
 // layer: 768 -> 3072 workgroups took 77 -> 164 us), so parallelism has to come from waves per workgroup, not from workgroups.
-template <typename T, int BMW, int NCT, int PG>
+template <typename T, int BMW, int NCT, int PG, bool SLAB>          // SLAB: as wgrad_kernel
 __global__ __launch_bounds__(256 * PG) void wgrad_halo_kernel(const T* __restrict__ dy, const T* __restrict__ src,
                                                           float* __restrict__ dw, const ast_gather_t g, const WHaloPlan hp,
                                                           const unsigned dy_bytes, const unsigned src_bytes, const int nrep, const long rep_stride) {
@@ -864,7 +875,7 @@ __global__ __launch_bounds__(256 * PG) void wgrad_halo_kernel(const T* __restric
   }
   dw += (size_t)(blockIdx.z % (nrep & 0xffff)) * rep_stride;      // this slice's gradient replica / slab (see g_wg_nrep)
   flush_tile_rows<BMW, NCT, RT, CTW>(acc, reinterpret_cast<float*>(wl_all), dw, g, cd0, col0, ncols, wave, lane,
-                                     [&](int t) { return taptab[16 + t]; }, (nrep >> 16) & 3);
+                                     [&](int t) { return taptab[16 + t]; }, SLAB ? 2 : (nrep >> 16) & 3);
 }
 
 bool plan_wgrad_halo(const ast_gather_t& g, int dtype, int nct, int bmw, WHaloPlan& hp) {
@@ -896,7 +907,8 @@ int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_g
   const int lds = std::max(std::max(PG * hp.lds, PG > 1 ? RED : 0), BMW * NCT * 16 * 4) + 160;
   static int attr_lds = 0;
   if (lds > attr_lds) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, BMW, NCT, PG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, BMW, NCT, PG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    AST_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, BMW, NCT, PG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_lds = 160 * 1024;
   }
   const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
@@ -909,8 +921,12 @@ int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_g
   g_wg_slices = gz;
   const unsigned dy_bytes = (unsigned)((size_t)g.N * g.Hm * g.Wm * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  hipLaunchKernelGGL((wgrad_halo_kernel<T, BMW, NCT, PG>), dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp,
-                     dy_bytes, src_bytes, wg_nrep_arg(), g_wg_rep_stride);
+  if (g_wg_slab)
+    hipLaunchKernelGGL((wgrad_halo_kernel<T, BMW, NCT, PG, true>), dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp,
+                       dy_bytes, src_bytes, wg_nrep_arg(), g_wg_rep_stride);
+  else
+    hipLaunchKernelGGL((wgrad_halo_kernel<T, BMW, NCT, PG, false>), dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp,
+                       dy_bytes, src_bytes, wg_nrep_arg(), g_wg_rep_stride);
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -92,7 +92,8 @@ int ast_wgrad_rep(const void* dy, const void* src, float* dw, const ast_gather_t
  * stores, no atomics) its partial gradient into its own copy of dW -- slabs[z * Cd*wtaps*Cs ...] for slice z; *slices_out = the
  * number of copies written (every one of them completely: nothing needs to be zeroed first).  ast_slab_sum adds the copies up:
  * copy 0 <- sum of the first slabs[i] copies of record i, for up to AST_MAX_SLAB_RECS weights in ONE launch (bases / floats_per_copy /
- * slabs are HOST arrays).  NOT an accumulate: a weight used twice in one backward pass must use ast_wgrad / ast_wgrad_rep. */
+ * slabs are HOST arrays).  NOT an accumulate: a weight used twice in one backward pass must use ast_wgrad / ast_wgrad_rep.
+ * (Deterministic mode routes every convolution weight gradient through these two calls.) */
 #define AST_MAX_SLAB_RECS 48
 int ast_wgrad_slab(const void* dy, const void* src, float* slabs, const ast_gather_t* g, int dtype, int nslabs, int* slices_out,
                    void* stream);
@@ -391,6 +392,50 @@ int ast_cqt_sections(const float* cqt, int Bc, int T, int nb, const float* mean,
  * kern = its sinc_interp_hann bank) and the halving resample between CQT octaves (orig=2, nnew=1). */
 int ast_resample_poly(const float* x, int B, int n, const float* kern, int orig, int nnew, int klen, int width, float* y, int m,
                       float gain, void* stream);
+
+/* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
+ * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
+ * workgroup's partial into a slot indexed by its workgroup / tile / row id (plain stores; every slot is written on every call, so
+ * nothing needs to be zeroed first) and reduce the slots in ascending order, so two calls on the same inputs give bit-identical
+ * results whatever the launch timing.  ws is f32 scratch owned by the caller; nslots is the caller's (fixed) number of slots,
+ * 1 .. AST_DET_MAX_SLOTS.  Elsewhere in this header: ast_igemm flags bit 12 and ast_igemm_ws_floats_det (split-K slabs), and
+ * ast_wgrad_slab + ast_slab_sum (weight gradients).  Every kernel these forms launch is an instantiation without float atomics
+ * (compile-time DET / SLAB template parameters; tools/det_isa_audit.py checks the code objects). */
+#define AST_DET_MAX_SLOTS 65536
+#define AST_IGEMM_DETERMINISTIC 4096
+/* out[b][i] (+)= sum_{s < nslots} parts[(b*nslots + s)*n + i], s ascending (accumulate: add to out, else overwrite) */
+int ast_ordered_sum(const float* parts, int64_t n, int nslots, int batches, float* out, int accumulate, void* stream);
+/* ast_igemm with flags bit 12 (on EVERY call in deterministic mode: it selects the atomic-free kernel instantiations): the split-K slices STORE into their own [M][Cd] slab of ws (nslices * M * Cd floats: this function,
+ * 0 when the plan does not split K) and the finish pass sums them in slice order; fused statistics (flags 8/16/64) are refused. */
+long ast_igemm_ws_floats_det(const ast_gather_t* g, int dtype);
+/* ast_sumsq: out[0] += sum x^2 through nslots workgroup partials (ws >= nslots floats) */
+int ast_sumsq_det(const float* x, int64_t n, float* out, float* ws, int nslots, void* stream);
+/* ast_colsum_acc: out[c] += sum_r x[r][c] through nslots row-slice partials (ws >= nslots * Creal floats) */
+int ast_colsum_acc_det(const void* x, int64_t rows, int C, int Creal, float* out, int dtype, float* ws, int nslots, void* stream);
+/* ast_chan_stats: sums[n][c] = {sum x, sum x^2}, overwritten (no zeroing needed); ws >= N * nslots * C * 2 floats */
+int ast_chan_stats_det(const void* x, float* sums, int N, int HW, int C, int dtype, float* ws, int nslots, void* stream);
+/* ast_norm_bwd_sums_pre: sums3[n][c] = {sum dz, sum dz*x, sum dz*r}, overwritten; ws >= N * nslots * C * 3 floats */
+int ast_norm_bwd_sums_det(const void* dy, const void* y, const void* x, const void* r, float* sums3, int N, int HW, int C, int relu,
+                          int dtype, const float* scale1, const float* shift1, const float* scale2, const float* shift2, float* ws,
+                          int nslots, void* stream);
+/* ast_layernorm_bwd / ast_add_drop_ln_bwd: dgamma / dbeta ADDED from per-row partials (one slot per row, rows <= AST_DET_MAX_SLOTS),
+ * ws >= 2 * rows * D floats */
+int ast_layernorm_bwd_det(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
+                          float* dgamma, float* dbeta, int rows, int D, int dtype, float* ws, void* stream);
+int ast_add_drop_ln_bwd_det(const float* dy, const float* ds_ext, const float* s, const float* gamma, const float* mean,
+                            const float* rstd, const float* mask, float* dx, float* dsub, float* dgamma, float* dbeta, int rows,
+                            int D, float* ws, void* stream);
+/* ast_recon_loss_total with one slot per 256-bin workgroup: ws >= 5 * ceil(B*T*Fq / 256) floats (ws_floats checked) */
+int ast_recon_loss_total_det(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const float* coef5,
+                             const float* inv5, float* ws, long ws_floats, float* res11, float* grad, void* stream);
+/* ast_bigk_gemm / ast_bign_dgrad (decoder="simple"): every K chunk (n chunk) stores its partial into its own [M][N] ([M][K]) slab of
+ * ws (the *_ws_floats functions; <0 on bad sizes), summed in chunk order into y / dx (overwritten; ast_bigk_gemm_det needs ldy == N) */
+long ast_bigk_gemm_det_ws_floats(int M, int N, int K);
+int ast_bigk_gemm_det(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, float* ws, long ws_floats, void* stream);
+long ast_bign_dgrad_det_ws_floats(int M, int N, int K);
+int ast_bign_dgrad_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, float* ws, long ws_floats, void* stream);
+/* ast_weight_grads_flush_t with the <dWp, W/sigma> inner products through per-tile partials (ws >= ntiles floats) summed in tile order */
+int ast_weight_grads_flush_det(const ast_weight_desc_t* descs, const void* tiles, int ntiles, float* ws, long ws_floats, void* stream);
 
 /* ---- token programs: transformer layers in one launch (csrc/tokprog.hip) ------------------------------------------------
  * Replaces, for the <= 64 token rows of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
