@@ -8,6 +8,7 @@ return None for them -- there is no second pass over the 31 M parameters.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 
@@ -248,7 +249,6 @@ def _wgrad_launch(dy, src, dwp, g, replicas=1, pw=None):
         e0.record()
     if pw is not None and pw.slab:                 # dwp holds `replicas` copies: one per pixel slice, plain stores; the bank sums them
                                                    # (deterministic mode: every convolution weight, WeightBank._build)
-        import ctypes
         slices = ctypes.c_int32(0)
         used = pw.bank.slab_used(pw)               # a weight used again in this backward: its next group of copies
         if used >= replicas:

@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <atomic>
+#include <initializer_list>
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -21,6 +24,25 @@ void ast_set_error(const char* fmt, ...);
     if (e_ != hipSuccess) { ast_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return -2; } } while (0)
 #define AST_HIP(x) do { hipError_t e_ = (x); \
     if (e_ != hipSuccess) { ast_set_error("%s:%d %s: %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); return -3; } } while (0)
+
+// ---- tuning knobs from the environment (host side): unset -> fallback, set -> atoi; a flag is "set and non-zero"
+inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }
+inline bool env_flag(const char* name, bool fallback) { const char* e = getenv(name); return e ? atoi(e) != 0 : fallback; }
+
+// ---- hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute: set it on a launcher's kernels the first time
+// the launcher runs on each device.  One static object per launcher instantiation; ordinals past the table set it every time.
+struct LdsAttrOnce {
+  std::atomic<bool> done[16] = {};
+  int set(int bytes, std::initializer_list<const void*> kernels) {
+    int dev = 0;
+    AST_HIP(hipGetDevice(&dev));
+    const bool tracked = dev >= 0 && dev < 16;
+    if (tracked && done[dev].load(std::memory_order_acquire)) return 0;
+    for (const void* k : kernels) AST_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (tracked) done[dev].store(true, std::memory_order_release);
+    return 0;
+  }
+};
 
 // ---- 8-channel unit load/store (NHWC tensors keep C a multiple of 8)
 template <typename T> struct U8;

@@ -1088,12 +1088,8 @@ bool plan_pconv(const ast_gather_t& g, int dtype, PconvPlan& pp, int& slb, int& 
 template <typename T, int SLB, int TM, int TN, bool WALL>
 int launch_pconv(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, const PconvPlan& pp, int flags,
                  float* ws, const void* bn_x, const float* bn_scale, const float* bn_shift, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)pconv_kernel<T, SLB, TM, TN, WALL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (WALL ? 150 : 64) * 1024));
-    AST_HIP(hipFuncSetAttribute((const void*)pconv_kernel<T, SLB, TM, TN, WALL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (WALL ? 150 : 64) * 1024));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set((WALL ? 150 : 64) * 1024, {(const void*)pconv_kernel<T, SLB, TM, TN, WALL, false>, (const void*)pconv_kernel<T, SLB, TM, TN, WALL, true>})) return rc;
   const int tiles = g.N * pp.tiles_h * pp.tiles_w * pp.nct;
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
@@ -1101,12 +1097,9 @@ int launch_pconv(const void* src, const void* wgt, const float* bias, void* dst,
   // registers -- measured SLOWER, 41 -> 54 us on the 64->64-channel layer: the prefetch registers cost a wave per SIMD,
   // and what the kernel lacks is overlap between workgroups, not bandwidth)
   const int grid = (tiles + 7) / 8 * 8;
-  if (flags & 4096)
-    hipLaunchKernelGGL((pconv_kernel<T, SLB, TM, TN, WALL, true>), dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
-  else
-    hipLaunchKernelGGL((pconv_kernel<T, SLB, TM, TN, WALL, false>), dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
+  const auto k = (flags & 4096) ? pconv_kernel<T, SLB, TM, TN, WALL, true> : pconv_kernel<T, SLB, TM, TN, WALL, false>;      // bit 12: DET
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                     g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -1184,14 +1177,10 @@ int launch_direct(const void* src, const void* wgt, const float* bias, void* dst
   const int tiles = ((M + 64 * jt - 1) / (64 * jt)) * ((g.Cd + TN * 16 - 1) / (TN * 16));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  if (flags & 4096)
-    hipLaunchKernelGGL((igemm_direct_kernel<T, TN, NKS, true>), dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
-                       p.bn_shift, jt);
-  else
-    hipLaunchKernelGGL((igemm_direct_kernel<T, TN, NKS, false>), dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
-                       p.bn_shift, jt);
+  const auto k = (flags & 4096) ? igemm_direct_kernel<T, TN, NKS, true> : igemm_direct_kernel<T, TN, NKS, false>;      // bit 12: DET
+  hipLaunchKernelGGL(k, dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                     g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
+                     p.bn_shift, jt);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -1211,12 +1200,8 @@ int launch_igemm_ut(const void* src, const void* wgt, const float* bias, void* d
                  float* ws, const IgemmPlan& p, hipStream_t s) {
   constexpr int LDS = KG * 2 * (KCH / 4) * (BM + BN) * 64 + 64;
   static_assert(KG == 1 || (KG - 1) * (BM / 16) * (BN / 16) / 4 * 256 * 16 <= KG * 2 * (KCH / 4) * (BM + BN) * 64, "reduce buffer fits");
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    AST_HIP(hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(LDS, {(const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>, (const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>})) return rc;
   const int E = 16 / sizeof(T);
   const int cpc = g.Cs / E;
   int shift = -1;
@@ -1227,14 +1212,10 @@ int launch_igemm_ut(const void* src, const void* wgt, const float* bias, void* d
   if (p.nsplit > 1 && !(flags & (4 | 4096))) AST_HIP(hipMemsetAsync(ws, 0, sizeof(float) * (size_t)M * g.Cd, s));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  if (flags & 4096)
-    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>), grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
-                       (const T*)p.bn_x, p.bn_scale, p.bn_shift);
-  else
-    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>), grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                       g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
-                       (const T*)p.bn_x, p.bn_scale, p.bn_shift);
+  const auto k = (flags & 4096) ? igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true> : igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>;      // bit 12: DET
+  hipLaunchKernelGGL(k, grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
+                     g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
+                     (const T*)p.bn_x, p.bn_scale, p.bn_shift);
   if (p.nsplit > 1) {
     const size_t total = (size_t)M * (g.Cd >> 2);
     hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, s, ws, bias,

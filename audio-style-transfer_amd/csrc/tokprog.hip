@@ -591,17 +591,10 @@ extern "C" int ast_tok_program(const ast_tok_op_t* ops, int nops, int G, int xcd
   for (int k = 0; k < nops; ++k)
     if (ops[k].type == AST_TOK_GEMM) mt = std::max(mt, ops[k].i[0] <= 16 ? 1 : (ops[k].i[0] <= 32 ? 2 : 4));
   const int lds = tok_lds_bytes(mt);
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)tok_program_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tok_lds_bytes(4)));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr, attr_op;
+  if (int rc = attr.set(tok_lds_bytes(4), {(const void*)tok_program_kernel})) return rc;
   if (per_op) {
-    static bool attr1 = false;
-    if (!attr1) {
-      AST_HIP(hipFuncSetAttribute((const void*)tok_op_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tok_lds_bytes(4)));
-      attr1 = true;
-    }
+    if (int rc = attr_op.set(tok_lds_bytes(4), {(const void*)tok_op_kernel})) return rc;
     for (int k = 0; k < nops; ++k) {
       const ast_tok_op_t& op = ops[k];
       int grid = 1, l = 0;

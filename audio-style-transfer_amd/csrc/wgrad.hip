@@ -1,6 +1,7 @@
 // Weight gradients of the gathered GEMMs (Conv2d / ConvTranspose2d / Linear): dw[cd][wtap][c] += sum_pix dy[pix][cd] * src[gather(pix,tap)][c].
 // Split from igemm.hip (same data layout and geometry struct: see its header comment).
 #include "gemm_common.h"
+#include <limits.h>
 
 namespace {
 
@@ -92,12 +93,33 @@ __device__ __forceinline__ void flush_tile_rows(const f32x4 (&acc)[RT][CTW], flo
 // Default: atomics straight from the accumulator registers.  The through-LDS form (AST_WGRAD_FLUSH_LDS=1: 256 contiguous bytes per
 // atomic wave-instruction) measured 1-1.5 us SLOWER per layer with 8 gradient replicas (64-channel layer 40.1 -> 41.5 us, 128: 41.0 ->
 // 42.2, 256: 41.8 -> 43.3; profiles/r03/wg_flush.txt): at ~11 adders per address the 4 x 64 B shape is not what bounds the flush.
-inline bool wg_flush_direct() { const char* e = getenv("AST_WGRAD_FLUSH_LDS"); return !(e && atoi(e) != 0); }
-static thread_local int g_wg_nrep = 1;
-static thread_local int g_wg_slab = 0;            // ast_wgrad_slab: g_wg_nrep slabs, one per pixel slice, plain stores
-static thread_local int g_wg_slices = 0;          // out: pixel slices of the last launch
-inline int wg_nrep_arg() { return g_wg_nrep | ((g_wg_slab ? 2 : (wg_flush_direct() ? 0 : 1)) << 16); }
-static thread_local long g_wg_rep_stride = 0;
+// How a launch flushes its partial sums: into `copies` copies of dW, `stride` floats apart (pixel slice z -> copy z % copies).
+// Slab (ast_wgrad_slab): one copy per pixel slice, plain stores, at most `copies` slices, their number reported in *slices_out.
+struct WgradFlush {
+  enum Mode { Atomic = 0, AtomicLds = 1, Slab = 2 } mode;          // the values are the kernels' flush-mode field
+  int copies;
+  long stride;
+  int* slices_out;                                                 // may be null
+};
+inline WgradFlush::Mode wg_atomic_mode() { return env_flag("AST_WGRAD_FLUSH_LDS", false) ? WgradFlush::AtomicLds : WgradFlush::Atomic; }
+inline int wg_flush_arg(const WgradFlush& f) { return f.copies | ((int)f.mode << 16); }       // the kernels' `nrep` argument
+inline int wg_slice_cap(const WgradFlush& f) { return f.mode == WgradFlush::Slab ? f.copies : INT_MAX; }
+inline void wg_report_slices(const WgradFlush& f, int slices) { if (f.slices_out) *f.slices_out = slices; }
+// The knobs more than one launcher reads, each with the caller's default (read per call: tests toggle them at run time)
+inline int wg_target_knob(int fallback) { return env_int("AST_WGRAD_WG_TARGET", fallback); }
+inline int wg_pg_knob(int fallback) { return env_int("AST_WGRAD_PG", fallback); }
+
+// Pixel slices of a launch with `tiles` output tiles: `want` slices (the launcher's workgroup target over its tiles), at least
+// `min_trips` K trips of `k_unit` pixels each, at most `cap`; a slice is a whole number of K trips; the 1-D grid is a multiple of 8.
+struct PixelSlices { int nsplit, pps, grid; };
+inline PixelSlices plan_pixel_slices(int P, int k_unit, int min_trips, int tiles, int want, int cap) {
+  const int min_px = min_trips * k_unit;
+  int nsplit = std::min(std::max(1, std::min((P + min_px - 1) / min_px, want)), cap);
+  int pps = (P + nsplit - 1) / nsplit;
+  pps = (pps + k_unit - 1) / k_unit * k_unit;
+  nsplit = (P + pps - 1) / pps;
+  return {nsplit, pps, (tiles * nsplit + 7) / 8 * 8};
+}
 template <typename T> struct WgradCfg;
 template <> struct WgradCfg<bf16_t> { static constexpr int BKP = 64, PAD = 16; };   // elements: row pitch = 32 B x odd for rows that are multiples of 64 B (see SWZ)
 template <> struct WgradCfg<float> { static constexpr int BKP = 32, PAD = 16; };
@@ -328,38 +350,26 @@ extern "C" int ast_debug_read_wg_phases(long long* host, int n) {
 #endif
 
 template <typename T, int BMW, int NCT, int PG>
-int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, hipStream_t s) {
+int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
   constexpr int BKP = WgradCfg<T>::BKP, PAD = WgradCfg<T>::PAD;
   constexpr int GROUP = (int)sizeof(T) * BKP * ((BMW + PAD) + (NCT * 16 + PAD));
   constexpr int RED = PG > 1 ? (BMW / 16) * ((NCT + 3) / 4) * 256 * 16 : 0;
   constexpr int LDS = std::max(std::max(PG * GROUP, RED), BMW * NCT * 16 * 4) + 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, BMW, NCT, PG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, BMW, NCT, PG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(LDS, {(const void*)wgrad_kernel<T, BMW, NCT, PG, false>, (const void*)wgrad_kernel<T, BMW, NCT, PG, true>})) return rc;
   const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
   const int tiles = gx * gy;
-  const char* wte = getenv("AST_WGRAD_WG_TARGET");
   // see launch_wgrad_halo; the single-group 64 x 192 tiles (23 launches of a step) take 384: 29.5-29.8 -> 28.1-28.3 us on
   // average in the replayed step (tools/knob_ab.sh; 320: 29.1, 448: 30.5), the two-group and the narrow ones do not (32.7 -> 43.3)
-  const int wg_target = wte ? atoi(wte) : (P >= 1500000 ? 768 : (PG == 1 && NCT >= 12 ? 384 : 256));
-  int nsplit = std::max(1, std::min((P + 4 * BKP - 1) / (4 * BKP), (wg_target + tiles - 1) / tiles));
-  if (g_wg_slab) nsplit = std::min(nsplit, g_wg_nrep);         // slab mode: one copy of dW per pixel slice
-  int pps = (P + nsplit - 1) / nsplit;
-  pps = (pps + BKP - 1) / BKP * BKP;
-  nsplit = (P + pps - 1) / pps;
+  const int wg_target = wg_target_knob(P >= 1500000 ? 768 : (PG == 1 && NCT >= 12 ? 384 : 256));
+  // at least 4 K trips per slice; slab mode: one copy of dW per pixel slice
+  const PixelSlices ps = plan_pixel_slices(P, BKP, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  const int total = gx * gy * nsplit;
-  g_wg_slices = nsplit;
-  if (g_wg_slab)
-    hipLaunchKernelGGL((wgrad_kernel<T, BMW, NCT, PG, true>), dim3((total + 7) / 8 * 8), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P,
-                       pps, dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
-  else
-    hipLaunchKernelGGL((wgrad_kernel<T, BMW, NCT, PG, false>), dim3((total + 7) / 8 * 8), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P,
-                       pps, dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  wg_report_slices(f, ps.nsplit);
+  const auto k = f.mode == WgradFlush::Slab ? wgrad_kernel<T, BMW, NCT, PG, true> : wgrad_kernel<T, BMW, NCT, PG, false>;
+  hipLaunchKernelGGL(k, dim3(ps.grid), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -619,47 +629,31 @@ bool wgrad_rows_eligible(const ast_gather_t& g, int dtype) {
 }
 
 template <int NST>
-int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, hipStream_t s) {
+int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
   constexpr int STAGE = 64 * 128 + 72 * 128 + 384;
   constexpr int LDS = (NST * STAGE > 64 * 192 * 4 ? NST * STAGE : 64 * 192 * 4) + 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_rows_kernel<NST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_rows_kernel<NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(LDS, {(const void*)wgrad_rows_kernel<NST, false>, (const void*)wgrad_rows_kernel<NST, true>})) return rc;
   const int gx = g.Cd / 64, gy = 3 * (g.Cs / 64);
   const int tiles = gx * gy;
-  const char* wte = getenv("AST_WGRAD_WG_TARGET");
-  const int wg_target = wte ? atoi(wte) : 384;          // 1.5 workgroups per CU (71 KB of LDS each); 256 and 512 measured slower (profiles/r03/wg_rows_layers.txt)
-  int nsplit = std::max(1, std::min((P + 4 * 64 - 1) / (4 * 64), (wg_target + tiles - 1) / tiles));
-  if (g_wg_slab) nsplit = std::min(nsplit, g_wg_nrep);
-  int pps = (P + nsplit - 1) / nsplit;
-  pps = (pps + 63) / 64 * 64;
-  nsplit = (P + pps - 1) / pps;
+  const int wg_target = wg_target_knob(384);            // 1.5 workgroups per CU (71 KB of LDS each); 256 and 512 measured slower (profiles/r03/wg_rows_layers.txt)
+  const PixelSlices ps = plan_pixel_slices(P, 64, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * 2);
   const unsigned src_bytes = (unsigned)((size_t)P * g.Cs * 2);
-  const int total = gx * gy * nsplit;
-  g_wg_slices = nsplit;
-  if (g_wg_slab)
-    hipLaunchKernelGGL((wgrad_rows_kernel<NST, true>), dim3((total + 7) / 8 * 8), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, pps,
-                       dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
-  else
-    hipLaunchKernelGGL((wgrad_rows_kernel<NST, false>), dim3((total + 7) / 8 * 8), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, pps,
-                       dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, nsplit, wg_nrep_arg(), g_wg_rep_stride);
+  wg_report_slices(f, ps.nsplit);
+  const auto k = f.mode == WgradFlush::Slab ? wgrad_rows_kernel<NST, true> : wgrad_rows_kernel<NST, false>;
+  hipLaunchKernelGGL(k, dim3(ps.grid), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int BMW, int NCT>
-int launch_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, hipStream_t s) {
+int launch_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
   // two pixel groups for the pixel-rich layers only: measured 172 800 pixels -11 % (51 -> 45 us), 43 200 pixels +20 %
   // (54 -> 65 us: their slices are a few K tiles long, halving them leaves the groups idle at the barriers)
-  const char* pe = getenv("AST_WGRAD_PG");
-  const char* mp = getenv("AST_WGRAD_PG_MINP");
-  const int pg = pe ? atoi(pe) : 2;
-  if (pg >= 2 && P >= (mp ? atoi(mp) : 100000)) return launch_wgrad_pg<T, BMW, NCT, 2>(dy, src, dw, g, P, s);
-  return launch_wgrad_pg<T, BMW, NCT, 1>(dy, src, dw, g, P, s);
+  if (wg_pg_knob(2) >= 2 && P >= env_int("AST_WGRAD_PG_MINP", 100000)) return launch_wgrad_pg<T, BMW, NCT, 2>(dy, src, dw, g, P, f, s);
+  return launch_wgrad_pg<T, BMW, NCT, 1>(dy, src, dw, g, P, f, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -873,14 +867,13 @@ __global__ __launch_bounds__(256 * PG) void wgrad_halo_kernel(const T* __restric
     }
     if (pg > 0) return;
   }
-  dw += (size_t)(blockIdx.z % (nrep & 0xffff)) * rep_stride;      // this slice's gradient replica / slab (see g_wg_nrep)
+  dw += (size_t)(blockIdx.z % (nrep & 0xffff)) * rep_stride;      // this slice's gradient replica / slab (see WgradFlush)
   flush_tile_rows<BMW, NCT, RT, CTW>(acc, reinterpret_cast<float*>(wl_all), dw, g, cd0, col0, ncols, wave, lane,
                                      [&](int t) { return taptab[16 + t]; }, SLAB ? 2 : (nrep >> 16) & 3);
 }
 
 bool plan_wgrad_halo(const ast_gather_t& g, int dtype, int nct, int bmw, WHaloPlan& hp) {
-  const char* mc = getenv("AST_WGRAD_HALO_MAXCD");
-  if (g.ntaps < 2 || g.Cd > (mc ? atoi(mc) : 32)) return false;          // measured: wins for <= 32 output channels, loses at 64
+  if (g.ntaps < 2 || g.Cd > env_int("AST_WGRAD_HALO_MAXCD", 32)) return false;          // measured: wins for <= 32 output channels, loses at 64
   const int E = dtype == AST_BF16 ? 8 : 4, ES = dtype == AST_BF16 ? 2 : 4;
   int dhmin = 64, dhmax = -64, dwmin = 64, dwmax = -64;
   for (int t = 0; t < g.ntaps; ++t) {
@@ -902,45 +895,35 @@ bool plan_wgrad_halo(const ast_gather_t& g, int dtype, int nct, int bmw, WHaloPl
 }
 
 template <typename T, int BMW, int NCT, int PG>
-int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, hipStream_t s) {
+int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, const WgradFlush& f, hipStream_t s) {
   constexpr int RED = (BMW / 16) * ((NCT + 3) / 4) * 256 * 16;          // bytes of one group's partial tile in the LDS reduction
   const int lds = std::max(std::max(PG * hp.lds, PG > 1 ? RED : 0), BMW * NCT * 16 * 4) + 160;
-  static int attr_lds = 0;
-  if (lds > attr_lds) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, BMW, NCT, PG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, BMW, NCT, PG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_lds = 160 * 1024;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(160 * 1024, {(const void*)wgrad_halo_kernel<T, BMW, NCT, PG, false>, (const void*)wgrad_halo_kernel<T, BMW, NCT, PG, true>})) return rc;
   const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
   // every workgroup adds its whole dW tile into the same few KB: same-address atomics serialise, so the workgroup count
   // stays at about one per CU and the waves come from the pixel groups (sweep in profiles/r01 and r02)
-  const char* wt = getenv("AST_WGRAD_WG_TARGET");
-  const int wg_target = wt ? atoi(wt) : (PG > 1 ? 256 : ((long)g.N * g.Hm * g.Wm >= 1500000 ? 768 : 256));
-  int gz = std::max(1, std::min((hp.ntiles + PG - 1) / PG, wg_target / (gx * gy)));
-  if (g_wg_slab) gz = std::min(gz, g_wg_nrep);
-  g_wg_slices = gz;
+  const int wg_target = wg_target_knob(PG > 1 ? 256 : ((long)g.N * g.Hm * g.Wm >= 1500000 ? 768 : 256));
+  const int gz = std::min(std::max(1, std::min((hp.ntiles + PG - 1) / PG, wg_target / (gx * gy))), wg_slice_cap(f));
+  wg_report_slices(f, gz);
   const unsigned dy_bytes = (unsigned)((size_t)g.N * g.Hm * g.Wm * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  if (g_wg_slab)
-    hipLaunchKernelGGL((wgrad_halo_kernel<T, BMW, NCT, PG, true>), dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp,
-                       dy_bytes, src_bytes, wg_nrep_arg(), g_wg_rep_stride);
-  else
-    hipLaunchKernelGGL((wgrad_halo_kernel<T, BMW, NCT, PG, false>), dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp,
-                       dy_bytes, src_bytes, wg_nrep_arg(), g_wg_rep_stride);
+  const auto k = f.mode == WgradFlush::Slab ? wgrad_halo_kernel<T, BMW, NCT, PG, true> : wgrad_halo_kernel<T, BMW, NCT, PG, false>;
+  hipLaunchKernelGGL(k, dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp, dy_bytes, src_bytes,
+                     wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int BMW, int NCT>
-int launch_wgrad_halo(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, hipStream_t s) {
+int launch_wgrad_halo(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, const WgradFlush& f, hipStream_t s) {
   // pixel groups: as many as the LDS holds (<= 4), when every group gets several tiles
   // (four groups need <= 128 VGPRs per thread; the kernel uses 130-200 and spills: 50 -> 105 us on the 32-channel layer)
-  const char* pe = getenv("AST_WGRAD_PG");
-  int pg = pe ? atoi(pe) : 2;
+  int pg = wg_pg_knob(2);
   while (pg > 1 && (pg * hp.lds > 150 * 1024 || hp.ntiles < 256 * pg * 2)) pg >>= 1;
-  if (pg >= 4) return launch_wgrad_halo_pg<T, BMW, NCT, 4>(dy, src, dw, g, hp, s);
-  if (pg == 2) return launch_wgrad_halo_pg<T, BMW, NCT, 2>(dy, src, dw, g, hp, s);
-  return launch_wgrad_halo_pg<T, BMW, NCT, 1>(dy, src, dw, g, hp, s);
+  if (pg >= 4) return launch_wgrad_halo_pg<T, BMW, NCT, 4>(dy, src, dw, g, hp, f, s);
+  if (pg == 2) return launch_wgrad_halo_pg<T, BMW, NCT, 2>(dy, src, dw, g, hp, f, s);
+  return launch_wgrad_halo_pg<T, BMW, NCT, 1>(dy, src, dw, g, hp, f, s);
 }
 
 
@@ -1125,7 +1108,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_tap_kernel(const T* __restrict_
   const bool cok = col < ncols;
   const int t = cok ? col / g.Cs : 0, ch = cok ? col - t * g.Cs : 0;
   const int wtc = taptab[t] >> 16;
-  float* dwr = dw + (size_t)(bz % nrep) * rep_stride;      // this pixel slice's gradient replica (see g_wg_nrep)
+  float* dwr = dw + (size_t)(bz % nrep) * rep_stride;      // this pixel slice's gradient replica (see WgradFlush)
   const float* rbase = reinterpret_cast<const float*>(wt_lds);
 #pragma unroll
   for (int rr = 0; rr < RPW; ++rr) {
@@ -1142,43 +1125,79 @@ __global__ __launch_bounds__(64 * NW) void wgrad_tap_kernel(const T* __restrict_
 }
 
 template <typename T>
-int launch_wgrad_tap(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, hipStream_t s) {
+int launch_wgrad_tap(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
   constexpr int NW = 8, KPX = WtCfg<T>::KPX;
   constexpr int LDS = NW * 64 * 64 * 4 + 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    AST_HIP(hipFuncSetAttribute((const void*)wgrad_tap_kernel<T, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(LDS, {(const void*)wgrad_tap_kernel<T, NW>})) return rc;
   const int gx = (g.Cd + 63) / 64, gy = (g.ntaps * g.Cs + 63) / 64, tiles = gx * gy;
   // pixel slices: about one workgroup (8 waves) per CU.  More slices = more flush bytes (slices x |dW| of f32 atomics at the chip's
   // ~1.3 TB/s), fewer = idle CUs; a slice keeps at least two K steps per wave.
-  const char* we = getenv("AST_WGRAD_TAP_WGS");
-  const int wg_target = we ? atoi(we) : 256;
-  int gz = std::max(1, std::min((P + 2 * KPX * NW - 1) / (2 * KPX * NW), (wg_target + tiles / 2) / tiles));
-  int pps = (P + gz - 1) / gz;
-  pps = (pps + KPX - 1) / KPX * KPX;
-  gz = (P + pps - 1) / pps;
+  const int wg_target = env_int("AST_WGRAD_TAP_WGS", 256);
+  const PixelSlices ps = plan_pixel_slices(P, KPX, 2 * NW, tiles, (wg_target + tiles / 2) / tiles, wg_slice_cap(f));
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  const int total = tiles * gz;
-  g_wg_slices = gz;
-  hipLaunchKernelGGL((wgrad_tap_kernel<T, NW>), dim3((total + 7) / 8 * 8), dim3(64 * NW), LDS, s, (const T*)dy, (const T*)src, dw, g, P, pps,
-                     dy_bytes, src_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, gz, g_wg_nrep, g_wg_rep_stride, gz == 1 ? 1 : 0);
+  wg_report_slices(f, ps.nsplit);
+  // (no flush mode to pass: this kernel has the atomic flush only, the dispatcher keeps it out of slab mode)
+  hipLaunchKernelGGL((wgrad_tap_kernel<T, NW>), dim3(ps.grid), dim3(64 * NW), LDS, s, (const T*)dy, (const T*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, f.copies, f.stride, ps.nsplit == 1 ? 1 : 0);
   AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// The one dispatcher behind ast_wgrad / ast_wgrad_rep / ast_wgrad_slab: picks the kernel family and tile shape for the layer
+// and hands the flush descriptor to its launcher.  (The messages keep the name of the entry point all three share.)
+int wgrad_dispatch(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, const WgradFlush& f, hipStream_t s) {
+  if (int rc = check_gather(gp, "ast_wgrad")) return rc;
+  if (!dy || !src || !dw) AST_FAIL("ast_wgrad: null pointer");
+  const ast_gather_t g = *gp;
+  if (g.ntaps == 0) return 0;
+  const int P = g.N * g.Hm * g.Wm;
+  if ((long)P * g.Cd * 4 >= (1L << 31)) AST_FAIL("ast_wgrad: dy exceeds the 2 GiB buffer-addressing range");
+  const int nct_all = (g.ntaps * g.Cs + 15) / 16;          // column tiles of the whole (tap, channel) space
+  const int bmw = g.Cd > 32 ? 64 : (g.Cd > 16 ? 32 : 16);
+  // all columns in one workgroup when the accumulators fit (<= 20 tiles x BMW/16 row tiles <= 20 per wave)
+  int nct;
+  if (bmw == 64) nct = nct_all <= 8 ? (nct_all <= 4 ? 4 : 8) : 12;
+  else nct = nct_all <= 4 ? 4 : (nct_all <= 8 ? 8 : (nct_all <= 12 ? 12 : 20));
+  // >= 64 output channels: the wave-autonomous tap-tile kernel (AST_WGRAD_TAP=0: the cooperative kernels below, for A/B)
+  // Opt-in (AST_WGRAD_TAP=1): measured SLOWER than the cooperative kernels below -- isolated 44.4 vs 39.4 us on the 64-channel
+  // layer, 71.8 vs 41.3 (256 channels), 67.2 vs 39.6 (512); only the stride-2 layers gain (24.9 vs 30.9) -- and the whole step
+  // 7.29 vs 6.2 ms: its nine tap tiles re-read every dy / source row nine times through L1 (398 MB per launch at ~9 TB/s: the
+  // fabric, not the MFMAs), and a workgroup takes a whole CU (128 KB of LDS) away from the other streams' kernels.  DESIGN 9.3.
+  // (the knobs here are read per call, host side only: tests toggle them at run time; the tap kernel has no slab form)
+  if (env_flag("AST_WGRAD_TAP", false) && f.mode != WgradFlush::Slab && g.Cd >= 64) {
+    AST_DISPATCH_T(dtype, { return launch_wgrad_tap<T>(dy, src, dw, g, P, f, s); });
+  }
+  if (env_flag("AST_WGRAD_ROWS", true) && wgrad_rows_eligible(g, dtype)) {
+    if ((long)P * g.Cs * 2 >= (1L << 31)) AST_FAIL("ast_wgrad: source exceeds the 2 GiB buffer-addressing range");
+    const int nst = env_int("AST_WGRAD_ROWS_STAGES", 4);    // ring depth: 4 stages = 71 KB of LDS (two workgroups per CU), 3 = 53 KB (three)
+    if (nst == 2) return launch_wgrad_rows<2>(dy, src, dw, g, P, f, s);
+    if (nst == 3) return launch_wgrad_rows<3>(dy, src, dw, g, P, f, s);
+    return launch_wgrad_rows<4>(dy, src, dw, g, P, f, s);
+  }
+  WHaloPlan whp;
+  const bool halo = plan_wgrad_halo(g, dtype, nct, bmw, whp);
+#define AST_WG(B_, N_) do { if (halo) return launch_wgrad_halo<T, B_, N_>(dy, src, dw, g, whp, f, s); \
+                            return launch_wgrad<T, B_, N_>(dy, src, dw, g, P, f, s); } while (0)
+  AST_DISPATCH_T(dtype, {
+    if (bmw == 64) { if (nct == 4) AST_WG(64, 4); if (nct == 8) AST_WG(64, 8); AST_WG(64, 12); }
+    if (bmw == 32) { if (nct == 4) AST_WG(32, 4); if (nct == 8) AST_WG(32, 8); if (nct == 12) AST_WG(32, 12); AST_WG(32, 20); }
+    if (nct == 4) AST_WG(16, 4); if (nct == 8) AST_WG(16, 8); if (nct == 12) AST_WG(16, 12); AST_WG(16, 20);
+  });
+#undef AST_WG
   return 0;
 }
 
 }  // namespace
 
-extern "C" int ast_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, void* stream);
+extern "C" int ast_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, void* stream) {
+  return wgrad_dispatch(dy, src, dw, gp, dtype, WgradFlush{wg_atomic_mode(), 1, 0, nullptr}, (hipStream_t)stream);
+}
+
 extern "C" int ast_wgrad_rep(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, int nrep, void* stream) {
   if (nrep < 1 || nrep > 64 || !gp) AST_FAIL("ast_wgrad_rep: 1..64 replicas");
-  g_wg_nrep = nrep;
-  g_wg_rep_stride = (long)gp->Cd * gp->wtaps * gp->Cs;
-  const int rc = ast_wgrad(dy, src, dw, gp, dtype, stream);
-  g_wg_nrep = 1; g_wg_rep_stride = 0;
-  return rc;
+  return wgrad_dispatch(dy, src, dw, gp, dtype, WgradFlush{wg_atomic_mode(), nrep, (long)gp->Cd * gp->wtaps * gp->Cs, nullptr}, (hipStream_t)stream);
 }
 
 // ---- slab mode: every pixel slice STORES its partial dW into its own copy; ast_slab_sum adds the copies up ----------------------
@@ -1213,16 +1232,11 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const SlabArgs a) {
 }
 }  // namespace
 
-extern "C" int ast_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, void* stream);
 extern "C" int ast_wgrad_slab(const void* dy, const void* src, float* slabs, const ast_gather_t* gp, int dtype, int nslabs, int* slices_out,
                               void* stream) {
   if (nslabs < 1 || nslabs > 4096 || !gp || !slices_out) AST_FAIL("ast_wgrad_slab: 1..4096 slabs and a slices output");
-  g_wg_nrep = nslabs; g_wg_slab = 1; g_wg_slices = 0;
-  g_wg_rep_stride = (long)gp->Cd * gp->wtaps * gp->Cs;
-  const int rc = ast_wgrad(dy, src, slabs, gp, dtype, stream);
-  *slices_out = g_wg_slices;
-  g_wg_nrep = 1; g_wg_slab = 0; g_wg_rep_stride = 0;
-  return rc;
+  *slices_out = 0;                                       // stays 0 when nothing was launched
+  return wgrad_dispatch(dy, src, slabs, gp, dtype, WgradFlush{WgradFlush::Slab, nslabs, (long)gp->Cd * gp->wtaps * gp->Cs, slices_out}, (hipStream_t)stream);
 }
 
 extern "C" int ast_slab_sum(float* const* bases, const int64_t* floats_per_copy, const int* slabs, int nrec, void* stream) {
@@ -1245,48 +1259,3 @@ extern "C" int ast_slab_sum(float* const* bases, const int64_t* floats_per_copy,
   AST_CHECK_LAUNCH();
   return 0;
 }
-
-extern "C" int ast_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, void* stream) {
-  if (int rc = check_gather(gp, "ast_wgrad")) return rc;
-  if (!dy || !src || !dw) AST_FAIL("ast_wgrad: null pointer");
-  const ast_gather_t g = *gp;
-  if (g.ntaps == 0) return 0;
-  const int P = g.N * g.Hm * g.Wm;
-  if ((long)P * g.Cd * 4 >= (1L << 31)) AST_FAIL("ast_wgrad: dy exceeds the 2 GiB buffer-addressing range");
-  hipStream_t s = (hipStream_t)stream;
-  const int nct_all = (g.ntaps * g.Cs + 15) / 16;          // column tiles of the whole (tap, channel) space
-  const int bmw = g.Cd > 32 ? 64 : (g.Cd > 16 ? 32 : 16);
-  // all columns in one workgroup when the accumulators fit (<= 20 tiles x BMW/16 row tiles <= 20 per wave)
-  int nct;
-  if (bmw == 64) nct = nct_all <= 8 ? (nct_all <= 4 ? 4 : 8) : 12;
-  else nct = nct_all <= 4 ? 4 : (nct_all <= 8 ? 8 : (nct_all <= 12 ? 12 : 20));
-  // >= 64 output channels: the wave-autonomous tap-tile kernel (AST_WGRAD_TAP=0: the cooperative kernels below, for A/B)
-  // Opt-in (AST_WGRAD_TAP=1): measured SLOWER than the cooperative kernels below -- isolated 44.4 vs 39.4 us on the 64-channel
-  // layer, 71.8 vs 41.3 (256 channels), 67.2 vs 39.6 (512); only the stride-2 layers gain (24.9 vs 30.9) -- and the whole step
-  // 7.29 vs 6.2 ms: its nine tap tiles re-read every dy / source row nine times through L1 (398 MB per launch at ~9 TB/s: the
-  // fabric, not the MFMAs), and a workgroup takes a whole CU (128 KB of LDS) away from the other streams' kernels.  DESIGN 9.3.
-  const char* te = getenv("AST_WGRAD_TAP");                  // read per call (host side only): tests toggle it at run time
-  const bool tap_on = te && atoi(te) != 0;
-  if (tap_on && !g_wg_slab && g.Cd >= 64) { AST_DISPATCH_T(dtype, { return launch_wgrad_tap<T>(dy, src, dw, g, P, s); }); }
-  const char* re = getenv("AST_WGRAD_ROWS");                 // read per call (host side only): tests toggle it at run time
-  if (!(re && atoi(re) == 0) && wgrad_rows_eligible(g, dtype)) {
-    if ((long)P * g.Cs * 2 >= (1L << 31)) AST_FAIL("ast_wgrad: source exceeds the 2 GiB buffer-addressing range");
-    const char* se = getenv("AST_WGRAD_ROWS_STAGES");       // ring depth: 4 stages = 71 KB of LDS (two workgroups per CU), 3 = 53 KB (three)
-    const int nst = se ? atoi(se) : 4;
-    if (nst == 2) return launch_wgrad_rows<2>(dy, src, dw, g, P, s);
-    if (nst == 3) return launch_wgrad_rows<3>(dy, src, dw, g, P, s);
-    return launch_wgrad_rows<4>(dy, src, dw, g, P, s);
-  }
-  WHaloPlan whp;
-  const bool halo = plan_wgrad_halo(g, dtype, nct, bmw, whp);
-#define AST_WG(B_, N_) do { if (halo) return launch_wgrad_halo<T, B_, N_>(dy, src, dw, g, whp, s); \
-                            return launch_wgrad<T, B_, N_>(dy, src, dw, g, P, s); } while (0)
-  AST_DISPATCH_T(dtype, {
-    if (bmw == 64) { if (nct == 4) AST_WG(64, 4); if (nct == 8) AST_WG(64, 8); AST_WG(64, 12); }
-    if (bmw == 32) { if (nct == 4) AST_WG(32, 4); if (nct == 8) AST_WG(32, 8); if (nct == 12) AST_WG(32, 12); AST_WG(32, 20); }
-    if (nct == 4) AST_WG(16, 4); if (nct == 8) AST_WG(16, 8); if (nct == 12) AST_WG(16, 12); AST_WG(16, 20);
-  });
-#undef AST_WG
-  return 0;
-}
-
