@@ -1274,6 +1274,17 @@ extern "C" int ast_igemm_plan(const ast_gather_t* gp, int dtype, int* out5) {
   return 0;
 }
 
+// The pconv_kernel<T, SLB, TM, TN, WALL> instantiation ast_igemm launches for this geometry: out4 = {SLB, TM, TN, WALL}, returns 1;
+// 0 when the patch kernel does not take the geometry.  TM follows the dispatch chain in ast_igemm_bn.
+extern "C" int ast_pconv_variant(const ast_gather_t* gp, int dtype, int* out4) {
+  if (!gp || !out4 || check_gather(gp, "ast_pconv_variant")) return -1;
+  PconvPlan pp; int slb = 0, tn = 0;
+  if (!plan_pconv(*gp, dtype, pp, slb, tn)) return 0;
+  const int tm = slb == 128 ? (pp.tm == 1 || pp.tm == 2 ? pp.tm : 3) : (pp.tm == 2 || pp.tm == 4 ? pp.tm : 3);
+  out4[0] = slb; out4[1] = tm; out4[2] = tn; out4[3] = pp.wall;
+  return 1;
+}
+
 extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t* gp,
                             int dtype, int flags, float* ws, long ws_floats, const void* bn_x, const float* bn_scale,
                             const float* bn_shift, void* stream) {
@@ -1284,6 +1295,8 @@ extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias,
   hipStream_t s = (hipStream_t)stream;
   IgemmPlan p = plan_igemm(g, M, dtype);
   p.bn_x = bn_x; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
+  // checked before the patch dispatch: its deterministic instantiation ignores the statistics table
+  if ((flags & 4096) && (flags & (8 | 16 | 64))) AST_FAIL("ast_igemm: the deterministic form (flags bit 12) has no fused statistics (flags 8 / 16 / 64)");
   {
     PconvPlan pp; int slb = 0, tn = 0;
     if (plan_pconv(g, dtype, pp, slb, tn)) {
@@ -1318,7 +1331,6 @@ extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias,
     if (!(flags & 8) || (flags & 3) || p.nsplit > 1 || direct_ok(g, p, dtype)) AST_FAIL("ast_igemm: per-image statistics (flag 64) need flag 8, plain stores and the gathered kernel (ast_igemm_plan: kch > 0, no split)");
     if (!ws || ws_floats < (long)g.N * g.Cd * 2) AST_FAIL("ast_igemm: per-image statistics need a zeroed [N][Cd][2] table");
   }
-  if ((flags & 4096) && (flags & (8 | 16 | 64))) AST_FAIL("ast_igemm: the deterministic form (flags bit 12) has no fused statistics (flags 8 / 16 / 64)");
   if (direct_ok(g, p, dtype)) { AST_DISPATCH_T(dtype, { return dispatch_direct<T>(src, wgt, bias, dst, g, M, flags, ws, p, s); }); }
 #define AST_IG(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 1>(src, wgt, bias, dst, g, M, flags, ws, p, s)
 #define AST_IG4(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 4>(src, wgt, bias, dst, g, M, flags, ws, p, s)

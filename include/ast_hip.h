@@ -78,6 +78,9 @@ int ast_igemm_bn(const void* src, const void* wgt, const float* bias, void* dst,
 long ast_igemm_ws_floats(const ast_gather_t* g, int dtype);
 /* the tile plan ast_igemm will use: out5 = {BM, BN, 16-byte chunks per row per barrier, grid-level split-K slices, in-workgroup K groups} */
 int ast_igemm_plan(const ast_gather_t* g, int dtype, int* out5);
+/* the patch-staged kernel ast_igemm will launch: out4 = {slab bytes, TM, TN, WALL} of pconv_kernel, returns 1; 0 when the
+ * geometry goes to the gathered or direct kernel, <0 on a bad geometry (reporting only, host side) */
+int ast_pconv_variant(const ast_gather_t* g, int dtype, int* out4);
 
 /* dw[cd][wtap[t]][c] += sum_pix dy[pix][cd] * src[gather(pix,t)][c]   (f32 atomics)
  * dy is the plain operand over the logical grid (N,Hm,Wm,Cd).

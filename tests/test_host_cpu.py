@@ -210,6 +210,8 @@ def test_igemm_argument_validation_returns_error_codes():
     assert lib.ast_igemm_plan(gp, bf16, ctypes.byref(out)) == 0 and out[2] < 0, list(out)
     assert igemm(gp, 8, None, 64 * 64 * 2) != 0
     assert igemm_bn(gp, 16, fake, 64 * 64 * 3, sf=None) != 0
+    assert igemm(gp, 4096 | 8, fake, 64 * 64 * 2) != 0 and b"deterministic" in lib.ast_last_error()      # refused on the patch path too
+    assert igemm(gg, 4096 | 8, fake, 64 * 64 * 2) != 0 and igemm_bn(gp, 4096 | 16, fake, 64 * 64 * 3) != 0
     # null geometry / tensors
     assert lib.ast_igemm(None, fake, None, fake, gg, bf16, 0, None, 0, None) != 0
 
@@ -251,3 +253,178 @@ def test_round3_entry_points_refuse_bad_arguments():
     assert lib.ast_wgrad_slab(fake, fake, fake, g, _lib.BF16, 0, ctypes.byref(sl), None) != 0
     assert lib.ast_wgrad_slab(fake, fake, fake, g, _lib.BF16, 4, None, None) != 0
     assert lib.ast_wgrad_slab(None, fake, fake, g, _lib.BF16, 4, ctypes.byref(sl), None) != 0      # (ast_wgrad's own null check)
+
+
+# ---- the float64 gather-GEMM reference and the case table of tests/test_gpu_igemm_variants.py (tests/igemm_cases.py) ------------
+
+def _ref_conv(N, H, W, Cs, Cd, kh, kw, stride, ph, pw, seed):
+    import torch.nn.functional as F
+    import igemm_cases as IC
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, Cs, H, W, dtype=torch.float64, generator=gen)
+    w = torch.randn(Cd, Cs, kh, kw, dtype=torch.float64, generator=gen)
+    b = torch.randn(Cd, dtype=torch.float64, generator=gen)
+    g = IC.conv_gather(N, H, W, Cs, Cd, kh, kw, stride, ph, pw)
+    y, A = IC.gather_gemm_ref(x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1).reshape(Cd, kh * kw, Cs), b, g)
+    ref = F.conv2d(x, w, b, stride=stride, padding=(ph, pw)).permute(0, 2, 3, 1)
+    Aref = F.conv2d(x.abs(), w.abs(), b.abs(), stride=stride, padding=(ph, pw)).permute(0, 2, 3, 1)
+    return y, A, ref, Aref
+
+
+@pytest.mark.parametrize("N,H,W,Cs,Cd,kh,kw,stride,ph,pw", [
+    (2, 7, 9, 8, 16, 3, 3, 1, 1, 1), (2, 9, 12, 8, 8, 3, 3, 2, 1, 1), (3, 5, 6, 16, 8, 1, 1, 1, 0, 0), (2, 9, 19, 8, 8, 1, 1, 2, 0, 0),
+    (2, 6, 7, 8, 24, 2, 3, 1, 1, 1), (2, 12, 11, 8, 8, 2, 3, 2, 1, 1), (1, 2, 2, 8, 8, 3, 3, 1, 1, 1)])
+def test_gather_gemm_ref_matches_conv2d(N, H, W, Cs, Cd, kh, kw, stride, ph, pw):
+    """gather_gemm_ref on Conv2d forward geometries (ops.gather_direct and the rectangular-kernel builder of the case table)
+    against F.conv2d in float64, and its second output against the same convolution of absolute values."""
+    y, A, ref, Aref = _ref_conv(N, H, W, Cs, Cd, kh, kw, stride, ph, pw, seed=11)
+    assert y.shape == ref.shape
+    assert float((y - ref).abs().max()) < 1e-12 and float((A - Aref).abs().max()) < 1e-12
+    assert bool((A >= y.abs() - 1e-12).all())
+
+
+@pytest.mark.parametrize("Hs,Ws,Hd,Wd,k,stride,pad", [(5, 7, 10, 14, 3, 2, 1), (5, 7, 9, 13, 3, 2, 1), (4, 6, 4, 6, 3, 1, 1), (4, 5, 8, 9, 1, 2, 0)])
+def test_gather_gemm_ref_matches_conv_transpose2d(Hs, Ws, Hd, Wd, k, stride, pad):
+    """The parity classes of ops.gathers_transposed, each written through gather_gemm_ref into one destination, assemble
+    F.conv_transpose2d; pixels of the other classes are left as they were (old_dst) by every class's launch."""
+    import torch.nn.functional as F
+    import igemm_cases as IC
+    N, Cs, Cd = 2, 8, 16
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(N, Cs, Hs, Ws, dtype=torch.float64, generator=gen)
+    w = torch.randn(Cs, Cd, k, k, dtype=torch.float64, generator=gen)
+    b = torch.randn(Cd, dtype=torch.float64, generator=gen)
+    oph, opw = Hd - ((Hs - 1) * stride - 2 * pad + k), Wd - ((Ws - 1) * stride - 2 * pad + k)
+    ref = F.conv_transpose2d(x, w, b, stride=stride, padding=pad, output_padding=(oph, opw)).permute(0, 2, 3, 1)
+    wgt = w.permute(1, 2, 3, 0).reshape(Cd, k * k, Cs)
+    dst = torch.full((N, Hd, Wd, Cd), 7.0, dtype=torch.float64)
+    seen = torch.zeros(Hd, Wd, dtype=torch.int32)
+    for g in ops.gathers_transposed(N, Hs, Ws, Cs, Hd, Wd, Cd, k, stride, pad):
+        m = IC.grid_mask(g)
+        new, A = IC.gather_gemm_ref(x.permute(0, 2, 3, 1), wgt, b, g)
+        assert float(A[:, ~m].abs().max() if (~m).any() else 0.0) == 0.0 and float(new[:, ~m].abs().max() if (~m).any() else 0.0) == 0.0
+        acc, _ = IC.gather_gemm_ref(x.permute(0, 2, 3, 1), wgt, None, g, old_dst=dst)      # accumulate form: off-grid pixels keep old_dst
+        assert torch.equal(acc[:, ~m], dst[:, ~m])
+        assert float((acc[:, m] - (dst[:, m] + new[:, m] - b)).abs().max()) < 1e-12
+        dst[:, m] = new[:, m]
+        seen += m.int()
+    assert bool((seen == 1).all())
+    assert float((dst - ref).abs().max()) < 1e-12
+    # ReLU is applied after bias and the old value
+    g = ops.gathers_transposed(N, Hs, Ws, Cs, Hd, Wd, Cd, k, stride, pad)[0]
+    r, _ = IC.gather_gemm_ref(x.permute(0, 2, 3, 1), wgt, b, g, relu=True)
+    p, _ = IC.gather_gemm_ref(x.permute(0, 2, 3, 1), wgt, b, g)
+    assert torch.equal(r, p.clamp(min=0))
+
+
+def test_igemm_case_table_plans_are_pinned():
+    """Every row of the case table gets exactly the plan (ast_igemm_plan's five integers) and split-K workspace
+    (ast_igemm_ws_floats) it records, under its own environment: a planner change that moves a row onto another kernel variant
+    fails here, not silently in the GPU test.  Patch rows also pin the pconv_kernel instantiation (ast_pconv_variant: SLB, TM,
+    TN, WALL).  Also: the table holds the configurations it is there for, every patch instantiation the planner can select by
+    itself among them, bar the ones PATCH_NOT_LAUNCHED names."""
+    import igemm_cases as IC
+    seen, seen_pc = set(), {"f32": set(), "bf16": set()}
+    for c in IC.CASES:
+        with IC.case_env(c):
+            plan, ws = IC.plan_of(c.gather(), c.dtype)
+            pc = IC.patch_variant_of(c.gather(), c.dtype)
+        assert (plan, ws) == (c.plan, c.ws), (c.name, plan, ws)
+        assert pc == c.pc, (c.name, pc)
+        fam = "patch" if plan[2] < 0 else ("direct" if plan[2] == 0 else "gathered")
+        assert fam == c.family, c.name
+        g = c.gather()
+        if fam == "gathered":
+            assert (ws > 0) == (plan[3] > 1), c.name
+            E = 4 if c.dtype == "f32" else 8
+            seen.add(("gathered", c.dtype) + plan + ((g.Cs // E) % plan[2] == 0,))
+        elif fam == "direct":
+            E = 4 if c.dtype == "f32" else 8
+            seen.add(("direct", c.dtype, plan[0] // 64, g.Cd, (g.ntaps * (g.Cs // E) + 3) // 4))
+        else:
+            if plan[3] < 0:                                                           # row blocks: rows or the last fragment overhang
+                assert g.Hm % -plan[0] or (-plan[0] * g.Wm) % 16, c.name
+            else:                                                                     # 2-D tiles: overhang on both axes
+                assert g.Hm % -plan[0] and g.Wm % 16, c.name
+            assert pc and (pc[0], pc[2] * 16) == (-plan[2], plan[1]), c.name
+            seen.add(("patch", c.dtype) + plan)
+            seen_pc[c.dtype].add(pc)
+    for dt in ("f32", "bf16"):
+        for bm, bn, kch, kg, splits in ((64, 64, 4, 1, (1,)), (64, 64, 8, 1, (1,)), (64, 64, 8, 4, (1,)), (64, 128, 4, 1, (1,)), (64, 128, 8, 1, (1,)),
+                                        (64, 32, 4, 1, (1, 2, 4)), (128, 32, 4, 1, (1, 2, 4)), (64, 16, 4, 1, (1, 2, 4)), (128, 16, 4, 1, (1, 2, 4))):
+            for ns in splits:
+                for ut in (True, False):
+                    assert ("gathered", dt, bm, bn, kch, ns, kg, ut) in seen, (dt, bm, bn, kch, ns, kg, ut)
+        for cd in (8, 16):
+            for nks in (1, 2, 3):
+                assert ("direct", dt, 1, cd, nks) in seen, (dt, cd, nks)
+        for jt in (2, 4, 8):
+            assert any(s[:3] == ("direct", dt, jt) for s in seen), (dt, jt)
+        for plan in ((-8, 32, -64, 1, 1), (-16, 32, -64, 1, 1), (-8, 64, -64, 1, 1), (-8, 32, -128, 1, 1), (-8, 64, -128, 1, 1), (-12, 64, -128, 1, 1),
+                     (-3, 32, -128, -8, 1), (-9, 32, -128, -12, 1), (-5, 32, -64, -8, 1), (-5, 32, -128, -4, 1)):
+            assert ("patch", dt) + plan in seen, (dt, plan)
+        assert seen_pc[dt] == IC.PATCH_SELECTABLE[dt], (dt, sorted(seen_pc[dt] ^ IC.PATCH_SELECTABLE[dt]))
+    # WALL on and off on the same geometry, for each tile form WALL runs with
+    for name in ("rows", "2d", "rows12", "tiny4"):
+        on, off = IC.BY_NAME[f"p128-wall-{name}-bf16"], IC.BY_NAME[f"p128-nowall-{name}-bf16"]
+        assert on.geom == off.geom and on.pc[3] == 1 and off.pc[3] == 0 and on.pc[:2] == off.pc[:2], name
+    # what the table leaves alone is selectable (so the list is honest), and nothing else is: 64-byte slabs with WALL
+    for slb_tm_tn_wall, geom in (((64, 2, 2, 1), (5, 61, 67, 160, 64, 3, 3, 1, 1, 1)), ((64, 3, 2, 1), (50, 9, 19, 160, 128, 3, 3, 1, 1, 1)),
+                                 ((64, 4, 2, 1), (32, 125, 49, 160, 64, 3, 3, 1, 1, 1))):
+        assert slb_tm_tn_wall in IC.PATCH_NOT_LAUNCHED["bf16"]
+        probe = IC.Case("probe", "patch", "bf16", ("conv",) + geom, (), (), 0)
+        with IC.case_env(probe):
+            assert IC.patch_variant_of(probe.gather(), "bf16") == slb_tm_tn_wall, geom
+    assert not (IC.PATCH_NOT_LAUNCHED["bf16"] & IC.PATCH_SELECTABLE["bf16"]) and len(IC.PATCH_NOT_LAUNCHED["bf16"]) == 3
+    # the f32 direct rows cannot be 3x3: the library refuses 4 source channels, and 8 make 18 chunks
+    import ctypes
+    out = (ctypes.c_int32 * 5)()
+    g4 = IC.conv_gather(2, 7, 19, 4, 8, 3, 3, 1, 1, 1)
+    assert _lib.lib().ast_igemm_plan(g4, _lib.dcode(torch.float32), ctypes.byref(out)) != 0
+
+
+def test_igemm_case_inputs_stay_inside_reference_assumptions():
+    """What the GPU test relies on, checked for every row's seeded inputs: no reference output (plus its bound, plus an old
+    value) comes near the sentinel that marks untouched memory, the bias is non-zero, and the BatchNorm pre-activation
+    fma(x, scale, shift) of the backward-sums form keeps |.| > 1e-3, so that the ReLU mask cannot flip on f32 rounding."""
+    import igemm_cases as IC
+    for c in IC.CASES:
+        g, d = c.gather(), IC.make_inputs(c)
+        assert d["src"].dtype == IC.DTYPES[c.dtype] and float(d["bias"].abs().min()) >= 0.05
+        assert float(IC.bn_pre(d["bn_x"], d["scale"], d["shift"]).abs().min()) > IC.MASK_MARGIN, c.name
+        # A bounds |ref| for every form: products, bias and the old value, all by absolute value
+        amax = (d["src"].double().abs().amax() * d["wgt"].double().abs().sum(dim=(1, 2)).amax() + d["bias"].abs().max() + d["old"].double().abs().max())
+        K = g.ntaps * g.Cs
+        assert float(amax) * (1 + 2 * K * IC.U24 + 2.0 ** -8) < 0.25 * abs(IC.SENTINEL), c.name
+        assert float(torch.tensor(IC.SENTINEL).to(IC.DTYPES[c.dtype])) == IC.SENTINEL
+
+
+def test_igemm_bound_rejects_broken_results():
+    """The derived bound is not vacuous: it rejects the reference with one 16-byte K chunk dropped and with one tail pixel
+    zeroed, for an f32 and a bf16 row of each kernel family; a result 0.999 of the bound away passes, 1.01 on one element fails."""
+    import igemm_cases as IC
+    for name in ("g128x32k4s1-div", "g64x128k8s1-shift", "d-cd8-nks3", "d-cd16-nks1", "p128-tiny4", "p64-rows8"):
+        for dt in ("f32", "bf16"):
+            c = IC.BY_NAME[f"{name}-{dt}"]
+            g, d = c.gather(), IC.make_inputs(c)
+            bf = dt == "bf16"
+            ref, A = IC.gather_gemm_ref(d["src"], d["wgt"], d["bias"], g)
+            bound = IC.out_bound(ref, A, g, bf)
+            m = IC.grid_mask(g)
+            # a result just inside the bound on every element passes, just outside on one element does not
+            near = ref + 0.999 * bound
+            assert bool(((near - ref).abs() <= bound)[:, m].all())
+            over = ref.clone()
+            hd0, wd0 = g.doh, g.dow
+            over[0, hd0, wd0, 0] += 1.01 * bound[0, hd0, wd0, 0]
+            assert int(((over - ref).abs() > bound).sum()) == 1
+            E = 4 if dt == "f32" else 8
+            w2 = d["wgt"].clone()
+            w2[:, g.tap[g.ntaps - 1] >> 16, g.Cs - E:] = 0                      # the last chunk of the last tap: the K tail
+            broken, _ = IC.gather_gemm_ref(d["src"], w2, d["bias"], g)
+            frac = float(((broken - ref).abs() > bound)[:, m].double().mean())
+            assert frac > 0.5, (c.name, frac)                                    # most outputs, not a stray one
+            tail = ref.clone()
+            hd, wd = (g.Hm - 1) * g.dsh + g.doh, (g.Wm - 1) * g.dsw + g.dow
+            tail[g.N - 1, hd, wd, :] = 0                                         # pixel M - 1
+            assert int(((tail - ref).abs() > bound).sum()) == g.Cd, c.name
