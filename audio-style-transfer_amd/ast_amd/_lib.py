@@ -132,6 +132,16 @@ _SIGS = {
     "ast_bigk_gemm_det": ([vp, vp, vp, vp, i32, i32, i32, vp, C.c_long, vp], i32),
     "ast_bign_dgrad_det_ws_floats": ([i32, i32, i32], C.c_long),
     "ast_bign_dgrad_det": ([vp, vp, vp, i32, i32, i32, i32, vp, C.c_long, vp], i32),
+    # wide token path: 65 .. AST_WIDE_MAX_ROWS rows (include/ast_hip.h)
+    "ast_skinny_gemm_wide": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+    "ast_skinny_gemm_wide_ex": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, C.c_uint64, vp, vp], i32),
+    "ast_linear_wgrad_wide": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "ast_bigk_gemm_wide": ([vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    "ast_bigk_gemm_wide_det_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_bigk_gemm_wide_det": ([vp, vp, vp, vp, i32, i32, i32, vp, C.c_long, vp], i32),
+    "ast_bign_dgrad_wide": ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    "ast_bign_dgrad_wide_det_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_bign_dgrad_wide_det": ([vp, vp, vp, i32, i32, i32, i32, vp, C.c_long, vp], i32),
     "ast_tok_max_ops": ([], i32),
     "ast_tok_program": ([vp, i32, i32, i32, vp, vp, vp, vp], i32),
 }

@@ -455,6 +455,32 @@ class ConvT2dFn(torch.autograd.Function):
 
 
 SKINNY_MAX_ROWS = 64
+WIDE_MAX_ROWS = 1024            # AST_WIDE_MAX_ROWS: the row-blocked entries (ast_*_wide) take 65 .. 1024 token rows
+
+
+def _skinny_gemm(rows, *args):
+    """ast_skinny_gemm, or its 64-rows-per-workgroup form above SKINNY_MAX_ROWS; args = (x, w, bias, y, N, K, ldw, ldy, relu)."""
+    x, w, b, y, *rest = args
+    name = "ast_skinny_gemm" if rows <= SKINNY_MAX_ROWS else "ast_skinny_gemm_wide"
+    check(getattr(lib(), name)(x, w, b, y, rows, *rest, stream()), name)
+
+
+def _skinny_gemm_ex(rows, *args):
+    x, w, b, y, *rest = args
+    name = "ast_skinny_gemm_ex" if rows <= SKINNY_MAX_ROWS else "ast_skinny_gemm_wide_ex"
+    check(getattr(lib(), name)(x, w, b, y, rows, *rest, stream()), name)
+
+
+def _linear_wgrad(rows, *args):
+    dy, x, dw, db, *rest = args
+    name = "ast_linear_wgrad" if rows <= SKINNY_MAX_ROWS else "ast_linear_wgrad_wide"
+    check(getattr(lib(), name)(dy, x, dw, db, rows, *rest, stream()), name)
+
+
+def _token_rows_ok(rows):
+    """Row counts of the hand-written token kernels: <= 64 always; 65 .. 1024 (the wide entries) in deterministic mode, where the
+    igemm path of the default mode has no weight gradient without atomics."""
+    return rows <= SKINNY_MAX_ROWS or (config.deterministic and rows <= WIDE_MAX_ROWS)
 
 
 class LinearFn(torch.autograd.Function):
@@ -467,14 +493,14 @@ class LinearFn(torch.autograd.Function):
         x = x.contiguous()
         rows = x.shape[0]
         assert x.shape[1] == pw.Cip and x.dtype == pw.dtype, (x.shape, pw.Cip, x.dtype, pw.dtype)
-        ctx.skinny = rows <= SKINNY_MAX_ROWS and pw.KK == 1 and pw.u is None and pw.Ci == pw.Cip
+        ctx.skinny = (_token_rows_ok(rows) and pw.KK == 1 and pw.u is None and pw.Ci == pw.Cip
+                      and (rows <= SKINNY_MAX_ROWS or x.dtype == torch.float32))
         y = torch.empty((rows, pw.Cop), dtype=x.dtype, device=x.device)
         if ctx.skinny:
             if pw.Cop != pw.Co:
                 y.zero_()
             b = None if pw.bias is None else pw.bias.data_ptr() + 4 * pw.b_off
-            check(lib().ast_skinny_gemm(ptr(x), pw.weight.data_ptr() + 4 * pw.w_off, b, ptr(y), rows, pw.Co, pw.Ci, pw.s_co,
-                                        pw.Cop, int(relu), stream()), "ast_skinny_gemm")
+            _skinny_gemm(rows, ptr(x), pw.weight.data_ptr() + 4 * pw.w_off, b, ptr(y), pw.Co, pw.Ci, pw.s_co, pw.Cop, int(relu))
         else:
             g, _ = gather_direct(rows, 1, 1, pw.Cip, pw.Cop, 1, 1, 0)
             _igemm(x, pw.wf, pw.bias_ptr_tensor(), y, g, 2 if relu else 0)
@@ -499,17 +525,15 @@ class LinearFn(torch.autograd.Function):
             else:
                 gw = acc_grad(pw.weight)
                 gb = None if pw.bias is None else acc_grad(pw.bias).data_ptr() + 4 * pw.b_off
-                check(lib().ast_linear_wgrad(ptr(dy), ptr(x), gw.data_ptr() + 4 * pw.w_off, gb, rows, pw.Co, pw.Ci, pw.Cop, pw.s_co,
-                                             stream()), "ast_linear_wgrad")
+                _linear_wgrad(rows, ptr(dy), ptr(x), gw.data_ptr() + 4 * pw.w_off, gb, pw.Co, pw.Ci, pw.Cop, pw.s_co)
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)       # dx[m][k] = sum_n dy[m][n] Wt[k][n], Wt = packed [Ci][Cop]
-                check(lib().ast_skinny_gemm(ptr(dy), ptr(pw.wb), None, ptr(dx), rows, pw.Ci, pw.Cop, pw.Cop, pw.Cip, 0, stream()),
-                      "ast_skinny_gemm")
+                _skinny_gemm(rows, ptr(dy), ptr(pw.wb), None, ptr(dx), pw.Ci, pw.Cop, pw.Cop, pw.Cip, 0)
             return dx, None, None, None
         if config.deterministic:
             # not on the train step's path (every linear there takes the skinny form): its gradient staging adds with atomics
-            raise RuntimeError("LinearFn: the non-skinny weight gradient (> 64 token rows, spectral norm or unpadded channels) has no "
-                               "deterministic form")
+            raise RuntimeError(f"LinearFn: the non-skinny weight gradient (> {WIDE_MAX_ROWS} token rows, spectral norm, unpadded channels "
+                               "or bf16 above 64 rows) has no deterministic form")
         g, _ = gather_direct(rows, 1, 1, pw.Cip, pw.Cop, 1, 1, 0)
         dwp = torch.zeros((pw.Cop, 1, pw.Cip), dtype=torch.float32, device=x.device)
         _wgrad(dy, x, dwp, g)
@@ -523,7 +547,7 @@ class LinearFn(torch.autograd.Function):
 
 
 class BigLinearFn(torch.autograd.Function):
-    """nn.Linear with one HUGE dimension on <= 64 token rows, straight on the f32 parameter (no packed copies: the
+    """nn.Linear with one HUGE dimension on <= 1024 token rows (above 64: the row-blocked ast_*_wide entries), straight on the f32 parameter (no packed copies: the
     weight is 301 MB) -- SimpleDecoder_TransformerOnly.py:16-17.  in_features huge: ast_bigk_gemm (the input is data,
     no input gradient exists on the reference's path); out_features huge: ast_skinny_gemm forward, ast_bign_dgrad
     backward.  Weight/bias gradients: ast_linear_wgrad into the parameter gradients."""
@@ -534,17 +558,19 @@ class BigLinearFn(torch.autograd.Function):
         rows, K = x.shape
         N = weight.shape[0]
         assert weight.shape[1] == K and x.dtype == torch.float32 and weight.is_contiguous()
-        if rows > SKINNY_MAX_ROWS:
-            raise RuntimeError(f"BigLinearFn: {rows} token rows > {SKINNY_MAX_ROWS}")
+        if rows > WIDE_MAX_ROWS:
+            raise RuntimeError(f"BigLinearFn: {rows} token rows > {WIDE_MAX_ROWS} (the cap of the wide token path, AST_WIDE_MAX_ROWS)")
         y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
         ctx.big_in = K > N
+        sfx = "" if rows <= SKINNY_MAX_ROWS else "_wide"
         if ctx.big_in and config.deterministic:     # per-K-chunk slabs added in chunk order
-            ws = det_ws(lib().ast_bigk_gemm_det_ws_floats(rows, N, K), x.device)
-            check(lib().ast_bigk_gemm_det(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, ptr(ws), ws.numel(), stream()), "ast_bigk_gemm_det")
+            ws = det_ws(getattr(lib(), f"ast_bigk_gemm{sfx}_det_ws_floats")(rows, N, K), x.device)
+            check(getattr(lib(), f"ast_bigk_gemm{sfx}_det")(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, ptr(ws), ws.numel(), stream()),
+                  f"ast_bigk_gemm{sfx}_det")
         elif ctx.big_in:
-            check(lib().ast_bigk_gemm(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, N, stream()), "ast_bigk_gemm")
+            check(getattr(lib(), f"ast_bigk_gemm{sfx}")(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, N, stream()), f"ast_bigk_gemm{sfx}")
         else:
-            check(lib().ast_skinny_gemm(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, 0, stream()), "ast_skinny_gemm")
+            _skinny_gemm(rows, ptr(x), ptr(weight), ptr(bias), ptr(y), N, K, K, N, 0)
         ctx.save_for_backward(x)
         ctx.weight, ctx.bias = weight, bias
         return y
@@ -556,23 +582,24 @@ class BigLinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         rows, K = x.shape
         N = w.shape[0]
-        check(lib().ast_linear_wgrad(ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, rows, N, K, N, K,
-                                     stream()), "ast_linear_wgrad")
+        _linear_wgrad(rows, ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, N, K, N, K)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.big_in:
                 raise NotImplementedError("BigLinearFn: input gradient of the huge-input linear (its input is data on the reference's path)")
             dx = torch.empty_like(x)
+            sfx = "" if rows <= SKINNY_MAX_ROWS else "_wide"
             if config.deterministic:                # per-n-chunk slabs added in chunk order
-                ws = det_ws(lib().ast_bign_dgrad_det_ws_floats(rows, N, K), x.device)
-                check(lib().ast_bign_dgrad_det(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel(), stream()), "ast_bign_dgrad_det")
+                ws = det_ws(getattr(lib(), f"ast_bign_dgrad{sfx}_det_ws_floats")(rows, N, K), x.device)
+                check(getattr(lib(), f"ast_bign_dgrad{sfx}_det")(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel(), stream()),
+                      f"ast_bign_dgrad{sfx}_det")
             else:
-                check(lib().ast_bign_dgrad(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, stream()), "ast_bign_dgrad")
+                check(getattr(lib(), f"ast_bign_dgrad{sfx}")(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, stream()), f"ast_bign_dgrad{sfx}")
         return dx, None, None
 
 
 class FFNFn(torch.autograd.Function):
-    """linear2(dropout(relu(linear1(x)))) on <= 64 token rows in two launches forward and two backward
+    """linear2(dropout(relu(linear1(x)))) on <= 64 token rows (deterministic mode: <= 1024, the wide entries) in two launches forward and two backward
     (transformer.py _ff_block as style_encoder.py:181-187 / new_decoder.py:111-118 use it): the dropout mask is
     drawn in linear1's epilogue and stored combined with the ReLU mask; backward applies it in the epilogue of
     dh = dy W2.  Weight gradients go to the bank's batched launch."""
@@ -590,11 +617,10 @@ class FFNFn(torch.autograd.Function):
             _DropState.calls += 1
             seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
             mask = torch.empty_like(h)
-        check(lib().ast_skinny_gemm_ex(ptr(x), pw1.weight.data_ptr() + 4 * pw1.w_off, pw1.bias.data_ptr() + 4 * pw1.b_off, ptr(h), rows,
-                                       pw1.Co, pw1.Ci, pw1.s_co, pw1.Cop, 1, None, ptr(mask), float(p), seed, ptr(ctr), stream()),
-              "ast_skinny_gemm_ex")
-        check(lib().ast_skinny_gemm(ptr(h), pw2.weight.data_ptr() + 4 * pw2.w_off, pw2.bias.data_ptr() + 4 * pw2.b_off, ptr(y), rows,
-                                    pw2.Co, pw2.Ci, pw2.s_co, pw2.Cop, 0, stream()), "ast_skinny_gemm")
+        _skinny_gemm_ex(rows, ptr(x), pw1.weight.data_ptr() + 4 * pw1.w_off, pw1.bias.data_ptr() + 4 * pw1.b_off, ptr(h),
+                        pw1.Co, pw1.Ci, pw1.s_co, pw1.Cop, 1, None, ptr(mask), float(p), seed, ptr(ctr))
+        _skinny_gemm(rows, ptr(h), pw2.weight.data_ptr() + 4 * pw2.w_off, pw2.bias.data_ptr() + 4 * pw2.b_off, ptr(y),
+                     pw2.Co, pw2.Ci, pw2.s_co, pw2.Cop, 0)
         ctx.save_for_backward(x, h, mask)
         ctx.pw1, ctx.pw2 = pw1, pw2
         return y
@@ -608,25 +634,22 @@ class FFNFn(torch.autograd.Function):
         pw2.bank.defer_linear_wgrad(pw2, dy, h)
         dh = torch.empty_like(h)
         if mask is None:                       # eval-mode autograd: ReLU mask only
-            check(lib().ast_skinny_gemm(ptr(dy), ptr(pw2.wb), None, ptr(dh), rows, pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0, stream()),
-                  "ast_skinny_gemm")
+            _skinny_gemm(rows, ptr(dy), ptr(pw2.wb), None, ptr(dh), pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0)
             dz = torch.empty_like(dh)
             check(lib().ast_relu_bwd(ptr(dh), ptr(h), ptr(dz), dh.numel(), dcode(dh.dtype), stream()), "ast_relu_bwd")
             dh = dz
         else:
-            check(lib().ast_skinny_gemm_ex(ptr(dy), ptr(pw2.wb), None, ptr(dh), rows, pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0, ptr(mask), None,
-                                           0.0, 0, None, stream()), "ast_skinny_gemm_ex")
+            _skinny_gemm_ex(rows, ptr(dy), ptr(pw2.wb), None, ptr(dh), pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0, ptr(mask), None, 0.0, 0, None)
         pw1.bank.defer_linear_wgrad(pw1, dh, x)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            check(lib().ast_skinny_gemm(ptr(dh), ptr(pw1.wb), None, ptr(dx), rows, pw1.Ci, pw1.Cop, pw1.Cop, pw1.Cip, 0, stream()),
-                  "ast_skinny_gemm")
+            _skinny_gemm(rows, ptr(dh), ptr(pw1.wb), None, ptr(dx), pw1.Ci, pw1.Cop, pw1.Cop, pw1.Cip, 0)
         return dx, None, None, None, None, None
 
 
 def _skinny_ok(pw, rows):
-    return (rows <= SKINNY_MAX_ROWS and pw.KK == 1 and pw.u is None and pw.Ci == pw.Cip and pw.Co == pw.Cop and pw.bank is not None
+    return (_token_rows_ok(rows) and pw.KK == 1 and pw.u is None and pw.Ci == pw.Cip and pw.Co == pw.Cop and pw.bank is not None
             and pw.bias is not None)
 
 

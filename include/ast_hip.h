@@ -440,6 +440,37 @@ int ast_bign_dgrad_det(const float* dy, const float* w, float* dx, int M, int N,
 /* ast_weight_grads_flush_t with the <dWp, W/sigma> inner products through per-tile partials (ws >= ntiles floats) summed in tile order */
 int ast_weight_grads_flush_det(const ast_weight_desc_t* descs, const void* tiles, int ntiles, float* ws, long ws_floats, void* stream);
 
+/* ---- wide token path: 65 .. AST_WIDE_MAX_ROWS token rows (f32) ----------------------------------------------------------------
+ * The entries above stop at 64 rows (one 16-row tile per workgroup, sized for B*(S+1) <= 40).  These take M in
+ * 65 .. AST_WIDE_MAX_ROWS and refuse anything else; a workgroup covers 64 rows (four 16-row v_mfma_f32_16x16x4_f32 accumulator
+ * tiles per wave), so a weight byte is fetched once per 64 rows.  Arguments, epilogues, alignment and K / ldw rules are those of
+ * the <= 64-row twin named in each line.  Only ast_bigk_gemm_wide and ast_bign_dgrad_wide (default mode) add with f32 atomics.
+ * ast_skinny_gemm_wide[_ex]: every token linear of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
+ *   new_decoder.py:49-51,111-119) and embedding_to_stft forward (SimpleDecoder_TransformerOnly.py:17,62-66) at a larger batch.
+ *   The dropout mask of element (m, n) depends on (seed, counter, m * ldy + n) only, as in ast_skinny_gemm_ex.
+ * ast_linear_wgrad_wide: dW += dy^T x, db += colsum(dy) (both linears of SimpleDecoder_TransformerOnly.py:16-17 and any token
+ *   linear without a weight bank).  A wave owns its dW tile, walks the rows in ascending 64-row chunks and does one read-add-store:
+ *   deterministic by construction, used in both modes.
+ * ast_bigk_gemm_wide[_det]: stft_to_embedding (SimpleDecoder_TransformerOnly.py:16,56-60).  _det: one [M][N] slab per 1024-k chunk in
+ *   ws (ast_bigk_gemm_wide_det_ws_floats = ceil(K/1024) * M * N; -1 on refused sizes) + ast_ordered_sum; needs ldy == N.
+ * ast_bign_dgrad_wide[_det]: data gradient of embedding_to_stft (SimpleDecoder_TransformerOnly.py:17,62-66), K <= 256.  _det: one
+ *   [M][K] slab per 512-n chunk (ast_bign_dgrad_wide_det_ws_floats = ceil(N/512) * M * K; -1 on refused sizes) + ast_ordered_sum. */
+#define AST_WIDE_MAX_ROWS 1024
+int ast_skinny_gemm_wide(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw, int ldy, int relu,
+                         void* stream);
+int ast_skinny_gemm_wide_ex(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw, int ldy,
+                            int relu, const float* mul_mask, float* drop_mask, float p, uint64_t seed, const int64_t* d_offset,
+                            void* stream);
+int ast_linear_wgrad_wide(const float* dy, const float* x, float* dW, float* db, int M, int N, int K, int lddy, int ldw, void* stream);
+int ast_bigk_gemm_wide(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldy, void* stream);
+long ast_bigk_gemm_wide_det_ws_floats(int M, int N, int K);
+int ast_bigk_gemm_wide_det(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, float* ws, long ws_floats,
+                           void* stream);
+int ast_bign_dgrad_wide(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, void* stream);
+long ast_bign_dgrad_wide_det_ws_floats(int M, int N, int K);
+int ast_bign_dgrad_wide_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, float* ws, long ws_floats,
+                            void* stream);
+
 /* ---- token programs: transformer layers in one launch (csrc/tokprog.hip) ------------------------------------------------
  * Replaces, for the <= 64 token rows of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
  * new_decoder.py:49-51,111-119), the per-operator launches above (ast_skinny_gemm*, ast_attn_fwd_p / ast_attn_bwd_p,
