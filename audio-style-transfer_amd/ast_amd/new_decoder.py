@@ -117,6 +117,9 @@ class Decoder(nn.Module):
 
     def _memory(self, content_emb, class_emb):
         B, Sc, D = content_emb.shape
+        if 2 * Sc > ops.ATTN_MAX_L:
+            raise ValueError(f"{Sc} content sections make {2 * Sc} memory tokens; the attention core takes {ops.ATTN_MAX_L} "
+                             f"(at most {ops.ATTN_MAX_L // 2} sections per clip)")
         cm = L.linear(content_emb.reshape(B * Sc, D), self._cp).view(B, Sc, D)
         km = L.linear(class_emb, self._kp).unsqueeze(1).expand(-1, Sc, -1)
         return ops.dropout(torch.cat([cm, km], dim=1), self.dropout.p, self.training)
@@ -178,6 +181,8 @@ class Decoder(nn.Module):
         B = memory.size(0)
         if target_length is None:
             target_length = memory.size(1) // 2
+        if target_length > self.pos_encoding.pe.size(1):
+            raise ValueError(f"target_length {target_length}, but the positional table holds {self.pos_encoding.pe.size(1)} positions")
         if self.decode_mode == "kv_cache" and not torch.is_grad_enabled():
             return self._inference_pass_cached(memory, target_length)
         seq = self.start_token.expand(B, -1, -1)

@@ -456,6 +456,7 @@ class ConvT2dFn(torch.autograd.Function):
 
 SKINNY_MAX_ROWS = 64
 WIDE_MAX_ROWS = 1024            # AST_WIDE_MAX_ROWS: the row-blocked entries (ast_*_wide) take 65 .. 1024 token rows
+ATTN_MAX_L = 1024               # AST_ATTN_MAX_L: the attention core takes up to 1024 query and 1024 key tokens (past 16: csrc/attn.hip)
 
 
 def _skinny_gemm(rows, *args):
@@ -1229,7 +1230,8 @@ class CastFn(torch.autograd.Function):
 # attention core + dropout
 # ---------------------------------------------------------------------------
 class AttnCoreFn(torch.autograd.Function):
-    """softmax(QK^T/sqrt(dh) + causal) V for <=16 tokens.  q:(B*Lq, ldq) k,v views of (B*Lk, ldk).
+    """softmax(QK^T/sqrt(dh) + causal) V for up to ATTN_MAX_L query and key tokens (one wave per (batch, head) up to 16 x 16,
+    tiles of 16 queries x 16 keys on f32 MFMA past that; no float atomics either way).  q:(B*Lq, ldq) k,v views of (B*Lk, ldk).
     p_drop > 0: the attention-probability dropout is drawn inside the kernels (same values forward and backward)."""
 
     @staticmethod

@@ -31,6 +31,8 @@ class SinusoidalPositionalEncoding(nn.Module):
         self.register_buffer("pe", table[None])
 
     def forward(self, x):
+        if x.size(1) > self.pe.size(1):
+            raise ValueError(f"{x.size(1)} tokens, but the positional table holds {self.pe.size(1)} positions")
         return x + self.pe[:, :x.size(1)]
 
 

@@ -154,3 +154,12 @@ __device__ __forceinline__ float block_sum(float v, float* red /* >= 17 floats o
   do { if ((dtype) == AST_F32) { using T = float; __VA_ARGS__; } \
        else if ((dtype) == AST_BF16) { using T = bf16_t; __VA_ARGS__; } \
        else AST_FAIL("%s: bad dtype %d", __func__, (int)(dtype)); } while (0)
+
+// ---- attention core past 16 tokens (attn.hip); ast_attn_fwd_p / ast_attn_bwd_p (misc.hip) dispatch here.  Not exported.
+#define AST_HIDDEN __attribute__((visibility("hidden")))
+AST_HIDDEN int attn_long_fwd_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                                    int dh, int ldq, int ldk, int ldo, int causal, const float* drop_mask, float p, uint64_t seed,
+                                    const int64_t* d_offset, void* stream);
+AST_HIDDEN int attn_long_bwd_launch(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
+                                    float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
+                                    const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream);

@@ -490,7 +490,9 @@ extern "C" int ast_attn_fwd_p(const float* q, const float* k, const float* v, fl
                               int dh, int ldq, int ldk, int ldo, int causal, const float* drop_mask, float p, uint64_t seed,
                               const int64_t* d_offset, void* stream) {
   if (!q || !k || !v || !o || !probs || p < 0.f || p >= 1.f) AST_FAIL("ast_attn_fwd: bad args");
-  if (Lq < 1 || Lk < 1 || Lq > MAXL || Lk > MAXL || dh < 1 || dh > 64) AST_FAIL("ast_attn_fwd: needs 1<=L<=%d and dh<=64 (Lq=%d Lk=%d dh=%d)", MAXL, Lq, Lk, dh);
+  if (Lq < 1 || Lk < 1 || dh < 1 || dh > 64) AST_FAIL("ast_attn_fwd: needs 1<=L and 1<=dh<=64 (Lq=%d Lk=%d dh=%d)", Lq, Lk, dh);
+  if (Lq > MAXL || Lk > MAXL)                                          // 17 .. AST_ATTN_MAX_L tokens: the tiled kernels of attn.hip
+    return attn_long_fwd_launch(q, k, v, o, probs, B, H, Lq, Lk, dh, ldq, ldk, ldo, causal, drop_mask, p, seed, d_offset, stream);
 #define AST_ATTN_FWD(ML_)                                                                                                          \
   hipLaunchKernelGGL(attn_fwd_kernel<ML_>, dim3(B * H), dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H, Lq, Lk, dh, ldq, ldk, \
                      ldo, causal, drop_mask, p, seed, d_offset)
@@ -507,7 +509,9 @@ extern "C" int ast_attn_bwd_p(const float* dout, const float* q, const float* k,
                               float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, const float* drop_mask,
                               float p, uint64_t seed, const int64_t* d_offset, void* stream) {
   if (!dout || !q || !k || !v || !probs || !dq || !dk || !dv || p < 0.f || p >= 1.f) AST_FAIL("ast_attn_bwd: bad args");
-  if (Lq < 1 || Lk < 1 || Lq > MAXL || Lk > MAXL || dh < 1 || dh > 64) AST_FAIL("ast_attn_bwd: needs 1<=L<=%d and dh<=64", MAXL);
+  if (Lq < 1 || Lk < 1 || dh < 1 || dh > 64) AST_FAIL("ast_attn_bwd: needs 1<=L and 1<=dh<=64 (Lq=%d Lk=%d dh=%d)", Lq, Lk, dh);
+  if (Lq > MAXL || Lk > MAXL)
+    return attn_long_bwd_launch(dout, q, k, v, probs, dq, dk, dv, B, H, Lq, Lk, dh, ldq, ldk, ldo, drop_mask, p, seed, d_offset, stream);
 #define AST_ATTN_BWD(ML_)                                                                                                           \
   hipLaunchKernelGGL(attn_bwd_kernel<ML_>, dim3(B * H), dim3(64), 0, (hipStream_t)stream, dout, q, k, v, probs, dq, dk, dv, H, Lq, Lk, \
                      dh, ldq, ldk, ldo, drop_mask, p, seed, d_offset)

@@ -278,7 +278,13 @@ int ast_bilinear_bwd(const float* dy, void* dx, int N, int C, int Cp, int H, int
 
 /* ---- small-sequence attention core (nn.MultiheadAttention inner product part) - */
 /* q:(B,Lq,ldq) k,v:(B,Lk,ldk) rows of f32 (already projected); heads of width dh; causal optional;
- * p_out (B,H,Lq,Lk) saved probabilities (after dropout mask scaling); drop_mask optional (B,H,Lq,Lk) of 0/1/(1-p) */
+ * p_out (B,H,Lq,Lk) saved probabilities (after dropout mask scaling); drop_mask optional (B,H,Lq,Lk) of 0/1/(1-p)
+ * Lq and Lk up to AST_ATTN_MAX_L tokens, dh <= 64.  Up to 16 x 16 tokens: one wave per (batch, head) (csrc/misc.hip).  Past
+ * that (the decoder's memory is 2 S tokens, so from S = 9 sections on): tiles of 16 queries x 16 keys on
+ * v_mfma_f32_16x16x4_f32 (csrc/attn.hip), which also need dh % 4 == 0, row strides that are multiples of 4 floats and 16-byte
+ * aligned q / k / v / o / gradient pointers.  No float atomics on either path; the backward writes every element of dq, dk, dv
+ * (and uses dq as scratch before it does). */
+#define AST_ATTN_MAX_L 1024
 int ast_attn_fwd(const float* q, const float* k, const float* v, float* o, float* probs,
                  int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, int causal,
                  const float* drop_mask, void* stream);

@@ -177,6 +177,33 @@ def run_simple_decoder(B=2, S=2):
     print("simple decoder: loss", float(rec["total_loss"]), "out_abs", g["out_abs"])
 
 
+def run_decoder_long(B=2, S=9):
+    """The decoder alone at S = 9 sections (18 memory tokens: attention past 16 tokens), on seeded embeddings as
+    run_simple_decoder: teacher-forced forward + loss + backward in train mode, then the eval-mode autoregressive decode
+    (with the buffers that one training forward updated).  Writes decoder_b2s9.npz only; callable on its own."""
+    dec, digest = build("decoder")
+    content = sp.seeded_normal((B, S, 256), 5101)
+    cls = sp.seeded_normal((B, 256), 5102)
+    y = sp.seeded_input(B, S, seed=5103, F=513)
+    sub_long = lambda t: t[:, :, :, ::23, ::29].detach().numpy().copy()
+    dec.train()
+    out = dec(content, cls, y=y)
+    rec = r_dec.compute_comprehensive_loss(out, y)
+    rec["total_loss"].backward()
+    g = {"layout_digest": np.frombuffer(digest.encode(), dtype=np.uint8), "out_sub": sub_long(out)}
+    for k, v in rec.items():
+        g["rec_" + k] = float(v)
+    gn = grad_norms(dec)
+    g["gradnorm_keys"] = np.array(sorted(gn.keys()))
+    g["gradnorm_vals"] = np.array([gn[k] for k in sorted(gn.keys())], dtype=np.float64)
+    dec.eval()
+    with torch.no_grad():
+        ar = dec(content, cls, target_length=S)
+    g["infer_sub"] = sub_long(ar)
+    np.savez_compressed(os.path.join(OUT, f"decoder_b{B}s{S}.npz"), **g)
+    print("decoder long: loss", float(rec["total_loss"]), "infer mean abs", float(ar.abs().mean()))
+
+
 def run_losses():
     g = {}
     disc, _ = build("disc")
@@ -255,4 +282,6 @@ if __name__ == "__main__":
         run_model_config(4, 1, "b4s1")
     if "simple" in which:
         run_simple_decoder(2, 2)
+    if "decoder_b2s9" in which:
+        run_decoder_long(2, 9)
     assert not os.path.exists(os.path.join(REF, "__pycache__")), "bytecode leaked into the reference tree"
