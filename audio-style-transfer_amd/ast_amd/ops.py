@@ -459,23 +459,18 @@ WIDE_MAX_ROWS = 1024            # AST_WIDE_MAX_ROWS: the row-blocked entries (as
 ATTN_MAX_L = 1024               # AST_ATTN_MAX_L: the attention core takes up to 1024 query and 1024 key tokens (past 16: csrc/attn.hip)
 
 
-def _skinny_gemm(rows, *args):
-    """ast_skinny_gemm, or its 64-rows-per-workgroup form above SKINNY_MAX_ROWS; args = (x, w, bias, y, N, K, ldw, ldy, relu)."""
-    x, w, b, y, *rest = args
-    name = "ast_skinny_gemm" if rows <= SKINNY_MAX_ROWS else "ast_skinny_gemm_wide"
-    check(getattr(lib(), name)(x, w, b, y, rows, *rest, stream()), name)
+def _token_entry(who, stem, rows, tail=""):
+    """Name of the csrc/skinny.hip entry for `rows` token rows: ast_<stem><tail> up to SKINNY_MAX_ROWS, its 64-rows-per-workgroup form
+    ast_<stem>_wide<tail> up to WIDE_MAX_ROWS; `who` is the caller named when there are more."""
+    if rows > WIDE_MAX_ROWS:
+        raise RuntimeError(f"{who}: {rows} token rows > {WIDE_MAX_ROWS} (the cap of the wide token path, AST_WIDE_MAX_ROWS)")
+    return f"ast_{stem}{'' if rows <= SKINNY_MAX_ROWS else '_wide'}{tail}"
 
 
-def _skinny_gemm_ex(rows, *args):
-    x, w, b, y, *rest = args
-    name = "ast_skinny_gemm_ex" if rows <= SKINNY_MAX_ROWS else "ast_skinny_gemm_wide_ex"
-    check(getattr(lib(), name)(x, w, b, y, rows, *rest, stream()), name)
-
-
-def _linear_wgrad(rows, *args):
-    dy, x, dw, db, *rest = args
-    name = "ast_linear_wgrad" if rows <= SKINNY_MAX_ROWS else "ast_linear_wgrad_wide"
-    check(getattr(lib(), name)(dy, x, dw, db, rows, *rest, stream()), name)
+def _token_call(who, stem, rows, tail, *args):
+    """That entry, called with args on the current stream and checked."""
+    name = _token_entry(who, stem, rows, tail)
+    check(getattr(lib(), name)(*args, stream()), name)
 
 
 def _token_rows_ok(rows):
@@ -501,7 +496,7 @@ class LinearFn(torch.autograd.Function):
             if pw.Cop != pw.Co:
                 y.zero_()
             b = None if pw.bias is None else pw.bias.data_ptr() + 4 * pw.b_off
-            _skinny_gemm(rows, ptr(x), pw.weight.data_ptr() + 4 * pw.w_off, b, ptr(y), pw.Co, pw.Ci, pw.s_co, pw.Cop, int(relu))
+            _token_call("LinearFn", "skinny_gemm", rows, "", ptr(x), pw.weight.data_ptr() + 4 * pw.w_off, b, ptr(y), rows, pw.Co, pw.Ci, pw.s_co, pw.Cop, int(relu))
         else:
             g, _ = gather_direct(rows, 1, 1, pw.Cip, pw.Cop, 1, 1, 0)
             _igemm(x, pw.wf, pw.bias_ptr_tensor(), y, g, 2 if relu else 0)
@@ -526,10 +521,10 @@ class LinearFn(torch.autograd.Function):
             else:
                 gw = acc_grad(pw.weight)
                 gb = None if pw.bias is None else acc_grad(pw.bias).data_ptr() + 4 * pw.b_off
-                _linear_wgrad(rows, ptr(dy), ptr(x), gw.data_ptr() + 4 * pw.w_off, gb, pw.Co, pw.Ci, pw.Cop, pw.s_co)
+                _token_call("LinearFn", "linear_wgrad", rows, "", ptr(dy), ptr(x), gw.data_ptr() + 4 * pw.w_off, gb, rows, pw.Co, pw.Ci, pw.Cop, pw.s_co)
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)       # dx[m][k] = sum_n dy[m][n] Wt[k][n], Wt = packed [Ci][Cop]
-                _skinny_gemm(rows, ptr(dy), ptr(pw.wb), None, ptr(dx), pw.Ci, pw.Cop, pw.Cop, pw.Cip, 0)
+                _token_call("LinearFn", "skinny_gemm", rows, "", ptr(dy), ptr(pw.wb), None, ptr(dx), rows, pw.Ci, pw.Cop, pw.Cop, pw.Cip, 0)
             return dx, None, None, None
         if config.deterministic:
             # not on the train step's path (every linear there takes the skinny form): its gradient staging adds with atomics
@@ -559,19 +554,17 @@ class BigLinearFn(torch.autograd.Function):
         rows, K = x.shape
         N = weight.shape[0]
         assert weight.shape[1] == K and x.dtype == torch.float32 and weight.is_contiguous()
-        if rows > WIDE_MAX_ROWS:
-            raise RuntimeError(f"BigLinearFn: {rows} token rows > {WIDE_MAX_ROWS} (the cap of the wide token path, AST_WIDE_MAX_ROWS)")
-        y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
         ctx.big_in = K > N
-        sfx = "" if rows <= SKINNY_MAX_ROWS else "_wide"
-        if ctx.big_in and config.deterministic:     # per-K-chunk slabs added in chunk order
-            ws = det_ws(getattr(lib(), f"ast_bigk_gemm{sfx}_det_ws_floats")(rows, N, K), x.device)
-            check(getattr(lib(), f"ast_bigk_gemm{sfx}_det")(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, ptr(ws), ws.numel(), stream()),
-                  f"ast_bigk_gemm{sfx}_det")
+        stem, tail = ("bigk_gemm", "_det" if config.deterministic else "") if ctx.big_in else ("skinny_gemm", "")
+        _token_entry("BigLinearFn", stem, rows, tail)      # more than WIDE_MAX_ROWS rows raise before anything is allocated
+        y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+        if tail:                                    # per-K-chunk slabs added in chunk order
+            ws = det_ws(getattr(lib(), _token_entry("BigLinearFn", stem, rows, "_det_ws_floats"))(rows, N, K), x.device)
+            _token_call("BigLinearFn", stem, rows, tail, ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, ptr(ws), ws.numel())
         elif ctx.big_in:
-            check(getattr(lib(), f"ast_bigk_gemm{sfx}")(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, N, stream()), f"ast_bigk_gemm{sfx}")
+            _token_call("BigLinearFn", stem, rows, tail, ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, N)
         else:
-            _skinny_gemm(rows, ptr(x), ptr(weight), ptr(bias), ptr(y), N, K, K, N, 0)
+            _token_call("BigLinearFn", stem, rows, tail, ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, 0)
         ctx.save_for_backward(x)
         ctx.weight, ctx.bias = weight, bias
         return y
@@ -583,19 +576,17 @@ class BigLinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         rows, K = x.shape
         N = w.shape[0]
-        _linear_wgrad(rows, ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, N, K, N, K)
+        _token_call("BigLinearFn", "linear_wgrad", rows, "", ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, rows, N, K, N, K)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.big_in:
                 raise NotImplementedError("BigLinearFn: input gradient of the huge-input linear (its input is data on the reference's path)")
             dx = torch.empty_like(x)
-            sfx = "" if rows <= SKINNY_MAX_ROWS else "_wide"
             if config.deterministic:                # per-n-chunk slabs added in chunk order
-                ws = det_ws(getattr(lib(), f"ast_bign_dgrad{sfx}_det_ws_floats")(rows, N, K), x.device)
-                check(getattr(lib(), f"ast_bign_dgrad{sfx}_det")(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel(), stream()),
-                      f"ast_bign_dgrad{sfx}_det")
+                ws = det_ws(getattr(lib(), _token_entry("BigLinearFn", "bign_dgrad", rows, "_det_ws_floats"))(rows, N, K), x.device)
+                _token_call("BigLinearFn", "bign_dgrad", rows, "_det", ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel())
             else:
-                check(getattr(lib(), f"ast_bign_dgrad{sfx}")(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, stream()), f"ast_bign_dgrad{sfx}")
+                _token_call("BigLinearFn", "bign_dgrad", rows, "", ptr(dy), ptr(w), ptr(dx), rows, N, K, N)
         return dx, None, None
 
 
@@ -618,10 +609,10 @@ class FFNFn(torch.autograd.Function):
             _DropState.calls += 1
             seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
             mask = torch.empty_like(h)
-        _skinny_gemm_ex(rows, ptr(x), pw1.weight.data_ptr() + 4 * pw1.w_off, pw1.bias.data_ptr() + 4 * pw1.b_off, ptr(h),
-                        pw1.Co, pw1.Ci, pw1.s_co, pw1.Cop, 1, None, ptr(mask), float(p), seed, ptr(ctr))
-        _skinny_gemm(rows, ptr(h), pw2.weight.data_ptr() + 4 * pw2.w_off, pw2.bias.data_ptr() + 4 * pw2.b_off, ptr(y),
-                     pw2.Co, pw2.Ci, pw2.s_co, pw2.Cop, 0)
+        _token_call("FFNFn", "skinny_gemm", rows, "_ex", ptr(x), pw1.weight.data_ptr() + 4 * pw1.w_off, pw1.bias.data_ptr() + 4 * pw1.b_off, ptr(h),
+                                                 rows, pw1.Co, pw1.Ci, pw1.s_co, pw1.Cop, 1, None, ptr(mask), float(p), seed, ptr(ctr))
+        _token_call("FFNFn", "skinny_gemm", rows, "", ptr(h), pw2.weight.data_ptr() + 4 * pw2.w_off, pw2.bias.data_ptr() + 4 * pw2.b_off, ptr(y),
+                                          rows, pw2.Co, pw2.Ci, pw2.s_co, pw2.Cop, 0)
         ctx.save_for_backward(x, h, mask)
         ctx.pw1, ctx.pw2 = pw1, pw2
         return y
@@ -635,17 +626,18 @@ class FFNFn(torch.autograd.Function):
         pw2.bank.defer_linear_wgrad(pw2, dy, h)
         dh = torch.empty_like(h)
         if mask is None:                       # eval-mode autograd: ReLU mask only
-            _skinny_gemm(rows, ptr(dy), ptr(pw2.wb), None, ptr(dh), pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0)
+            _token_call("FFNFn", "skinny_gemm", rows, "", ptr(dy), ptr(pw2.wb), None, ptr(dh), rows, pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0)
             dz = torch.empty_like(dh)
             check(lib().ast_relu_bwd(ptr(dh), ptr(h), ptr(dz), dh.numel(), dcode(dh.dtype), stream()), "ast_relu_bwd")
             dh = dz
         else:
-            _skinny_gemm_ex(rows, ptr(dy), ptr(pw2.wb), None, ptr(dh), pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0, ptr(mask), None, 0.0, 0, None)
+            _token_call("FFNFn", "skinny_gemm", rows, "_ex", ptr(dy), ptr(pw2.wb), None, ptr(dh), rows, pw2.Ci, pw2.Cop, pw2.Cop, pw2.Cip, 0, ptr(mask), None,
+                                                     0.0, 0, None)
         pw1.bank.defer_linear_wgrad(pw1, dh, x)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _skinny_gemm(rows, ptr(dh), ptr(pw1.wb), None, ptr(dx), pw1.Ci, pw1.Cop, pw1.Cop, pw1.Cip, 0)
+            _token_call("FFNFn", "skinny_gemm", rows, "", ptr(dh), ptr(pw1.wb), None, ptr(dx), rows, pw1.Ci, pw1.Cop, pw1.Cop, pw1.Cip, 0)
         return dx, None, None, None, None, None
 
 

@@ -450,7 +450,8 @@ int ast_weight_grads_flush_det(const ast_weight_desc_t* descs, const void* tiles
  * The entries above stop at 64 rows (one 16-row tile per workgroup, sized for B*(S+1) <= 40).  These take M in
  * 65 .. AST_WIDE_MAX_ROWS and refuse anything else; a workgroup covers 64 rows (four 16-row v_mfma_f32_16x16x4_f32 accumulator
  * tiles per wave), so a weight byte is fetched once per 64 rows.  Arguments, epilogues, alignment and K / ldw rules are those of
- * the <= 64-row twin named in each line.  Only ast_bigk_gemm_wide and ast_bign_dgrad_wide (default mode) add with f32 atomics.
+ * the <= 64-row entry named in each line, which runs the same kernel template with one row tile per wave (csrc/skinny.hip); only the
+ * wide entries check ldw >= K, ldy >= N and lddy >= N.  Only ast_bigk_gemm_wide and ast_bign_dgrad_wide (default mode) add with f32 atomics.
  * ast_skinny_gemm_wide[_ex]: every token linear of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
  *   new_decoder.py:49-51,111-119) and embedding_to_stft forward (SimpleDecoder_TransformerOnly.py:17,62-66) at a larger batch.
  *   The dropout mask of element (m, n) depends on (seed, counter, m * ldy + n) only, as in ast_skinny_gemm_ex.
