@@ -144,6 +144,10 @@ _SIGS = {
     "ast_bign_dgrad_wide_det": ([vp, vp, vp, i32, i32, i32, i32, vp, C.c_long, vp], i32),
     "ast_tok_max_ops": ([], i32),
     "ast_tok_program": ([vp, i32, i32, i32, vp, vp, vp, vp], i32),
+    # ragged inference batches: per-clip lengths read from the device (include/ast_hip.h)
+    "ast_attn_fwd_len": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
+    "ast_sections_overlap_avg_len": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp], i32),
+    "ast_istft_len": ([vp, i32, i32, vp, vp, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

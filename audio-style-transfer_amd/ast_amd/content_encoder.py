@@ -33,8 +33,12 @@ class ContentEncoder(nn.Module):
         self._inp = bank.add(self.input_proj.weight, "linear", L.tok_dtype, bias=self.input_proj.bias) if self.input_proj else None
         self._layers = [L.EncoderLayer(bank, l) for l in self.transformer.layers]
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths: torch.Tensor = None) -> torch.Tensor:
+        """lengths: None, or an int32 (B,) device tensor for a zero-padded batch at inference -- clip b holds lengths[b] real
+        sections, and its transformer attends to those only.  Rows s >= lengths[b] of the result are finite and unspecified."""
         B, S, C, T, F = x.shape
+        if lengths is not None and self.training:
+            raise ValueError("per-clip lengths are an inference feature: call .eval() first (training takes equal-length batches)")
         bank = _module_bank(self)
         bank.prepare(self.training)
         feat = run_resnet(self.cnn, ops.cached_nhwc(x, L.img_dtype()), self.training)
@@ -42,7 +46,10 @@ class ContentEncoder(nn.Module):
         if self._inp is not None:
             feat = L.linear(feat, self._inp)
         seq = L.layer_norm(self.pos_encoder(feat.view(B, S, -1)), self.norm)
-        if config.tok_programs > 0 and tokprog.encoder_stack_ok(seq, self._layers):
+        if lengths is not None:                       # the token programs have no key mask: per-operator layers
+            for lyr in self._layers:
+                seq = lyr(seq, self.training, lengths)
+        elif config.tok_programs > 0 and tokprog.encoder_stack_ok(seq, self._layers):
             seq = tokprog.encoder_stack(seq, self._layers, self.training, xcd=1)
         else:
             for lyr in self._layers:

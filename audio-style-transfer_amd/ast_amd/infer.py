@@ -4,7 +4,11 @@
              -> sections2spectrogram (overlap-average) -> inverse_STFT -> waveforms (B, 256*(T-1))
 
 for a batch of clips, replayed as ONE hipGraph per input shape (the eager form is ~300 small launches per batch and
-launch-bound).  Class embeddings are an input, as in the reference (a per-class table built beforehand)."""
+launch-bound).  Class embeddings are an input, as in the reference (a per-class table built beforehand).
+
+Clips of different lengths go through one graph too: pad them to the longest (utilityFunctions.pad_sections) and pass
+`n_sections`.  The per-clip counts stay on the device and are read by the kernels, so one graph per (B, S_max) serves
+every mix of lengths ("Ragged inference batches")."""
 from __future__ import annotations
 
 import torch
@@ -26,9 +30,26 @@ class StyleTransferSession:
             spec = U.sections2spectrogram_batch(out, frames, self.overlap)
             return U.inverse_STFT_batch(spec), out
 
-    def __call__(self, sections: torch.Tensor, class_emb: torch.Tensor, original_frames: int = None):
-        """sections (B,S,2,287,597) f32, class_emb (B,d) f32 on the device -> (waveforms (B, 256*(T-1)), stft sections)."""
+    def _run_ragged(self, sections, class_emb, frames, n_sections, n_frames):
+        """frames: the batch's frame count (int, from S_max); n_sections, n_frames: int32 (B,) on the device."""
+        with torch.no_grad():
+            content_emb = self.content(sections, n_sections)
+            out = self.decoder(content_emb, class_emb, target_length=content_emb.size(1), lengths=n_sections)
+            nf = n_frames.clamp(2, frames)              # what the two kernels clamp to, so `lengths` says what they wrote
+            spec = U.sections2spectrogram_batch(out, frames, self.overlap, n_sections=n_sections, n_frames=nf)
+            return U.inverse_STFT_batch(spec, nf), out, (nf - 1) * 256
+
+    def __call__(self, sections: torch.Tensor, class_emb: torch.Tensor, original_frames=None, n_sections: torch.Tensor = None):
+        """sections (B,S,2,287,597) f32, class_emb (B,d) f32 on the device -> (waveforms (B, 256*(T-1)), stft sections).
+
+        n_sections (int32 (B,) device tensor): the batch is zero-padded to S sections and clip b holds n_sections[b] of them.
+        original_frames may then be an int32 (B,) device tensor as well (default per clip: the frames its sections cover,
+        191 * (n_b - 1) + 287, formed on the device).  Returns (waveforms, stft sections, lengths): lengths[b] =
+        256 * (frames_b - 1) samples of waveforms[b] are clip b, the rest of the row is 0; output sections s >= n_b are
+        finite and unspecified.  No length is read on the host: every mix of lengths at one (B, S) replays the same graph."""
         B, S, _, wind, _ = sections.shape
+        if n_sections is not None:
+            return self._call_ragged(sections, class_emb, original_frames, n_sections)
         frames = original_frames or (wind - self.overlap) * (S - 1) + wind
         if not self.use_graph:
             return self._run(sections, class_emb, frames)
@@ -51,5 +72,35 @@ class StyleTransferSession:
             s_sec.copy_(sections)
         if s_cls.data_ptr() != class_emb.data_ptr():
             s_cls.copy_(class_emb)
+        g.replay()
+        return outs
+
+    def _call_ragged(self, sections, class_emb, original_frames, n_sections):
+        B, S, _, wind, _ = sections.shape
+        frames = (wind - self.overlap) * (S - 1) + wind
+        for name, t in (("n_sections", n_sections), ("original_frames", original_frames)):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (B,) and t.is_cuda):
+                raise ValueError(f"with n_sections, {name} must be an int32 device tensor of shape ({B},)")
+        n_frames = U.default_frames(n_sections, wind, self.overlap) if original_frames is None else original_frames
+        if not self.use_graph:
+            return self._run_ragged(sections, class_emb, frames, n_sections, n_frames)
+        key = (tuple(sections.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged")
+        if key not in self._graphs:
+            s_sec, s_cls, s_n, s_f = sections.clone(), class_emb.clone(), n_sections.clone(), n_frames.clone()
+            side = torch.cuda.Stream(device=sections.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self._run_ragged(s_sec, s_cls, frames, s_n, s_f)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                outs = self._run_ragged(s_sec, s_cls, frames, s_n, s_f)
+            self._graphs[key] = (g, s_sec, s_cls, s_n, s_f, outs)
+        g, *static, outs = self._graphs[key]
+        for dst, src in zip(static, (sections, class_emb, n_sections, n_frames)):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src)
         g.replay()
         return outs

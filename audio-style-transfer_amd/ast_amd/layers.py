@@ -507,8 +507,9 @@ class MHA:
             self.qkv = bank.add(m.in_proj_weight, "linear", tok_dtype, bias=m.in_proj_bias)
         self.out = bank.add(m.out_proj.weight, "linear", tok_dtype, bias=m.out_proj.bias)
 
-    def __call__(self, x, mem, training, p_drop, causal=False):
-        """x: (B,Lq,d), mem: (B,Lk,d) or None for self-attention."""
+    def __call__(self, x, mem, training, p_drop, causal=False, key_mask=None):
+        """x: (B,Lq,d), mem: (B,Lk,d) or None for self-attention.  key_mask: None or (key_len int32 (B,), key_period): key j of
+        batch b counts iff (j % key_period) < key_len[b] (inference only, ops.AttnCoreFn)."""
         B, Lq, d = x.shape
         dh = d // self.h
         if self.cross:
@@ -520,7 +521,10 @@ class MHA:
             Lk = Lq
             q = kv = linear(x.reshape(B * Lq, d), self.qkv)
             k_off, v_off = d, 2 * d
-        o = ops.AttnCoreFn.apply(q, kv, B, self.h, Lq, Lk, dh, k_off, v_off, causal, float(p_drop) if training else 0.0)
+        if key_mask is not None:
+            ops.require_inference(q, kv)
+        o = ops.AttnCoreFn.apply(q, kv, B, self.h, Lq, Lk, dh, k_off, v_off, causal, float(p_drop) if training else 0.0,
+                                 *(key_mask or ()))
         return linear(o, self.out).view(B, Lq, d)
 
 
@@ -533,15 +537,18 @@ class EncoderLayer:
         self.ff1 = bank.add(layer.linear1.weight, "linear", tok_dtype, bias=layer.linear1.bias)
         self.ff2 = bank.add(layer.linear2.weight, "linear", tok_dtype, bias=layer.linear2.bias)
 
-    def __call__(self, x, training):
+    def __call__(self, x, training, lengths=None):
+        """lengths: None, or int32 (B,) -- row b attends to its first lengths[b] tokens only (a padded batch at inference)."""
         l, p = self.l, self.l.dropout.p
         B, L, d = x.shape
+        km = None if lengths is None else (lengths, L)
         if not config.fused_tokens:
-            x = layer_norm(x + ops.dropout(self.attn(x, None, training, l.self_attn.dropout), l.dropout1.p, training), l.norm1)
+            x = layer_norm(x + ops.dropout(self.attn(x, None, training, l.self_attn.dropout, key_mask=km), l.dropout1.p, training),
+                           l.norm1)
             h = ops.dropout(linear(x.reshape(B * L, d), self.ff1, relu=True), p, training)
             h = ops.dropout(linear(h, self.ff2), l.dropout2.p, training).view(B, L, d)
             return layer_norm(x + h, l.norm2)
-        _, x = ops.add_drop_ln(x, self.attn(x, None, training, l.self_attn.dropout), l.norm1, l.dropout1.p, training)
+        _, x = ops.add_drop_ln(x, self.attn(x, None, training, l.self_attn.dropout, key_mask=km), l.norm1, l.dropout1.p, training)
         h = ops.ffn(x.reshape(B * L, d), self.ff1, self.ff2, p, training)
         _, y = ops.add_drop_ln(x, h.view(B, L, d), l.norm2, l.dropout2.p, training)
         return y
@@ -557,21 +564,24 @@ class DecoderLayer:
         self.ff1 = bank.add(layer.linear1.weight, "linear", tok_dtype, bias=layer.linear1.bias)
         self.ff2 = bank.add(layer.linear2.weight, "linear", tok_dtype, bias=layer.linear2.bias)
 
-    def __call__(self, x, memory, training):
+    def __call__(self, x, memory, training, lengths=None):
+        """lengths: None, or int32 (B,) -- the memory is [content x Sc | class x Sc] (new_decoder._memory) and row b attends to
+        the first lengths[b] tokens of each half.  The causal self-attention needs no mask."""
         l = self.l
         B, L, d = x.shape
+        km = None if lengths is None else (lengths, memory.shape[1] // 2)
         if not config.fused_tokens:
             h = layer_norm(x, l.norm1)
             x = x + ops.dropout(self.sa(h, None, training, l.self_attn.dropout, causal=True), l.dropout1.p, training)
             h = layer_norm(x, l.norm2)
-            x = x + ops.dropout(self.ca(h, memory, training, l.multihead_attn.dropout), l.dropout2.p, training)
+            x = x + ops.dropout(self.ca(h, memory, training, l.multihead_attn.dropout, key_mask=km), l.dropout2.p, training)
             h = layer_norm(x, l.norm3)
             h = ops.dropout(linear(h.reshape(B * L, d), self.ff1, relu=True), l.dropout.p, training)
             h = ops.dropout(linear(h, self.ff2), l.dropout3.p, training).view(B, L, d)
             return x + h
         h = layer_norm(x, l.norm1)
         x, h = ops.add_drop_ln(x, self.sa(h, None, training, l.self_attn.dropout, causal=True), l.norm2, l.dropout1.p, training)
-        x, h = ops.add_drop_ln(x, self.ca(h, memory, training, l.multihead_attn.dropout), l.norm3, l.dropout2.p, training)
+        x, h = ops.add_drop_ln(x, self.ca(h, memory, training, l.multihead_attn.dropout, key_mask=km), l.norm3, l.dropout2.p, training)
         h = ops.ffn(h.reshape(B * L, d), self.ff1, self.ff2, l.dropout.p, training)
         x, _ = ops.add_drop_ln(x, h.view(B, L, d), None, l.dropout3.p, training)
         return x
@@ -582,10 +592,11 @@ class DecoderLayer:
         B, Lm, d = memory.shape
         return linear(memory.reshape(B * Lm, d), self.ca.kv), Lm
 
-    def step(self, x_t, kv_self, mem_kv):
+    def step(self, x_t, kv_self, mem_kv, lengths=None):
         """One new token x_t (B,1,d) through the layer.  kv_self: cached (B, t, 2d) K|V of the earlier tokens of THIS layer (or
         None); returns (y_t, kv_self grown by one).  Causality makes the earlier tokens' K/V independent of later ones, so
-        this equals row t of the full-sequence layer (new_decoder.py:294-314 recomputes all rows every step)."""
+        this equals row t of the full-sequence layer (new_decoder.py:294-314 recomputes all rows every step).  lengths: as in
+        __call__ (masks both halves of the memory)."""
         l = self.l
         B, _, d = x_t.shape
         dh = d // self.sa.h
@@ -599,7 +610,10 @@ class DecoderLayer:
         x = x_t.reshape(B, d) + linear(o, self.sa.out)
         h = layer_norm(x, l.norm2)
         kvm, Lm = mem_kv
-        o = ops.AttnCoreFn.apply(linear(h, self.ca.q), kvm, B, self.ca.h, 1, Lm, dh, 0, d, False, 0.0)
+        qm = linear(h, self.ca.q)
+        if lengths is not None:
+            ops.require_inference(qm, kvm)
+        o = ops.AttnCoreFn.apply(qm, kvm, B, self.ca.h, 1, Lm, dh, 0, d, False, 0.0, *(() if lengths is None else (lengths, Lm // 2)))
         x = x + linear(o, self.ca.out)
         h = layer_norm(x, l.norm3)
         x = x + linear(linear(h, self.ff1, relu=True), self.ff2)

@@ -124,12 +124,18 @@ class Decoder(nn.Module):
         km = L.linear(class_emb, self._kp).unsqueeze(1).expand(-1, Sc, -1)
         return ops.dropout(torch.cat([cm, km], dim=1), self.dropout.p, self.training)
 
-    def prepare_memory(self, content_emb, class_emb):
-        """new_decoder.py:208-229."""
+    def prepare_memory(self, content_emb, class_emb, lengths=None):
+        """new_decoder.py:208-229.  With per-clip lengths (int32 (B,), inference) the memory keeps its padded shape
+        (B, 2 Sc, d): pass the same lengths to forward_inference, whose cross-attention skips the padded tokens of both halves."""
+        self._check_lengths(lengths, content_emb.shape[0])
         self._prepare()
         return self._memory(content_emb, class_emb)
 
-    def _stack(self, tgt, memory):
+    def _stack(self, tgt, memory, lengths=None):
+        if lengths is not None:                       # the token programs have no key mask: per-operator layers
+            for lyr in self._layers:
+                tgt = lyr(tgt, memory, self.training, lengths)
+            return tgt
         if config.tok_programs > 0 and tokprog.decoder_stack_ok(tgt, memory, self._layers):
             return tokprog.decoder_stack(tgt, memory, self._layers, self.training)
         for lyr in self._layers:
@@ -162,7 +168,7 @@ class Decoder(nn.Module):
     # K/V (identical results: the layers are causal).  Class attribute so callers and tests can switch it.
     decode_mode = "recompute"
 
-    def _inference_pass_cached(self, memory, target_length):
+    def _inference_pass_cached(self, memory, target_length, lengths=None):
         B, d = memory.size(0), self.d_model
         mem_kv = [lyr.memory_kv(memory) for lyr in self._layers]
         caches = [None] * len(self._layers)
@@ -172,34 +178,47 @@ class Decoder(nn.Module):
         for t in range(target_length):
             x = tok + pe[:, t:t + 1]
             for i, lyr in enumerate(self._layers):
-                x, caches[i] = lyr.step(x, caches[i], mem_kv[i])
+                x, caches[i] = lyr.step(x, caches[i], mem_kv[i]) if lengths is None else lyr.step(x, caches[i], mem_kv[i], lengths)
             outs.append(x)
             tok = x
         return self._generate(torch.cat(outs, dim=1))
 
-    def _inference_pass(self, memory, target_length=None):
+    def _check_lengths(self, lengths, B):
+        if lengths is None:
+            return
+        if self.training:
+            raise ValueError("per-clip lengths are an inference feature: call .eval() first (training takes equal-length batches)")
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must be an int32 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+
+    def _inference_pass(self, memory, target_length=None, lengths=None):
         B = memory.size(0)
+        self._check_lengths(lengths, B)
         if target_length is None:
             target_length = memory.size(1) // 2
         if target_length > self.pos_encoding.pe.size(1):
             raise ValueError(f"target_length {target_length}, but the positional table holds {self.pos_encoding.pe.size(1)} positions")
         if self.decode_mode == "kv_cache" and not torch.is_grad_enabled():
-            return self._inference_pass_cached(memory, target_length)
+            return self._inference_pass_cached(memory, target_length, lengths)
         seq = self.start_token.expand(B, -1, -1)
         outs = []
         for _ in range(target_length):
-            nxt = self._stack(self.pos_encoding(seq), memory)[:, -1:, :]      # no input_norm here (new_decoder.py:296)
+            nxt = self._stack(self.pos_encoding(seq), memory, lengths)[:, -1:, :]      # no input_norm here (new_decoder.py:296)
             outs.append(nxt)
             seq = torch.cat([seq, nxt], dim=1)
         return self._generate(torch.cat(outs, dim=1))
 
-    def forward_inference(self, memory, target_length=None):
-        """new_decoder.py:272-319."""
+    def forward_inference(self, memory, target_length=None, lengths=None):
+        """new_decoder.py:272-319.  lengths: see forward."""
         self._prepare()
-        return self._inference_pass(memory, target_length)
+        return self._inference_pass(memory, target_length, lengths)
 
-    def forward(self, content_emb, class_emb, y=None, target_length=None, y_embeddings=None):
-        """new_decoder.py:321-345 (+ optional precomputed encode_target(y))."""
+    def forward(self, content_emb, class_emb, y=None, target_length=None, y_embeddings=None, lengths=None):
+        """new_decoder.py:321-345 (+ optional precomputed encode_target(y)).
+        lengths: None, or an int32 (B,) device tensor for a padded batch at inference (eval mode, torch.no_grad()): clip b
+        holds lengths[b] real sections, and its cross-attention sees content and class tokens s < lengths[b] only.  Output
+        sections s >= lengths[b] are finite and unspecified."""
+        self._check_lengths(lengths, content_emb.shape[0])
         if y_embeddings is None or not (self.training and y is not None):
             self._prepare()
         memory = self._memory(content_emb, class_emb)
@@ -207,7 +226,7 @@ class Decoder(nn.Module):
             if len(y.shape) != 5:
                 raise ValueError(f"Expected y to have shape [B, S, 2, 287, 513], got {y.shape}")
             return self._training_pass(y, memory, y_embeddings)
-        return self._inference_pass(memory, target_length)
+        return self._inference_pass(memory, target_length, lengths)
 
 
 def compute_comprehensive_loss(output, target, lambda_temporal=0.3, lambda_phase=0.2, lambda_spectral=0.1):

@@ -1224,14 +1224,27 @@ class CastFn(torch.autograd.Function):
 class AttnCoreFn(torch.autograd.Function):
     """softmax(QK^T/sqrt(dh) + causal) V for up to ATTN_MAX_L query and key tokens (one wave per (batch, head) up to 16 x 16,
     tiles of 16 queries x 16 keys on f32 MFMA past that; no float atomics either way).  q:(B*Lq, ldq) k,v views of (B*Lk, ldk).
-    p_drop > 0: the attention-probability dropout is drawn inside the kernels (same values forward and backward)."""
+    p_drop > 0: the attention-probability dropout is drawn inside the kernels (same values forward and backward).
+    key_len (int32 (B,) device tensor) with key_period: key j of batch b counts iff (j % key_period) < key_len[b]
+    (ast_attn_fwd_len).  Inference only: no dropout and no backward exist for it; p_drop > 0 raises here, an input that
+    requires grad (with grad enabled) raises in require_inference, which the callers that pass a mask call first."""
 
     @staticmethod
-    def forward(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop):
+    def forward(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop, key_len=None, key_period=0):
         d = H * dh
         o = torch.empty((B * Lq, d), dtype=torch.float32, device=q.device)
         probs = torch.empty((B, H, Lq, Lk), dtype=torch.float32, device=q.device)
         ldq, ldk = q.stride(0), kv.stride(0)
+        if key_len is not None:
+            if p_drop > 0.0:
+                raise RuntimeError("the key-masked attention core (key_len) has no dropout: p_drop must be 0")
+            if key_len.dtype != torch.int32 or tuple(key_len.shape) != (B,) or not key_len.is_contiguous():
+                raise ValueError(f"key_len must be a contiguous int32 tensor of shape ({B},), got {key_len.dtype} {tuple(key_len.shape)}")
+            check(lib().ast_attn_fwd_len(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
+                                         B, H, Lq, Lk, dh, ldq, ldk, d, int(causal), ptr(key_len), int(key_period), stream()),
+                  "ast_attn_fwd_len")
+            ctx.mark_non_differentiable(o)
+            return o
         seed, ctr = 0, None
         if p_drop > 0.0:
             if _DropState.counter is None or _DropState.counter.device != q.device:
@@ -1258,7 +1271,15 @@ class AttnCoreFn(torch.autograd.Function):
         check(lib().ast_attn_bwd_p(ptr(do), q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(probs),
                                    dq.data_ptr(), dkv.data_ptr() + 4 * k_off, dkv.data_ptr() + 4 * v_off, B, H, Lq, Lk, dh,
                                    q.stride(0), kv.stride(0), d, None, p_drop, seed, ptr(ctr), stream()), "ast_attn_bwd")
-        return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None
+        return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None, None, None
+
+
+def require_inference(*tensors):
+    """The key-masked attention core has no backward: refuse inputs that autograd would track.  AttnCoreFn.forward runs with
+    grad mode off and cannot see the caller's, so the callers that pass a key mask (layers.MHA, DecoderLayer.step) ask here."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("the key-masked attention core (key_len) is inference only: it has no backward; "
+                           "run it under torch.no_grad()")
 
 
 class _DropState:

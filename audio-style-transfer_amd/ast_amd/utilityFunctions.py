@@ -85,14 +85,50 @@ def sections2spectrogram(sections, original_size, overlap=OVERLAP_FRAMES):
     return sections2spectrogram_batch(sections.unsqueeze(0), original_size, overlap)[0]
 
 
-def sections2spectrogram_batch(sections, original_size, overlap=OVERLAP_FRAMES, n_bins=None):
-    """Batched form: (B,S,2,wind,F) -> (B,2,original_size,n_bins or F)."""
+def _len_tensor(t, B, what):
+    if t.dtype != torch.int32 or tuple(t.shape) != (B,):
+        raise ValueError(f"{what} must be an int32 tensor of shape ({B},), got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def default_frames(n_sections, wind=WINDOW_SIZE, overlap=OVERLAP_FRAMES):
+    """Frames that n sections cover, (wind - overlap) * (n - 1) + wind, elementwise on an int32 device tensor (no sync)."""
+    return n_sections * (wind - overlap) + overlap
+
+
+def pad_sections(clips):
+    """Clips of different section counts, a list of (S_i, 2, 287, F) tensors on one device, as one zero-padded batch:
+    -> (sections (B, S_max, 2, 287, F), n_sections int32 (B,)), both on that device."""
+    if not clips:
+        raise ValueError("pad_sections needs at least one clip")
+    tail = tuple(clips[0].shape[1:])
+    if any(c.dim() != 4 or tuple(c.shape[1:]) != tail or c.shape[0] < 1 for c in clips):
+        raise ValueError(f"every clip must be (S_i >= 1, {', '.join(map(str, tail))}), got {[tuple(c.shape) for c in clips]}")
+    n = [int(c.shape[0]) for c in clips]
+    out = clips[0].new_zeros((len(clips), max(n)) + tail)
+    for b, c in enumerate(clips):
+        out[b, :n[b]] = c
+    return out, torch.tensor(n, dtype=torch.int32, device=out.device)
+
+
+def sections2spectrogram_batch(sections, original_size, overlap=OVERLAP_FRAMES, n_bins=None, n_sections=None, n_frames=None):
+    """Batched form: (B,S,2,wind,F) -> (B,2,original_size,n_bins or F).
+    n_sections (int32 (B,) device tensor): a zero-padded batch -- clip b averages its sections k < n_sections[b] only, and its
+    frames t >= n_frames[b] (int32 (B,); default: what its sections cover) come out as 0 (ast_sections_overlap_avg_len)."""
     B, S, _, wind, F = sections.shape
     hop = wind - overlap
     n_bins = F if n_bins is None else n_bins
     out_T = min(int(original_size), hop * (S - 1) + wind)
     sec = sections.float().contiguous()
     out = torch.empty((B, 2, out_T, n_bins), dtype=torch.float32, device=sec.device)
+    if n_sections is None and n_frames is not None:
+        raise ValueError("n_frames needs n_sections")
+    if n_sections is not None:
+        n_sections = _len_tensor(n_sections, B, "n_sections")
+        n_frames = default_frames(n_sections, wind, overlap) if n_frames is None else _len_tensor(n_frames, B, "n_frames")
+        check(lib().ast_sections_overlap_avg_len(ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T, ptr(n_sections), ptr(n_frames),
+                                                 stream()), "ast_sections_overlap_avg_len")
+        return out
     check(lib().ast_sections_overlap_avg(ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T, stream()), "ast_sections_overlap_avg")
     return out
 
@@ -113,12 +149,18 @@ def inverse_STFT(stft_tensor, n_fft=1024, hop_length=256):
     return inverse_STFT_batch(stft_tensor.unsqueeze(0))[0]
 
 
-def inverse_STFT_batch(spec):
-    """(B, 2, T, 513) -> (B, 256*(T-1)) waveforms in one launch pair."""
+def inverse_STFT_batch(spec, n_frames=None):
+    """(B, 2, T, 513) -> (B, 256*(T-1)) waveforms in one launch pair.
+    n_frames (int32 (B,) device tensor): clip b is inverted as a clip of n_frames[b] frames (clamped to [2, T]); its samples
+    from 256 * (n_frames[b] - 1) on are 0 (ast_istft_len)."""
     spec = spec.float().contiguous()
     B, _, T, _ = spec.shape
     frames = torch.empty((B, T, 1024), dtype=torch.float32, device=spec.device)
     wave = torch.empty((B, 256 * (T - 1)), dtype=torch.float32, device=spec.device)
+    if n_frames is not None:
+        check(lib().ast_istft_len(ptr(spec), B, T, ptr(frames), ptr(wave), ptr(_len_tensor(n_frames, B, "n_frames")), stream()),
+              "ast_istft_len")
+        return wave
     check(lib().ast_istft(ptr(spec), B, T, ptr(frames), ptr(wave), stream()), "ast_istft")
     return wave
 

@@ -160,6 +160,9 @@ __device__ __forceinline__ float block_sum(float v, float* red /* >= 17 floats o
 AST_HIDDEN int attn_long_fwd_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
                                     int dh, int ldq, int ldk, int ldo, int causal, const float* drop_mask, float p, uint64_t seed,
                                     const int64_t* d_offset, void* stream);
+AST_HIDDEN int attn_long_fwd_len_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq,
+                                        int Lk, int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len, int key_period,
+                                        void* stream);
 AST_HIDDEN int attn_long_bwd_launch(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
                                     float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
                                     const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream);

@@ -16,6 +16,12 @@
 //   attn_long_dq_kernel    (query tiles)  dq: reads its own rows' dot, then one wave sums over the key tiles in order,
 // so every output element has one owner and a fixed summation order: the path is bit-reproducible as it stands.
 // Rows past Lq / Lk and columns past dh are predicated: loaded as zero, never stored.
+//
+// ast_attn_fwd_len (inference with ragged batches) is FORWARD ONLY: NO dropout and NO backward are built.  It runs the
+// instantiations NS + ATTN_MASK of the forward kernel: key j of batch b counts iff (j % key_period) < key_len[b].  key_len is
+// read from the device and clamped to [1, key_period], so key 0 stays valid, which is all the merge of the four lane groups
+// needs (see there).  Masked K / V rows are treated like the rows past Lk: loaded as zero, scored -inf, probability 0; a key
+// tile with no valid key is skipped.  Same template, same signature: `drop` carries key_len and `seed` carries key_period.
 #include "ast_common.h"
 #include "../../include/ast_hip.h"
 
@@ -31,8 +37,9 @@ __device__ __forceinline__ float g4_max(float v) { v = fmaxf(v, __shfl_xor(v, 16
 
 // 16-row fragment of a (rows, ld) matrix for a contraction over the head dimension: row r0 + (l&15), columns 16 s + 4 g ..
 template <int NS>
-__device__ __forceinline__ void load_frag(f32x4 (&f)[NS], const float* base, int ld, int r0, int nrows, int dh, int i, int g) {
-  const bool rv = r0 + i < nrows;
+__device__ __forceinline__ void load_frag(f32x4 (&f)[NS], const float* base, int ld, int r0, int nrows, int dh, int i, int g,
+                                          bool row_ok = true) {
+  const bool rv = row_ok && r0 + i < nrows;
 #pragma unroll
   for (int s = 0; s < NS; ++s) f[s] = ld4(base + (size_t)(rv ? r0 + i : 0) * ld + 16 * s + 4 * g, rv && 16 * s + 4 * g < dh);
 }
@@ -48,13 +55,14 @@ __device__ __forceinline__ f32x4 dot_tile(const f32x4 (&a)[NS], const f32x4 (&b)
 }
 // acc[t][.] += sum_r X[x0 + 4g + r][16 t + (l&15)] * w[r]  as A operand (X rows) x B operand (w: k-slot g of step r <-> row 4g + r).
 // D: lane (column l&15 of w's tile, rows 16 t + 4 g + r') -> four consecutive head columns of one output row.
+// rows_ok bit r: row x0 + 4g + r may be read (a masked row is loaded as zero).
 template <int NS>
 __device__ __forceinline__ void rows_mma(f32x4 (&acc)[NS], const float* xbase, int ld, int x0, int nrows, int dh, const f32x4& w,
-                                         int i, int g) {
+                                         int i, int g, unsigned rows_ok = 15u) {
   float a[4][NS];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const bool rv = x0 + 4 * g + r < nrows;
+    const bool rv = (rows_ok >> r & 1u) && x0 + 4 * g + r < nrows;
 #pragma unroll
     for (int t = 0; t < NS; ++t) a[r][t] = (rv && 16 * t + i < dh) ? xbase[(size_t)(x0 + 4 * g + r) * ld + 16 * t + i] : 0.f;
   }
@@ -83,14 +91,33 @@ __device__ __forceinline__ Drop make_drop(const float* mask, float p, uint64_t s
 
 // grid (query tiles, B*H).  Pass 1: running maximum and sum of every query row, kept per lane over its own keys and merged
 // across the four lane groups once; pass 2: scores again, probs written, P (after dropout) times V accumulated.
-template <int NS>
+// The key mask of the NS + ATTN_MASK instantiations.  kl = the clamped key_len[b]; tile_live() is uniform over the workgroup
+// (b is), so skipping a tile is a scalar branch.
+constexpr int ATTN_MASK = 8;
+struct KeyMask {
+  int kl, period;
+  __device__ __forceinline__ bool key(int j) const { return j % period < kl; }
+  // does the tile of keys 16 kt .. 16 kt + 15 (< Lk) hold a valid key: its first key, or the start of the next period
+  __device__ __forceinline__ bool tile_live(int kt, int Lk) const {
+    const int a = (16 * kt) % period;
+    return a < kl || 16 * kt + (period - a) < min(16 * kt + 16, Lk);
+  }
+};
+template <int NSM>
 __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                             const float* __restrict__ v, float* __restrict__ o, float* __restrict__ probs,
                                                             int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, int causal,
                                                             const float* __restrict__ drop, float pdrop, uint64_t seed,
                                                             const int64_t* __restrict__ d_offset) {
-  const Drop dr = make_drop(drop, pdrop, seed, d_offset);
+  constexpr int NS = NSM & (ATTN_MASK - 1);
+  constexpr bool MASK = NSM >= ATTN_MASK;
+  const Drop dr = make_drop(MASK ? nullptr : drop, pdrop, seed, d_offset);
   const int b = blockIdx.y / H, h = blockIdx.y % H, q0 = blockIdx.x * 16;
+  KeyMask km = {1, 1};
+  if constexpr (MASK) {
+    km.period = (int)seed;
+    km.kl = min(max(reinterpret_cast<const int32_t*>(drop)[b], 1), km.period);
+  }
   const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
   const float scale = rsqrtf((float)dh);
   const float* qb = q + (size_t)b * Lq * ldq + h * dh;
@@ -106,13 +133,16 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restri
 
   float m = -INFINITY, l = 0.f;
   for (int kt = 0; kt < kt_end; ++kt) {
-    load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g);
+    if constexpr (MASK) { if (!km.tile_live(kt, Lk)) continue; }
+    if constexpr (MASK) load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g, km.key(kt * 16 + i));
+    else load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g);
     f32x4 s = dot_tile<NS>(kf, qf);
     float tm = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = kt * 16 + 4 * g + r;
       if (j >= Lk || (causal && j > qi)) s[r] = -INFINITY;
+      if constexpr (MASK) { if (!km.key(j)) s[r] = -INFINITY; }
       tm = fmaxf(tm, s[r]);
     }
     const float mn = fmaxf(m, tm);
@@ -123,6 +153,8 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restri
     m = mn;
   }
   // key 0 is never masked, so the row maximum is finite (rows past Lq score 0 everywhere)
+  // (MASK too: key_len >= 1.  A lane group that saw no valid key holds m = -inf, l = 0 and adds 0 * exp(-inf - M) = 0: M is
+  // finite, so there is no inf - inf.)
   const float M = g4_max(m);
   const float den = g4_sum(l * __expf(m - M));
 
@@ -133,13 +165,19 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restri
   const bool qv = qi < Lq;
   for (int kt = 0; kt < nkt; ++kt) {
     f32x4 p = {0.f, 0.f, 0.f, 0.f};
-    if (kt < kt_end) {
-      load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g);
+    bool live = kt < kt_end;
+    unsigned vok = 15u;                                                // MASK: bit r = V row 16 kt + 4 g + r may be read
+    if constexpr (MASK) live = live && km.tile_live(kt, Lk);
+    if (live) {
+      if constexpr (MASK) load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g, km.key(kt * 16 + i));
+      else load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g);
       const f32x4 s = dot_tile<NS>(kf, qf);
+      if constexpr (MASK) vok = 0u;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = kt * 16 + 4 * g + r;
         p[r] = (j >= Lk || (causal && j > qi)) ? 0.f : __expf(s[r] - M) / den;
+        if constexpr (MASK) { if (km.key(j)) vok |= 1u << r; else p[r] = 0.f; }
       }
     }
     f32x4 pd = p;
@@ -153,7 +191,8 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restri
         pd[r] = 0.f;
       }
     }
-    if (kt < kt_end) rows_mma<NS>(acc, vb, ldk, kt * 16, Lk, dh, pd, i, g);
+    if constexpr (MASK) { if (live) rows_mma<NS>(acc, vb, ldk, kt * 16, Lk, dh, pd, i, g, vok); }
+    else if (live) rows_mma<NS>(acc, vb, ldk, kt * 16, Lk, dh, pd, i, g);
   }
   store_rows<NS>(acc, o + (size_t)b * Lq * ldo + h * dh, ldo, qi, qv, dh, g);
 }
@@ -311,6 +350,19 @@ int attn_long_fwd_launch(const float* q, const float* k, const float* v, float* 
   const dim3 grid((Lq + 15) / 16, B * H);
   AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_fwd_kernel<NS>, grid, dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H, Lq, Lk, dh,
                                      ldq, ldk, ldo, causal, drop_mask, p, seed, d_offset));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+int attn_long_fwd_len_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk, int dh,
+                             int ldq, int ldk, int ldo, int causal, const int32_t* key_len, int key_period, void* stream) {
+  const void* ptrs[] = {q, k, v, o};
+  if (int rc = attn_long_check("ast_attn_fwd_len", B, H, Lq, Lk, dh, ldq, ldk, ldo, ptrs, 4)) return rc;
+  const dim3 grid((Lq + 15) / 16, B * H);
+  // key_len in the `drop` slot, key_period in the `seed` slot (see attn_long_fwd_kernel)
+  AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_fwd_kernel<NS + ATTN_MASK>, grid, dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H,
+                                     Lq, Lk, dh, ldq, ldk, ldo, causal, reinterpret_cast<const float*>(key_len), 0.f,
+                                     (uint64_t)key_period, (const int64_t*)nullptr));
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -130,6 +130,87 @@ __global__ void istft_ola_kernel(const float* __restrict__ frames, int T, int no
     wave[(size_t)b * nout + i] = env > 1e-11f ? acc / env : acc;
   }
 }
+
+// ---- the same pair for a batch of clips of different lengths (ast_istft_len; evaluation_style_transfer.py:135-159 run on a
+// padded batch): clip b holds Tb = n_frames[b] frames, read from the device and clamped to [2, T], inside rows of T frames.
+// They are kernels of their own, so that the code of the two above does not move; the arithmetic per frame and per sample is
+// the same, in the same order, so a clip comes out as it does alone through ast_istft at T = Tb.
+__device__ __forceinline__ int clip_frames(const int32_t* __restrict__ n_frames, int b, int T) { return min(max(n_frames[b], 2), T); }
+
+// the 5 radix-4 Stockham stages of istft_frames_kernel / stft_sections_kernel on buf[0] (filled, barrier passed); returns the
+// index of the half of buf that holds the result
+__device__ __forceinline__ int fft1024_stages(float2 (&buf)[2][NFFT], int tid) {
+  int cur = 0;
+#pragma unroll
+  for (int p = 1; p < NFFT; p *= 4) {
+    const int k = tid & (p - 1);
+    const int j = ((tid - k) << 2) + k;
+    const float alpha = -(float)k / (2.f * p);
+    float s1, c1, s2, c2, s3, c3;
+    sincospif(alpha, &s1, &c1); sincospif(2.f * alpha, &s2, &c2); sincospif(3.f * alpha, &s3, &c3);
+    const float2 a0 = buf[cur][tid], a1 = buf[cur][tid + 256], a2 = buf[cur][tid + 512], a3 = buf[cur][tid + 768];
+    const float2 u0 = a0;
+    const float2 u1 = make_float2(a1.x * c1 - a1.y * s1, a1.x * s1 + a1.y * c1);
+    const float2 u2 = make_float2(a2.x * c2 - a2.y * s2, a2.x * s2 + a2.y * c2);
+    const float2 u3 = make_float2(a3.x * c3 - a3.y * s3, a3.x * s3 + a3.y * c3);
+    const float2 v0 = make_float2(u0.x + u2.x, u0.y + u2.y), v1 = make_float2(u0.x - u2.x, u0.y - u2.y);
+    const float2 v2 = make_float2(u1.x + u3.x, u1.y + u3.y);
+    const float2 d = make_float2(u1.x - u3.x, u1.y - u3.y);
+    const float2 v3 = make_float2(d.y, -d.x);
+    buf[cur ^ 1][j] = make_float2(v0.x + v2.x, v0.y + v2.y);
+    buf[cur ^ 1][j + p] = make_float2(v1.x + v3.x, v1.y + v3.y);
+    buf[cur ^ 1][j + 2 * p] = make_float2(v0.x - v2.x, v0.y - v2.y);
+    buf[cur ^ 1][j + 3 * p] = make_float2(v1.x - v3.x, v1.y - v3.y);
+    cur ^= 1;
+    __syncthreads();
+  }
+  return cur;
+}
+__global__ __launch_bounds__(256) void istft_frames_len_kernel(const float* __restrict__ spec, int T, float* __restrict__ frames,
+                                                                const int32_t* __restrict__ n_frames) {
+  __shared__ float2 buf[2][NFFT];
+  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  if (t >= clip_frames(n_frames, b, T)) return;        // uniform over the workgroup, ahead of the first barrier
+  const float* re = spec + ((size_t)b * 2 + 0) * T * NBIN + (size_t)t * NBIN;
+  const float* im = spec + ((size_t)b * 2 + 1) * T * NBIN + (size_t)t * NBIN;
+#pragma unroll
+  for (int k4 = 0; k4 < 4; ++k4) {
+    const int k = tid + 256 * k4;
+    float xr, xi;
+    if (k <= NFFT / 2) { xr = re[k]; xi = (k == 0 || k == NFFT / 2) ? 0.f : im[k]; }
+    else { xr = re[NFFT - k]; xi = -im[NFFT - k]; }
+    buf[0][k] = make_float2(xr, -xi);
+  }
+  __syncthreads();
+  const int cur = fft1024_stages(buf, tid);
+  float* fr = frames + ((size_t)b * T + t) * NFFT;
+#pragma unroll
+  for (int k4 = 0; k4 < 4; ++k4) {
+    const int j = tid + 256 * k4;
+    const float hann = 0.5f - 0.5f * cospif(2.f * j / NFFT);
+    fr[j] = buf[cur][j].x * (1.f / NFFT) * hann;
+  }
+}
+// overlap-add and envelope over the frames t < Tb only; samples i >= HOP * (Tb - 1) are written as 0
+__global__ void istft_ola_len_kernel(const float* __restrict__ frames, int T, int nout, float* __restrict__ wave,
+                                     const int32_t* __restrict__ n_frames) {
+  const int b = blockIdx.y, Tb = clip_frames(n_frames, b, T);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nout; i += gridDim.x * blockDim.x) {
+    float acc = 0.f, env = 0.f;
+    if (i < HOP * (Tb - 1)) {
+      const int j = i + NFFT / 2;
+      const int t_hi = min(Tb - 1, j / HOP), t_lo = max(0, (j - NFFT + HOP) / HOP);
+      for (int t = t_lo; t <= t_hi; ++t) {
+        const int o = j - t * HOP;
+        if (o < 0 || o >= NFFT) continue;
+        const float hann = 0.5f - 0.5f * cospif(2.f * o / NFFT);
+        acc += frames[((size_t)b * T + t) * NFFT + o];
+        env += hann * hann;
+      }
+    }
+    wave[(size_t)b * nout + i] = env > 1e-11f ? acc / env : acc;
+  }
+}
 }  // namespace
 
 namespace {
@@ -147,6 +228,38 @@ __global__ __launch_bounds__(256) void overlap_avg_kernel(const float* __restric
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     int cnt = 0;
     const int i_hi = min(S - 1, t / hop), i_lo = max(0, (t - wind + hop) / hop);
+    for (int k = i_lo; k <= i_hi; ++k) {
+      const int tt = t - k * hop;
+      if (tt < 0 || tt >= wind) continue;
+      const float* p = sec + ((((b * S + k) * 2 + c) * wind + tt) * (size_t)F_in) + f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) if (f + q < F_out) acc[q] += p[q];
+      ++cnt;
+    }
+    const float inv = 1.f / (float)max(cnt, 1);
+    float* o = out + ((b * 2 + c) * (size_t)out_T + t) * F_out + f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (f + q < F_out) o[q] = acc[q] * inv;
+  }
+}
+// The same for clips of different section counts in one padded batch (ast_sections_overlap_avg_len): clip b averages its
+// sections k < n_sec[b] only, in the sum and in the count (later sections are never read), and frames t >= n_frames[b] are
+// written as 0.  Both are read from the device and clamped to [1, S] / [1, out_T].  A kernel of its own, so that the code of
+// the one above does not move; same sum order per element, so a clip comes out as it does alone at S = n_sec[b].
+__global__ __launch_bounds__(256) void overlap_avg_len_kernel(const float* __restrict__ sec, float* __restrict__ out, int S, int wind,
+                                                              int hop, int F_in, int F_out, int out_T, size_t total4,
+                                                              const int32_t* __restrict__ n_sec, const int32_t* __restrict__ n_frames) {
+  const int f4n = (F_out + 3) >> 2;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+    const int f = (int)(i % f4n) * 4;
+    size_t r = i / f4n;
+    const int t = (int)(r % out_T); r /= out_T;
+    const int c = (int)(r % 2);
+    const size_t b = r / 2;
+    const int Sb = min(max(n_sec[b], 1), S), Tb = min(max(n_frames[b], 1), out_T);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int cnt = 0;
+    const int i_hi = t < Tb ? min(Sb - 1, t / hop) : -1, i_lo = max(0, (t - wind + hop) / hop);
     for (int k = i_lo; k <= i_hi; ++k) {
       const int tt = t - k * hop;
       if (tt < 0 || tt >= wind) continue;
@@ -219,6 +332,31 @@ extern "C" int ast_sections_overlap_avg(const float* sections, float* out, int B
   const unsigned grid = (unsigned)std::min<size_t>((total4 + 255) / 256, 4096);
   hipLaunchKernelGGL(overlap_avg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, sections, out, S, wind, hop, F_in, F_out, out_T,
                      total4);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_sections_overlap_avg_len(const float* sections, float* out, int Bc, int S, int wind, int hop, int F_in, int F_out,
+                                            int out_T, const int32_t* n_sec, const int32_t* n_frames, void* stream) {
+  if (!sections || !out || Bc < 1 || S < 1 || wind < 1 || hop < 1 || hop > wind || F_out < 1 || F_out > F_in || out_T < 1 ||
+      out_T > hop * (S - 1) + wind)
+    AST_FAIL("ast_sections_overlap_avg_len: bad args");
+  if (!n_sec || !n_frames) AST_FAIL("ast_sections_overlap_avg_len: n_sec / n_frames is NULL (equal clips: ast_sections_overlap_avg)");
+  const size_t total4 = (size_t)Bc * 2 * out_T * ((F_out + 3) / 4);
+  const unsigned grid = (unsigned)std::min<size_t>((total4 + 255) / 256, 4096);
+  hipLaunchKernelGGL(overlap_avg_len_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, sections, out, S, wind, hop, F_in, F_out,
+                     out_T, total4, n_sec, n_frames);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_istft_len(const float* spec, int Bc, int T, float* frames_ws, float* wave, const int32_t* n_frames, void* stream) {
+  if (!spec || !frames_ws || !wave || Bc <= 0 || T <= 1) AST_FAIL("ast_istft_len: bad args");
+  if (!n_frames) AST_FAIL("ast_istft_len: n_frames is NULL (equal clips: ast_istft)");
+  hipStream_t s = (hipStream_t)stream;
+  const int nout = HOP * (T - 1);
+  hipLaunchKernelGGL(istft_frames_len_kernel, dim3(T, Bc), dim3(256), 0, s, spec, T, frames_ws, n_frames);
+  hipLaunchKernelGGL(istft_ola_len_kernel, dim3((nout + 255) / 256, Bc), dim3(256), 0, s, frames_ws, T, nout, wave, n_frames);
   AST_CHECK_LAUNCH();
   return 0;
 }

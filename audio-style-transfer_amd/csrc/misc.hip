@@ -193,12 +193,21 @@ __global__ void bilinear_bwd_kernel(const float* __restrict__ dy, T* __restrict_
 // ---- attention core for L <= 16 tokens: one wave per (batch, head), lane = feature
 // ML = the compile-time key-count bound (4, 8 or 16): every per-key array is indexed by a fully unrolled loop under a
 // `j < Lk` predicate, so it lives in registers (runtime-indexed arrays went to scratch memory).
+//
+// The instantiations ML + ATTN_MASK are the key-masked forward of ast_attn_fwd_len (inference: no dropout, no backward).  They
+// are the same template, so they keep its signature: with no dropout to describe, `drop` carries key_len, an int32 (B,) device
+// array, and `seed` carries key_period (pdrop = 0, d_offset = null).  Key j of batch b counts iff (j % key_period) < key_len[b],
+// key_len clamped here to [1, key_period] -- key 0 is therefore always valid and every row has a finite maximum.  A masked
+// key is never loaded (its K / V lanes hold zeros, like the lanes past dh), scores -inf and gets probability exactly 0.
 constexpr int MAXL = 16;
-template <int ML>
+constexpr int ATTN_MASK = 32;
+template <int MLM>
 __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                        float* __restrict__ o, float* __restrict__ probs, int H, int Lq, int Lk, int dh,
                                                        int ldq, int ldk, int ldo, int causal, const float* __restrict__ drop,
                                                        float pdrop, uint64_t seed, const int64_t* __restrict__ d_offset) {
+  constexpr int ML = MLM & (ATTN_MASK - 1);
+  constexpr bool MASK = MLM >= ATTN_MASK;
   // attention-probability dropout: either a precomputed mask (`drop`) or, with pdrop > 0, the mask value is DRAWN here
   // from (seed, step counter, element index) -- the backward kernel draws the same values again, so no mask tensor
   // and no mask kernel exist
@@ -207,9 +216,21 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ 
   const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
   const float scale = rsqrtf((float)dh);
   float kv[ML], vv[ML];
+  int period = 1, kl = 1;                                              // MASK only
+  if constexpr (MASK) {
+    period = (int)seed;
+    kl = min(max(reinterpret_cast<const int32_t*>(drop)[b], 1), period);
+    drop = nullptr;
+  }
 #pragma unroll
   for (int j = 0; j < ML; ++j) {
     if (j >= Lk) continue;
+    if constexpr (MASK) {
+      const bool ld = lane < dh && j % period < kl;
+      kv[j] = ld ? k[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+      vv[j] = ld ? v[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+      continue;
+    }
     kv[j] = lane < dh ? k[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
     vv[j] = lane < dh ? v[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
   }
@@ -222,6 +243,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ 
       if (j >= Lk) continue;
       s[j] = wave_sum(qi * kv[j]);
       if (causal && j > i) s[j] = -INFINITY;
+      if constexpr (MASK) { if (j % period >= kl) s[j] = -INFINITY; }  // then exp(-inf - mx) = 0 below: p = 0, and vv[j] = 0
       mx = fmaxf(mx, s[j]);
     }
     float den = 0.f;
@@ -504,6 +526,25 @@ extern "C" int ast_attn_fwd_p(const float* q, const float* k, const float* v, fl
 extern "C" int ast_attn_fwd(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
                             int dh, int ldq, int ldk, int ldo, int causal, const float* drop_mask, void* stream) {
   return ast_attn_fwd_p(q, k, v, o, probs, B, H, Lq, Lk, dh, ldq, ldk, ldo, causal, drop_mask, 0.f, 0, nullptr, stream);
+}
+extern "C" int ast_attn_fwd_len(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                                int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len, int key_period, void* stream) {
+  if (!q || !k || !v || !o || !probs) AST_FAIL("ast_attn_fwd_len: bad args");
+  if (!key_len) AST_FAIL("ast_attn_fwd_len: key_len is NULL (the unmasked core is ast_attn_fwd)");
+  if (Lq < 1 || Lk < 1 || dh < 1 || dh > 64) AST_FAIL("ast_attn_fwd_len: needs 1<=L and 1<=dh<=64 (Lq=%d Lk=%d dh=%d)", Lq, Lk, dh);
+  if (key_period < 1 || key_period > Lk || Lk % key_period != 0)
+    AST_FAIL("ast_attn_fwd_len: needs 1 <= key_period <= Lk and Lk %% key_period == 0 (key_period=%d Lk=%d)", key_period, Lk);
+  if (Lq > MAXL || Lk > MAXL)
+    return attn_long_fwd_len_launch(q, k, v, o, probs, B, H, Lq, Lk, dh, ldq, ldk, ldo, causal, key_len, key_period, stream);
+  // the masked instantiations take key_len in the `drop` slot and key_period in the `seed` slot (see attn_fwd_kernel)
+#define AST_ATTN_FWD(ML_)                                                                                                            \
+  hipLaunchKernelGGL(attn_fwd_kernel<ML_ + ATTN_MASK>, dim3(B * H), dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H, Lq, Lk, dh, \
+                     ldq, ldk, ldo, causal, reinterpret_cast<const float*>(key_len), 0.f, (uint64_t)key_period,                       \
+                     (const int64_t*)nullptr)
+  if (Lk <= 4) AST_ATTN_FWD(4); else if (Lk <= 8) AST_ATTN_FWD(8); else AST_ATTN_FWD(16);
+#undef AST_ATTN_FWD
+  AST_CHECK_LAUNCH();
+  return 0;
 }
 extern "C" int ast_attn_bwd_p(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq, float* dk,
                               float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, const float* drop_mask,

@@ -297,6 +297,20 @@ int ast_attn_bwd(const float* dout, const float* q, const float* k, const float*
 int ast_attn_fwd_p(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
                    int dh, int ldq, int ldk, int ldo, int causal, const float* drop_mask, float p, uint64_t seed,
                    const int64_t* d_offset, void* stream);
+/* Ragged inference batches (evaluation_style_transfer.py:135-159 run on a zero-padded batch of clips of different lengths):
+ * the forward core with a per-batch key mask.  Key j of batch b counts iff (j % key_period) < key_len[b]; key_len is an int32
+ * (B,) DEVICE array, read by the kernel, so a captured graph serves every mix of lengths.  key_period == Lk is a plain
+ * length mask (the content encoder's S section tokens, content_encoder.py:24-26); key_period == Lk / 2 masks both halves of
+ * the decoder's memory [content x S | class x S] (new_decoder.py:208-229).  Checked on the host (error through
+ * ast_last_error): key_len != NULL, 1 <= key_period <= Lk, Lk % key_period == 0, and everything ast_attn_fwd checks.  The
+ * device values cannot be checked without a sync: the kernel clamps key_len[b] to [1, key_period], so every query has a valid
+ * key and no value can produce NaN or an out-of-range access.  Masked keys contribute nothing, their probs entries are
+ * written as 0, and their K / V rows are never read (NaN there does not reach o).  Every query row is computed; rows of
+ * padded queries are finite and unspecified.  Same dispatch as ast_attn_fwd (csrc/misc.hip up to 16 x 16 tokens, csrc/attn.hip
+ * past that, Lq = 1 included).  NOT built: dropout and a backward -- inference only. */
+int ast_attn_fwd_len(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                     int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len /* (B,) device */, int key_period,
+                     void* stream);
 int ast_attn_bwd_p(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq, float* dk,
                    float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, const float* drop_mask,
                    float p, uint64_t seed, const int64_t* d_offset, void* stream);
@@ -370,6 +384,10 @@ int ast_weighted_sum_bwd(const float* g, const int* widx, int n, const float* we
 /* inverse_STFT (utilityFunctions.py:62-82; torch.istft defaults): spec (Bc,2,T,513) f32 -> wave (Bc, 256*(T-1));
  * frames_ws: Bc*T*1024 floats of scratch. */
 int ast_istft(const float* spec, int Bc, int T, float* frames_ws, float* wave, void* stream);
+/* The same for a padded batch (evaluation_style_transfer.py:154-157, one clip per row): clip b is inverted as a clip of
+ * n_frames[b] frames (int32 (Bc,) DEVICE array, clamped to [2, T]): overlap-add and envelope over its frames only, samples
+ * i >= 256 * (n_frames[b] - 1) of its row written as 0.  Rows of spec past n_frames[b] are never read. */
+int ast_istft_len(const float* spec, int Bc, int T, float* frames_ws, float* wave, const int32_t* n_frames, void* stream);
 /* sections2spectrogram (utilityFunctions.py:265-283): sections (Bc,S,2,wind,F_in) -> out (Bc,2,out_T,F_out), the
  * count-normalised overlap-average at step `hop`, bins [0,F_out) only, truncated to out_T <= hop*(S-1)+wind frames. */
 /* Dataset statistics, one clip at a time (Preprocessing_Dataset/compute_unified_stats.py:34-44): per (channel, bin) mean over
@@ -379,6 +397,11 @@ int ast_bin_stats_acc(const float* x, float* mean_acc, float* var_acc, int C, in
 int ast_zscore(const float* x, const float* mean, const float* std_, float* out, int C, int T, int F, float eps, void* stream);
 int ast_sections_overlap_avg(const float* sections, float* out, int Bc, int S, int wind, int hop, int F_in, int F_out,
                              int out_T, void* stream);
+/* The same for a padded batch (evaluation_style_transfer.py:154-155, one clip per row): clip b averages its sections
+ * k < n_sec[b] only, in the sum and in the count (later sections are never read), and frames t >= n_frames[b] of out are
+ * written as 0.  n_sec, n_frames: int32 (Bc,) DEVICE arrays, clamped to [1, S] and [1, out_T]. */
+int ast_sections_overlap_avg_len(const float* sections, float* out, int Bc, int S, int wind, int hop, int F_in, int F_out,
+                                 int out_T, const int32_t* n_sec, const int32_t* n_frames, void* stream);
 int ast_stft_sections(const float* wave, int Bc, int nsamp, const float* mean, const float* std_,
                       float* x, int S, int win, int step, int F_total, void* stream);
 
