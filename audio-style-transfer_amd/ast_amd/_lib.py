@@ -148,6 +148,13 @@ _SIGS = {
     "ast_attn_fwd_len": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
     "ast_sections_overlap_avg_len": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp], i32),
     "ast_istft_len": ([vp, i32, i32, vp, vp, vp, vp], i32),
+    # ragged waveforms: per-clip sample counts read from the device (include/ast_hip.h)
+    "ast_frontend_lengths": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
+    "ast_frontend_lengths_host": ([i32, i32, i32, i32, C.POINTER(i32 * 4)], i32),
+    "ast_stft_sections_len": ([vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp], i32),
+    "ast_decimate2_len": ([vp, i32, i32, vp, i32, i32, vp, i32, f32, vp, i32, i32, i32, i32, vp], i32),
+    "ast_cqt_octaves_len": ([vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp], i32),
+    "ast_cqt_sections_len": ([vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

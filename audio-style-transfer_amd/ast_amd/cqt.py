@@ -111,9 +111,20 @@ def resample_poly(x: torch.Tensor, kern: torch.Tensor, orig: int, new: int, widt
     return y
 
 
-def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256, out=None, bin0=0):
+def _n_samples_arg(n_samples, B, hop_length, window_size, overlap_frames):
+    if not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
+        raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+    if hop_length != 256:
+        raise ValueError("n_samples: the per-clip length arithmetic is built for hop_length=256 (the reference's only configuration)")
+    return n_samples.contiguous(), window_size, window_size - overlap_frames
+
+
+def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256, out=None, bin0=0, n_samples=None, window_size=287,
+              overlap_frames=96):
     """(B, n) f32 cuda -> (B, 2, T, n_bins) f32 (real plane, imaginary plane), T = 1 + n // hop_length.
-    With `out` (B, 2, T, ld) the bins land at out[..., bin0:bin0+n_bins] (e.g. behind the 513 STFT bins)."""
+    With `out` (B, 2, T, ld) the bins land at out[..., bin0:bin0+n_bins] (e.g. behind the 513 STFT bins).
+    n_samples (int32 (B,) device tensor): row b is a zero-padded clip of n_samples[b] samples (clamped on the device to
+    [NS_MIN(window_size), n]); its frames t < 1 + n_samples[b] // 256 are the clip's alone, later ones are unspecified."""
     if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
         raise ValueError("cqt_batch: (B, n) float32 cuda waveforms expected")
     waves = waves.contiguous()
@@ -126,13 +137,26 @@ def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256,
         raise ValueError("cqt_batch: out must be contiguous (B, 2, T, >= bin0 + n_bins)")
     ld = out.shape[3]
     ys, half = [waves], (p["ntaps"] - 1) // 2
-    for _ in range(len(p["octaves"]) - 1):
+    if n_samples is not None:
+        n_samples, win, step = _n_samples_arg(n_samples, B, hop_length, window_size, overlap_frames)
+    for o in range(len(p["octaves"]) - 1):
         # audio.resample(orig_sr=2, target_sr=1, scale=True): ceil(m/2) samples, times sqrt(2)
         m = ys[-1].shape[1]
-        ys.append(resample_poly(ys[-1], p["taps"], 2, 1, half, (m + 1) // 2, math.sqrt(2.0)))
+        if n_samples is None:
+            ys.append(resample_poly(ys[-1], p["taps"], 2, 1, half, (m + 1) // 2, math.sqrt(2.0)))
+            continue
+        y = torch.empty((B, (m + 1) // 2), dtype=torch.float32, device=waves.device)
+        check(lib().ast_decimate2_len(ptr(ys[-1]), B, m, ptr(p["taps"]), p["ntaps"], half, ptr(y), (m + 1) // 2, math.sqrt(2.0),
+                                      ptr(n_samples), n, win, step, o, stream()), "ast_decimate2_len")
+        ys.append(y)
     no = len(ys)
     I = ctypes.c_int * no
     assert all(1 + y.shape[1] // h >= T for y, h in zip(ys, p["hops"]))           # librosa trims every octave to the shortest
+    if n_samples is not None:
+        check(lib().ast_cqt_octaves_len((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*p["hops"]),
+                                        I(*p["los"]), I(*p["nfs"]), I(*p["row0s"]), no, B, ptr(p["w_re"]), ptr(p["w_im"]), ptr(p["scale"]),
+                                        p["nfft"], ptr(out), T, ld, bin0, ptr(n_samples), n, win, step, stream()), "ast_cqt_octaves_len")
+        return out
     check(lib().ast_cqt_octaves((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*p["hops"]), I(*p["los"]),
                                 I(*p["nfs"]), I(*p["row0s"]), no, B, ptr(p["w_re"]), ptr(p["w_im"]), ptr(p["scale"]), p["nfft"], ptr(out), T, ld,
                                 bin0, stream()), "ast_cqt_octaves")
@@ -140,16 +164,23 @@ def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256,
 
 
 def cqt_sections(waves: torch.Tensor, x: torch.Tensor, mean=None, std=None, sample_rate=22050, n_bins=84, hop_length=256,
-                 bin0=513, window_size=287, overlap_frames=96):
+                 bin0=513, window_size=287, overlap_frames=96, n_samples=None):
     """The CQT twin of utilityFunctions.stft_sections: waves (Bc, n) -> CQT -> z-score -> overlap windows, written into
-    x[..., bin0:bin0+n_bins] of the collate-layout batch x (Bc, S, 2, 287, F_total) (dataloader.py:94-121)."""
+    x[..., bin0:bin0+n_bins] of the collate-layout batch x (Bc, S, 2, 287, F_total) (dataloader.py:94-121).
+    n_samples (int32 (Bc,) device tensor): zero-padded clips of n_samples[b] samples; clip b comes out as that clip alone,
+    with 0 in its frames and sections past its own counts (ast_cqt_sections_len)."""
     Bc, S = x.shape[0], x.shape[1]
     if not x.is_contiguous() or x.shape[2] != 2 or x.shape[3] != window_size or x.shape[4] < bin0 + n_bins or waves.shape[0] != Bc:
         raise ValueError("cqt_sections: x must be contiguous (Bc, S, 2, window, >= bin0 + n_bins)")
-    c = cqt_batch(waves, sample_rate, n_bins, hop_length)
+    c = cqt_batch(waves, sample_rate, n_bins, hop_length, n_samples=n_samples, window_size=window_size, overlap_frames=overlap_frames)
     if mean is None:
         mean = torch.zeros(2, n_bins, device=x.device)
         std = torch.ones(2, n_bins, device=x.device) - 1e-8
+    if n_samples is not None:
+        check(lib().ast_cqt_sections_len(ptr(c), Bc, c.shape[2], n_bins, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(x), S,
+                                         window_size, window_size - overlap_frames, x.shape[4], bin0, ptr(n_samples.contiguous()),
+                                         waves.shape[1], stream()), "ast_cqt_sections_len")
+        return x
     check(lib().ast_cqt_sections(ptr(c), Bc, c.shape[2], n_bins, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(x), S, window_size,
                                  window_size - overlap_frames, x.shape[4], bin0, stream()), "ast_cqt_sections")
     return x

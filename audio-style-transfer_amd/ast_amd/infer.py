@@ -8,7 +8,11 @@ launch-bound).  Class embeddings are an input, as in the reference (a per-class 
 
 Clips of different lengths go through one graph too: pad them to the longest (utilityFunctions.pad_sections) and pass
 `n_sections`.  The per-clip counts stay on the device and are read by the kernels, so one graph per (B, S_max) serves
-every mix of lengths ("Ragged inference batches")."""
+every mix of lengths ("Ragged inference batches").
+
+From waveforms, as `process_audio` starts: `waves, n = utilityFunctions.pad_waveforms(clips)`, then
+`session.transfer(waves, class_emb, n_samples=n)` runs front end, models and reconstruction as one graph per (B, n_max); the
+per-clip sample counts stay on the device as well ("Ragged waveforms")."""
 from __future__ import annotations
 
 import torch
@@ -100,6 +104,59 @@ class StyleTransferSession:
             self._graphs[key] = (g, s_sec, s_cls, s_n, s_f, outs)
         g, *static, outs = self._graphs[key]
         for dst, src in zip(static, (sections, class_emb, n_sections, n_frames)):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src)
+        g.replay()
+        return outs
+
+    def _run_wave(self, waves, class_emb, n_samples, frames, stft_stats, cqt_stats):
+        x, n_sections, n_frames = U.frontend_sections(waves, n_samples, stft_stats, cqt_stats)
+        return self._run_ragged(x, class_emb, frames, n_sections, n_frames)
+
+    def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None):
+        """Waveform in, waveform out (evaluation_style_transfer.py:135-159 for a batch): waves (B, n_max) f32 and class_emb
+        (B, d) f32 on the device -> (waveforms (B, 256 * (frames - 1)), stft sections (B, S_max, 2, 287, 513), lengths).
+
+        n_samples (int32 (B,) device tensor, e.g. from utilityFunctions.pad_waveforms): row b of waves is a zero-padded clip of
+        n_samples[b] samples, clamped on the device to [36 608, n_max].  Clip b has T_b = 1 + n_b // 256 frames, the sections
+        the reference cuts from them, and comes back as lengths[b] = 256 * (frames_b - 1) samples, frames_b = min(T_b, what
+        its sections cover); the rest of its row is 0.  `frames` above is that count for a clip of n_max samples.  Without
+        n_samples every clip is n_max long (the same path, the counts filled in on the device).  stft_stats / cqt_stats:
+        (mean, std) of the z-score, (2, 513) / (2, 84), default none.  No length is read on the host: every mix of durations
+        at one (B, n_max) replays the same graph."""
+        if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
+            raise ValueError("transfer: (B, n) float32 cuda waveforms expected")
+        B, n = waves.shape
+        if n_samples is None:
+            n_samples = torch.full((B,), n, dtype=torch.int32, device=waves.device)
+        elif not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
+            raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+        if len(U.section_starts(1 + n // 256)) < 1:
+            raise ValueError(f"transfer: {n} samples give no section")
+        frames = U.clip_lengths(n, n, U.WINDOW_SIZE, self.overlap)[3]
+        stats = tuple(t for pair in (stft_stats, cqt_stats) if pair is not None for t in pair)
+        if not self.use_graph:
+            return self._run_wave(waves, class_emb, n_samples, frames, stft_stats, cqt_stats)
+        key = (tuple(waves.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged", "waves",
+               stft_stats is not None, cqt_stats is not None)
+        if key not in self._graphs:
+            s_wav, s_cls, s_n = waves.clone(), class_emb.clone(), n_samples.clone()
+            s_stats = [t.detach().clone() for t in stats]
+            k = 2 if stft_stats is not None else 0
+            s_stft, s_cqt = (tuple(s_stats[:2]) if stft_stats is not None else None), (tuple(s_stats[k:k + 2]) if cqt_stats is not None else None)
+            side = torch.cuda.Stream(device=waves.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                outs = self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt)
+            self._graphs[key] = (g, [s_wav, s_cls, s_n] + s_stats, outs)
+        g, static, outs = self._graphs[key]
+        for dst, src in zip(static, (waves, class_emb, n_samples) + stats):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         g.replay()

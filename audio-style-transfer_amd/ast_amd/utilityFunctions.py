@@ -20,9 +20,11 @@ def _ident_stats(device):
     return torch.zeros(2, 513, device=device), torch.ones(2, 513, device=device) - 1e-8
 
 
-def stft_sections(waves: torch.Tensor, mean=None, std=None, n_sections=None, F_total=513, out=None):
+def stft_sections(waves: torch.Tensor, mean=None, std=None, n_sections=None, F_total=513, out=None, n_samples=None):
     """waves (Bc, n) f32 cuda -> (Bc, S, 2, 287, F_total): STFT + z-score + windowing in one kernel
-    (utilityFunctions.py:12-37,240-263; dataloader.py:9-13).  Bins >= 513 are left untouched."""
+    (utilityFunctions.py:12-37,240-263; dataloader.py:9-13).  Bins >= 513 are left untouched.
+    n_samples (int32 (Bc,) device tensor): the rows are zero-padded clips of n_samples[b] samples -- clip b is transformed as
+    that clip alone (reflected at its own end), and its sections past its own count are 0 (ast_stft_sections_len)."""
     Bc, n = waves.shape
     T = 1 + n // 256
     step = WINDOW_SIZE - OVERLAP_FRAMES
@@ -32,6 +34,12 @@ def stft_sections(waves: torch.Tensor, mean=None, std=None, n_sections=None, F_t
         mean, std = _ident_stats(waves.device)
     if out is None:
         out = torch.zeros((Bc, n_sections, 2, WINDOW_SIZE, F_total), dtype=torch.float32, device=waves.device)
+    if n_samples is not None:
+        check(lib().ast_stft_sections_len(ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out),
+                                          n_sections, WINDOW_SIZE, step, F_total, ptr(_len_tensor(n_samples, Bc, "n_samples")), stream()),
+              "ast_stft_sections_len")
+        torch.autograd.graph.increment_version(out)
+        return out
     check(lib().ast_stft_sections(ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out),
                                   n_sections, WINDOW_SIZE, step, F_total, stream()), "ast_stft_sections")
     # version bump: the kernel wrote through the raw pointer (keeps version-keyed caches honest).  NOT `out.add_(0)`: that is a
@@ -109,6 +117,64 @@ def pad_sections(clips):
     for b, c in enumerate(clips):
         out[b, :n[b]] = c
     return out, torch.tensor(n, dtype=torch.int32, device=out.device)
+
+
+def pad_waveforms(clips):
+    """Clips of different durations, a list of (n_i,) or (1, n_i) f32 tensors on one device, as one zero-padded batch:
+    -> (waves (B, n_max), n_samples int32 (B,)), both on that device."""
+    if not clips:
+        raise ValueError("pad_waveforms needs at least one clip")
+    flat = [c.reshape(-1) if torch.is_tensor(c) and (c.dim() == 1 or (c.dim() == 2 and c.shape[0] == 1)) else None for c in clips]
+    if any(f is None or f.numel() < 1 or f.dtype != torch.float32 or f.device != flat[0].device for f in flat):
+        raise ValueError("every clip must be a float32 (n_i >= 1,) or (1, n_i) tensor on one device, got "
+                         f"{[(tuple(c.shape), c.dtype, str(c.device)) if torch.is_tensor(c) else type(c).__name__ for c in clips]}")
+    n = [int(f.numel()) for f in flat]
+    out = flat[0].new_zeros((len(flat), max(n)))
+    for b, f in enumerate(flat):
+        out[b, :n[b]] = f
+    return out, torch.tensor(n, dtype=torch.int32, device=out.device)
+
+
+def clip_lengths(ns, nsamp, window_size=WINDOW_SIZE, overlap_frames=OVERLAP_FRAMES):
+    """Host twin of what the front-end kernels compute for a clip of `ns` samples in a row of `nsamp` (csrc/ast_lengths.h, the
+    same function compiled for the host): (ns clamped to [NS_MIN, nsamp], frames T, sections, frames the sections cover)."""
+    import ctypes
+    out = (ctypes.c_int32 * 4)()
+    check(lib().ast_frontend_lengths_host(int(ns), int(nsamp), window_size, window_size - overlap_frames, ctypes.byref(out)),
+          "ast_frontend_lengths_host")
+    return tuple(out)
+
+
+def frontend_lengths(n_samples, nsamp):
+    """n_samples int32 (B,) on the device -> (n_sections, n_frames) int32 (B,) on the device, no sync (ast_frontend_lengths)."""
+    B = n_samples.shape[0]
+    n_samples = _len_tensor(n_samples, B, "n_samples")
+    n_sec, n_fr = torch.empty_like(n_samples), torch.empty_like(n_samples)
+    check(lib().ast_frontend_lengths(ptr(n_samples), B, int(nsamp), WINDOW_SIZE, WINDOW_SIZE - OVERLAP_FRAMES, ptr(n_sec), ptr(n_fr), stream()),
+          "ast_frontend_lengths")
+    return n_sec, n_fr
+
+
+def frontend_sections(waves, n_samples=None, stft_stats=None, cqt_stats=None):
+    """The inference front end of process_audio (evaluation_style_transfer.py:135-146: get_STFT, get_CQT, normalize,
+    concat_stft_cqt, get_overlap_windows) for a batch: waves (B, n_max) f32 on the device -> (x (B, S_max, 2, 287, 597),
+    n_sections, n_frames), S_max = len(section_starts(1 + n_max // 256)).  stft_stats / cqt_stats: (mean, std) of (2, 513) /
+    (2, 84), default none.  n_samples (int32 (B,) device tensor, e.g. from pad_waveforms): row b is a zero-padded clip of
+    n_samples[b] samples and comes out as that clip alone, with 0 in its sections s >= n_sections[b]; the two int32 (B,)
+    results stay on the device.  Without n_samples every clip is n_max long and both are None."""
+    if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
+        raise ValueError("frontend_sections: (B, n) float32 cuda waveforms expected")
+    B, n = waves.shape
+    S = len(section_starts(1 + n // 256))
+    if S < 1:
+        raise ValueError(f"frontend_sections: {n} samples give no section (at least {256 * ((WINDOW_SIZE + 1) // 2 - 1)} needed)")
+    mean, std = stft_stats if stft_stats is not None else (None, None)
+    x = torch.empty((B, S, 2, WINDOW_SIZE, 513 + 84), dtype=torch.float32, device=waves.device)
+    cqt_sections(waves, x, *(cqt_stats if cqt_stats is not None else ()), n_samples=n_samples)
+    stft_sections(waves, mean, std, n_sections=S, F_total=x.shape[-1], out=x, n_samples=n_samples)
+    if n_samples is None:
+        return x, None, None
+    return (x,) + frontend_lengths(n_samples, n)
 
 
 def sections2spectrogram_batch(sections, original_size, overlap=OVERLAP_FRAMES, n_bins=None, n_sections=None, n_frames=None):

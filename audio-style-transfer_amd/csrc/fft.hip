@@ -381,3 +381,87 @@ extern "C" int ast_stft_sections(const float* wave, int Bc, int nsamp, const flo
   AST_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- the STFT front end for a batch of clips of different sample counts (ast_stft_sections_len, ast_frontend_lengths;
+// evaluation_style_transfer.py:135-159 starts from one waveform per clip).  Clip b holds n_samples[b] samples (read from the
+// device, clamped to [ast_ns_min(win), nsamp]) inside a zero-padded row of nsamp: it is reflected at its own end, and its
+// rows t >= T_b and every row of its sections s >= n_sec_b (the dropped tail included) are written as 0.  Kernels of their
+// own, so that the code of stft_sections_kernel does not move; per frame the arithmetic is the same, in the same order, so
+// a clip's sections come out as they do alone through ast_stft_sections at nsamp = n_samples[b].
+#include "ast_lengths.h"
+namespace {
+__global__ __launch_bounds__(256) void stft_sections_len_kernel(const float* __restrict__ wave, int nsamp, const float* __restrict__ mean,
+                                                                 const float* __restrict__ stdv, float* __restrict__ x, int S, int win,
+                                                                 int step, int Ftot, const int32_t* __restrict__ n_samples) {
+  __shared__ float2 buf[2][NFFT];
+  const int row = blockIdx.x, s = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int t = s * step + row;
+  const AstClipLen L = ast_clip_len(n_samples[b], nsamp, win, step);
+  float* xr = x + ((((size_t)b * S + s) * 2 + 0) * win + row) * Ftot;
+  float* xi = x + ((((size_t)b * S + s) * 2 + 1) * win + row) * Ftot;
+  if (t >= L.T || s >= L.n_sec) {      // uniform over the workgroup, ahead of the first barrier
+    for (int f = tid; f < NBIN; f += 256) { xr[f] = 0.f; xi[f] = 0.f; }
+    return;
+  }
+  const int ns = L.ns;
+  const float* w = wave + (size_t)b * nsamp;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = tid + 256 * k;
+    int idx = t * HOP + j - NFFT / 2;
+    if (idx < 0) idx = -idx;
+    if (idx >= ns) idx = 2 * (ns - 1) - idx;           // t < T_b and ns > 512: 0 <= idx < ns
+    const float hann = 0.5f - 0.5f * cospif(2.f * j / NFFT);
+    buf[0][j] = make_float2(w[idx] * hann, 0.f);
+  }
+  __syncthreads();
+  const int cur = fft1024_stages(buf, tid);
+  for (int f = tid; f < NBIN; f += 256) {
+    const float2 z = buf[cur][f];
+    xr[f] = (z.x - mean[f]) / (stdv[f] + 1e-8f);
+    xi[f] = (z.y - mean[NBIN + f]) / (stdv[NBIN + f] + 1e-8f);
+  }
+}
+// n_sections[b], n_frames[b] of every clip: one thread per clip, ordinary stores
+__global__ void frontend_lengths_kernel(const int32_t* __restrict__ n_samples, int Bc, int nsamp, int win, int step,
+                                        int32_t* __restrict__ n_sections, int32_t* __restrict__ n_frames) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= Bc) return;
+  const AstClipLen L = ast_clip_len(n_samples[b], nsamp, win, step);
+  n_sections[b] = L.n_sec;
+  n_frames[b] = L.n_frames;
+}
+}  // namespace
+
+extern "C" int ast_frontend_lengths_host(int ns, int nsamp, int win, int step, int* out4) {
+  if (!out4 || win < 1 || win > AST_FE_MAX_WIN || step < 1 || step > win) AST_FAIL("ast_frontend_lengths_host: bad args (win=%d step=%d)", win, step);
+  if (nsamp < ast_ns_min(win)) AST_FAIL("ast_frontend_lengths_host: nsamp %d needs >= %d samples (one section at win %d)", nsamp, ast_ns_min(win), win);
+  const AstClipLen L = ast_clip_len(ns, nsamp, win, step);
+  out4[0] = L.ns; out4[1] = L.T; out4[2] = L.n_sec; out4[3] = L.n_frames;
+  return 0;
+}
+
+extern "C" int ast_frontend_lengths(const int32_t* n_samples, int Bc, int nsamp, int win, int step, int32_t* n_sections_out,
+                                    int32_t* n_frames_out, void* stream) {
+  if (!n_samples) AST_FAIL("ast_frontend_lengths: n_samples is NULL");
+  if (!n_sections_out || !n_frames_out) AST_FAIL("ast_frontend_lengths: null pointer");
+  if (Bc < 1 || win < 1 || win > AST_FE_MAX_WIN || step < 1 || step > win) AST_FAIL("ast_frontend_lengths: bad shape (Bc=%d win=%d step=%d)", Bc, win, step);
+  if (nsamp < ast_ns_min(win)) AST_FAIL("ast_frontend_lengths: nsamp %d needs >= %d samples (one section at win %d)", nsamp, ast_ns_min(win), win);
+  hipLaunchKernelGGL(frontend_lengths_kernel, dim3((Bc + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_samples, Bc, nsamp, win, step,
+                     n_sections_out, n_frames_out);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_stft_sections_len(const float* wave, int Bc, int nsamp, const float* mean, const float* std_, float* x, int S, int win,
+                                     int step, int F_total, const int32_t* n_samples, void* stream) {
+  if (!wave || !mean || !std_ || !x || Bc <= 0 || Bc > 65535 || nsamp <= NFFT / 2 || S <= 0 || S > 65535 || win <= 0 || win > AST_FE_MAX_WIN ||
+      step <= 0 || step > win || F_total < NBIN)
+    AST_FAIL("ast_stft_sections_len: bad args");
+  if (!n_samples) AST_FAIL("ast_stft_sections_len: n_samples is NULL (equal clips: ast_stft_sections)");
+  if (nsamp < ast_ns_min(win)) AST_FAIL("ast_stft_sections_len: nsamp %d needs >= %d samples (one section at win %d)", nsamp, ast_ns_min(win), win);
+  hipLaunchKernelGGL(stft_sections_len_kernel, dim3(win, S, Bc), dim3(256), 0, (hipStream_t)stream, wave, nsamp, mean, std_, x, S, win, step,
+                     F_total, n_samples);
+  AST_CHECK_LAUNCH();
+  return 0;
+}

@@ -419,6 +419,37 @@ int ast_cqt_octaves(const float* const* ys, const int* ns, const int* hops, cons
  * cqt (Bc,2,T,nb), x (Bc,S,2,win,F_total) f32.  The CQT twin of ast_stft_sections. */
 int ast_cqt_sections(const float* cqt, int Bc, int T, int nb, const float* mean, const float* std_, float* x, int S, int win,
                      int step, int F_total, int bin0, void* stream);
+/* ---- the front end for a padded batch of clips of different sample counts (evaluation_style_transfer.py:135-159 starts from
+ * one waveform per clip).  n_samples: int32 (Bc,) DEVICE array, clip b holds n_samples[b] samples inside a zero-padded row of
+ * nsamp.  The values cannot be checked without a sync, so every kernel clamps them to [NS_MIN, nsamp], NS_MIN =
+ * max(513, 256 * ((win + 1) / 2 - 1)): the smallest count that reflect-pads validly and yields one section (36 608 at win 287);
+ * the host refuses nsamp < NS_MIN.  With ns the clamped count (csrc/ast_lengths.h, one function for host and device):
+ *   T_b = 1 + ns / 256;  n_sec_b = len(section_starts(T_b)) (utilityFunctions.py:246-262) = k + (2 (T_b - k step) >= win),
+ *   k = ceil(max(T_b - win, 0) / step);  n_frames_b = min(T_b, step (n_sec_b - 1) + win), the frames the kept sections cover.
+ * Per output element the _len kernels run the arithmetic of the plain ones on the clip alone, in the same order. */
+/* n_sections_out[b] = n_sec_b, n_frames_out[b] = n_frames_b (int32 (Bc,) device arrays), one small launch */
+int ast_frontend_lengths(const int32_t* n_samples, int Bc, int nsamp, int win, int step, int32_t* n_sections_out,
+                         int32_t* n_frames_out, void* stream);
+/* the same function on the host for one value: out4 = {clamped ns, T_b, n_sec_b, n_frames_b} */
+int ast_frontend_lengths_host(int ns, int nsamp, int win, int step, int* out4);
+/* ast_stft_sections (utilityFunctions.py:12-37,240-263) with clip b transformed as a clip of n_samples[b] samples: reflected
+ * at its own end; rows t >= T_b and every row of sections s >= n_sec_b (the dropped tail included) are written as 0. */
+int ast_stft_sections_len(const float* wave, int Bc, int nsamp, const float* mean, const float* std_, float* x, int S, int win,
+                          int step, int F_total, const int32_t* n_samples, void* stream);
+/* The halving between CQT octaves (librosa audio.resample(2 -> 1); ast_resample_poly with orig = 2, nnew = 1, klen <= 4096) at
+ * level o: x (B, n = ceil(nsamp / 2^o)), and input sample s of clip b counts iff s < ceil(n_samples[b] / 2^o), as the clip
+ * alone ends there.  y (B, m). */
+int ast_decimate2_len(const float* x, int B, int n, const float* h, int klen, int width, float* y, int m, float gain,
+                      const int32_t* n_samples, int nsamp, int win, int step, int o, void* stream);
+/* ast_cqt_octaves (utilityFunctions.py:39-60) where octave o is the o-times-halved signal, ns[o] = ceil(nsamp / 2^o): the span
+ * of octave o reads 0 for s >= ceil(n_samples[b] / 2^o).  Frames t >= T_b are computed and unspecified (ast_cqt_sections_len
+ * drops them). */
+int ast_cqt_octaves_len(const float* const* ys, const int* ns, const int* hops, const int* los, const int* nfs, const int* row0s,
+                        int n_oct, int B, const float* w_re, const float* w_im, const float* scale, int nfft, float* out, int T,
+                        int ld, int bin_off, const int32_t* n_samples, int nsamp, int win, int step, void* stream);
+/* ast_cqt_sections (dataloader.py:9-18, utilityFunctions.py:240-263) with T = 1 + nsamp / 256: 0 for t >= T_b and s >= n_sec_b */
+int ast_cqt_sections_len(const float* cqt, int Bc, int T, int nb, const float* mean, const float* std_, float* x, int S, int win,
+                         int step, int F_total, int bin0, const int32_t* n_samples, int nsamp, void* stream);
 /* Polyphase FIR resampler: y[b][i*nnew + p] = gain * sum_k kern[p][k] * x[b][i*orig + k - width], x = 0 outside [0,n);
  * kern (nnew, klen), y (B, m).  Replaces torchaudio.functional.resample in load_audio (utilityFunctions.py:116-117;
  * kern = its sinc_interp_hann bank) and the halving resample between CQT octaves (orig=2, nnew=1). */

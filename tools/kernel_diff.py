@@ -36,6 +36,8 @@ def symbols(lib):
                 m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
                 if m:
                     body = code.setdefault(m.group(1), [])
+                elif body is not None and line.strip() == "...":
+                    pass        # objdump's mark for zero bytes: alignment padding before the next function, not code
                 elif body is not None and line.startswith("\t"):
                     body.append(re.sub(r"\s*//.*$", "", line).strip())          # the comment holds the address
             for block in re.split(r"\n  - (?=\.)", _run("llvm-readelf", "--notes", path)):
