@@ -111,6 +111,14 @@ def resample_poly(x: torch.Tensor, kern: torch.Tensor, orig: int, new: int, widt
     return y
 
 
+def _len_call(name, args, len_tail=None):
+    """Entry `name` for equal clips, or its twin `name`_len with the length arguments appended when there are any: called on the
+    current stream and checked."""
+    if len_tail is not None:
+        name, args = name + "_len", (*args, *len_tail)
+    check(getattr(lib(), name)(*args, stream()), name)
+
+
 def _n_samples_arg(n_samples, B, hop_length, window_size, overlap_frames):
     if not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
         raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
@@ -137,29 +145,26 @@ def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256,
         raise ValueError("cqt_batch: out must be contiguous (B, 2, T, >= bin0 + n_bins)")
     ld = out.shape[3]
     ys, half = [waves], (p["ntaps"] - 1) // 2
+    tail = None
     if n_samples is not None:
         n_samples, win, step = _n_samples_arg(n_samples, B, hop_length, window_size, overlap_frames)
+        tail = (ptr(n_samples), n, win, step)
     for o in range(len(p["octaves"]) - 1):
         # audio.resample(orig_sr=2, target_sr=1, scale=True): ceil(m/2) samples, times sqrt(2)
         m = ys[-1].shape[1]
-        if n_samples is None:
+        if tail is None:
             ys.append(resample_poly(ys[-1], p["taps"], 2, 1, half, (m + 1) // 2, math.sqrt(2.0)))
             continue
         y = torch.empty((B, (m + 1) // 2), dtype=torch.float32, device=waves.device)
-        check(lib().ast_decimate2_len(ptr(ys[-1]), B, m, ptr(p["taps"]), p["ntaps"], half, ptr(y), (m + 1) // 2, math.sqrt(2.0),
-                                      ptr(n_samples), n, win, step, o, stream()), "ast_decimate2_len")
+        check(lib().ast_decimate2_len(ptr(ys[-1]), B, m, ptr(p["taps"]), p["ntaps"], half, ptr(y), (m + 1) // 2, math.sqrt(2.0), *tail, o,
+                                      stream()), "ast_decimate2_len")
         ys.append(y)
     no = len(ys)
     I = ctypes.c_int * no
     assert all(1 + y.shape[1] // h >= T for y, h in zip(ys, p["hops"]))           # librosa trims every octave to the shortest
-    if n_samples is not None:
-        check(lib().ast_cqt_octaves_len((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*p["hops"]),
-                                        I(*p["los"]), I(*p["nfs"]), I(*p["row0s"]), no, B, ptr(p["w_re"]), ptr(p["w_im"]), ptr(p["scale"]),
-                                        p["nfft"], ptr(out), T, ld, bin0, ptr(n_samples), n, win, step, stream()), "ast_cqt_octaves_len")
-        return out
-    check(lib().ast_cqt_octaves((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*p["hops"]), I(*p["los"]),
-                                I(*p["nfs"]), I(*p["row0s"]), no, B, ptr(p["w_re"]), ptr(p["w_im"]), ptr(p["scale"]), p["nfft"], ptr(out), T, ld,
-                                bin0, stream()), "ast_cqt_octaves")
+    _len_call("ast_cqt_octaves", ((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*p["hops"]), I(*p["los"]),
+                                  I(*p["nfs"]), I(*p["row0s"]), no, B, ptr(p["w_re"]), ptr(p["w_im"]), ptr(p["scale"]), p["nfft"], ptr(out), T,
+                                  ld, bin0), tail)
     return out
 
 
@@ -176,13 +181,9 @@ def cqt_sections(waves: torch.Tensor, x: torch.Tensor, mean=None, std=None, samp
     if mean is None:
         mean = torch.zeros(2, n_bins, device=x.device)
         std = torch.ones(2, n_bins, device=x.device) - 1e-8
-    if n_samples is not None:
-        check(lib().ast_cqt_sections_len(ptr(c), Bc, c.shape[2], n_bins, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(x), S,
-                                         window_size, window_size - overlap_frames, x.shape[4], bin0, ptr(n_samples.contiguous()),
-                                         waves.shape[1], stream()), "ast_cqt_sections_len")
-        return x
-    check(lib().ast_cqt_sections(ptr(c), Bc, c.shape[2], n_bins, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(x), S, window_size,
-                                 window_size - overlap_frames, x.shape[4], bin0, stream()), "ast_cqt_sections")
+    _len_call("ast_cqt_sections", (ptr(c), Bc, c.shape[2], n_bins, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(x), S, window_size,
+                                   window_size - overlap_frames, x.shape[4], bin0),
+              None if n_samples is None else (ptr(n_samples.contiguous()), waves.shape[1]))
     return x
 
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from ._lib import check, lib, ptr, stream
+from .cqt import _len_call
 
 WINDOW_SIZE = 287
 OVERLAP_PERCENTAGE = 0.3
@@ -34,14 +35,9 @@ def stft_sections(waves: torch.Tensor, mean=None, std=None, n_sections=None, F_t
         mean, std = _ident_stats(waves.device)
     if out is None:
         out = torch.zeros((Bc, n_sections, 2, WINDOW_SIZE, F_total), dtype=torch.float32, device=waves.device)
-    if n_samples is not None:
-        check(lib().ast_stft_sections_len(ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out),
-                                          n_sections, WINDOW_SIZE, step, F_total, ptr(_len_tensor(n_samples, Bc, "n_samples")), stream()),
-              "ast_stft_sections_len")
-        torch.autograd.graph.increment_version(out)
-        return out
-    check(lib().ast_stft_sections(ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out),
-                                  n_sections, WINDOW_SIZE, step, F_total, stream()), "ast_stft_sections")
+    _len_call("ast_stft_sections", (ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out), n_sections,
+                                    WINDOW_SIZE, step, F_total),
+              None if n_samples is None else (ptr(_len_tensor(n_samples, Bc, "n_samples")),))
     # version bump: the kernel wrote through the raw pointer (keeps version-keyed caches honest).  NOT `out.add_(0)`: that is a
     # read-modify-write of ALL bins on this stream, and the CQT kernel fills bins >= 513 of the same tensor on another stream
     # (train.Trainer._run_frontend) -- the no-op add wrote stale CQT bins back now and then (found by the mixed-length oracle test)
@@ -189,13 +185,12 @@ def sections2spectrogram_batch(sections, original_size, overlap=OVERLAP_FRAMES, 
     out = torch.empty((B, 2, out_T, n_bins), dtype=torch.float32, device=sec.device)
     if n_sections is None and n_frames is not None:
         raise ValueError("n_frames needs n_sections")
+    tail = None
     if n_sections is not None:
         n_sections = _len_tensor(n_sections, B, "n_sections")
         n_frames = default_frames(n_sections, wind, overlap) if n_frames is None else _len_tensor(n_frames, B, "n_frames")
-        check(lib().ast_sections_overlap_avg_len(ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T, ptr(n_sections), ptr(n_frames),
-                                                 stream()), "ast_sections_overlap_avg_len")
-        return out
-    check(lib().ast_sections_overlap_avg(ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T, stream()), "ast_sections_overlap_avg")
+        tail = (ptr(n_sections), ptr(n_frames))
+    _len_call("ast_sections_overlap_avg", (ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T), tail)
     return out
 
 
@@ -223,11 +218,8 @@ def inverse_STFT_batch(spec, n_frames=None):
     B, _, T, _ = spec.shape
     frames = torch.empty((B, T, 1024), dtype=torch.float32, device=spec.device)
     wave = torch.empty((B, 256 * (T - 1)), dtype=torch.float32, device=spec.device)
-    if n_frames is not None:
-        check(lib().ast_istft_len(ptr(spec), B, T, ptr(frames), ptr(wave), ptr(_len_tensor(n_frames, B, "n_frames")), stream()),
-              "ast_istft_len")
-        return wave
-    check(lib().ast_istft(ptr(spec), B, T, ptr(frames), ptr(wave), stream()), "ast_istft")
+    _len_call("ast_istft", (ptr(spec), B, T, ptr(frames), ptr(wave)),
+              None if n_frames is None else (ptr(_len_tensor(n_frames, B, "n_frames")),))
     return wave
 
 

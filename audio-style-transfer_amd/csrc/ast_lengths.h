@@ -2,7 +2,7 @@
 // ast_cqt_octaves_len, ast_cqt_sections_len): the one place that says how many frames and sections a clip of `ns` samples has.
 // Host and device compile the same function, so the kernels, the host twin ast_frontend_lengths_host and the Python side agree.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "ast_common.h"
 
 #define AST_FE_HOP 256            // the front end's hop (get_STFT / get_CQT, utilityFunctions.py:12-60)
 #define AST_FE_MAX_WIN (1 << 20)  // the host refuses longer windows, so that 256 * (win / 2) stays an int
@@ -38,3 +38,11 @@ __host__ __device__ inline AstClipLen ast_clip_len(int ns_raw, int nsamp, int wi
 
 // samples of the clip after o ceil-halvings (librosa's audio.resample(2 -> 1) between octaves): ceil(ns / 2^o)
 __host__ __device__ inline int ast_halved(int ns, int o) { return (int)(((long long)ns + (1ll << o) - 1) >> o); }
+
+// ---- host: what every entry that takes per-clip lengths checks before ast_clip_len may run on its arguments
+inline bool ast_sectioning_ok(int win, int step) { return win >= 1 && win <= AST_FE_MAX_WIN && step >= 1 && step <= win; }
+// the padded row must hold one section: 0, or -1 with the message of entry `name` set
+inline int ast_row_check(const char* name, int nsamp, int win) {
+  if (nsamp < ast_ns_min(win)) AST_FAIL("%s: nsamp %d needs >= %d samples (one section at win %d)", name, nsamp, ast_ns_min(win), win);
+  return 0;
+}

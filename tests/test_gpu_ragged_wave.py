@@ -132,6 +132,66 @@ def test_full_lengths_equal_the_unmasked_entries():
     assert torch.equal(U.stft_sections(waves, n_samples=full), U.stft_sections(waves))
 
 
+def test_generic_paths_equal_the_unmasked_entries():
+    """The instantiations the two tests above do not reach: the octave kernel without register-held taps (nfft = 64, 13 filters)
+    and the four-outputs-per-thread halving (B * m = 256 Ki).  With full lengths the _len entry equals the plain one, and a
+    short clip's row equals the clip alone at its own length; both to the last bit (same arithmetic in the same order)."""
+    import ctypes
+    import math
+    from ast_amd._lib import check, lib, ptr, stream
+    gen = torch.Generator().manual_seed(33)
+    rn = lambda *shape: torch.randn(*shape, generator=gen).to(DEV)
+    win, step = 7, 5                                                  # NS_MIN(7) = 768
+
+    def octaves(ys, T, n_samples=None, nsamp=None):
+        B, no, nf, nfft = ys[0].shape[0], len(ys), 13, 64
+        out = torch.full((B, 2, T, nf * no), float("nan"), device=DEV)
+        I = ctypes.c_int * no
+        args = ((ctypes.c_void_p * no)(*[y.data_ptr() for y in ys]), I(*[y.shape[1] for y in ys]), I(*[256 >> o for o in range(no)]),
+                I(*[nf * (no - 1 - o) for o in range(no)]), I(*[nf] * no), I(*[0] * no), no, B, ptr(w_re), ptr(w_im), ptr(scale), nfft, ptr(out),
+                T, nf * no, 0)
+        if n_samples is None:
+            check(lib().ast_cqt_octaves(*args, stream()), "ast_cqt_octaves")
+        else:
+            check(lib().ast_cqt_octaves_len(*args, ptr(n_samples), nsamp, win, step, stream()), "ast_cqt_octaves_len")
+        return out
+
+    nsamp, T, halved = 2048, 9, lambda n, o: -(-n // (1 << o))
+    w_re, w_im, scale = rn(13, 64), rn(13, 64), rn(39)
+    ys = [rn(3, halved(nsamp, o)) for o in range(3)]
+    plain = octaves(ys, T)
+    assert bool(torch.isfinite(plain).all())
+    assert torch.equal(octaves(ys, T, i32([nsamp] * 3), nsamp), plain)
+    ns = [nsamp, 1500, 1024]
+    ragged = octaves(ys, T, i32(ns), nsamp)
+    for b in (1, 2):
+        Tb = 1 + ns[b] // 256
+        solo = octaves([y[b:b + 1, :halved(ns[b], o)].contiguous() for o, y in enumerate(ys)], Tb)
+        assert torch.equal(ragged[b, :, :Tb], solo[0]), f"octaves of clip {b}"
+    assert torch.equal(ragged[0], plain[0])
+
+    def halve(x, n_samples=None, nsamp=None):
+        B, n = x.shape
+        y = torch.full((B, (n + 1) // 2), float("nan"), device=DEV)
+        if n_samples is None:
+            check(lib().ast_resample_poly(ptr(x), B, n, ptr(taps), 2, 1, 30, 14, ptr(y), y.shape[1], math.sqrt(2.0), stream()), "ast_resample_poly")
+        else:
+            check(lib().ast_decimate2_len(ptr(x), B, n, ptr(taps), 30, 14, ptr(y), y.shape[1], math.sqrt(2.0), ptr(n_samples), nsamp, win, step,
+                                          0, stream()), "ast_decimate2_len")
+        return y
+
+    nsamp, taps, x = 131072, rn(1, 30), rn(4, 131072)                 # m * B = 65536 * 4: the threshold itself
+    plain = halve(x)
+    assert bool(torch.isfinite(plain).all())
+    assert torch.equal(halve(x, i32([nsamp] * 4), nsamp), plain)
+    ns = [nsamp, 100001, 768, nsamp]
+    ragged = halve(x, i32(ns), nsamp)
+    for b in (1, 2):
+        solo = halve(x[b:b + 1, :ns[b]].contiguous())
+        assert torch.equal(ragged[b, :solo.shape[1]], solo[0]), f"halving of clip {b}"
+    assert torch.equal(ragged[0], plain[0]) and torch.equal(ragged[3], plain[3])
+
+
 # ---- 3. StyleEncoder -----------------------------------------------------------------------------------------------------------------
 def _seeded(tag, ctor):
     m = ctor()
