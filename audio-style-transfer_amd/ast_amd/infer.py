@@ -50,7 +50,8 @@ class StyleTransferSession:
         original_frames may then be an int32 (B,) device tensor as well (default per clip: the frames its sections cover,
         191 * (n_b - 1) + 287, formed on the device).  Returns (waveforms, stft sections, lengths): lengths[b] =
         256 * (frames_b - 1) samples of waveforms[b] are clip b, the rest of the row is 0; output sections s >= n_b are
-        finite and unspecified.  No length is read on the host: every mix of lengths at one (B, S) replays the same graph."""
+        finite and unspecified (exactly 0 with SimpleDecoder_TransformerOnly.Decoder).  No length is read on the host:
+        every mix of lengths at one (B, S) replays the same graph."""
         B, S, _, wind, _ = sections.shape
         if n_sections is not None:
             return self._call_ragged(sections, class_emb, original_frames, n_sections)

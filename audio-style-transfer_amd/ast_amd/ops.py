@@ -590,6 +590,32 @@ class BigLinearFn(torch.autograd.Function):
         return dx, None, None
 
 
+BIGN_MAX_ROWS = 4096            # AST_BIGN_MAX_ROWS: ast_bign_gemm_len takes 1 .. 4096 rows
+
+
+def big_out_linear(x, weight, bias, S, lengths=None):
+    """nn.Linear with a huge out_features on the (B*S, K) f32 rows of a padded batch, at inference (ast_bign_gemm_len): up to
+    BIGN_MAX_ROWS rows; lengths (int32 (B,) device tensor, clamped to [1, S] on the device) -- rows of sections s >= lengths[b]
+    come back as exactly 0 and their inputs are never read.  No backward exists: an input that autograd would track raises."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        raise RuntimeError("the length-masked output linear (big_out_linear) is inference only: it has no backward; "
+                           "run it under torch.no_grad()")
+    x = x.contiguous()
+    rows, K = x.shape
+    N = weight.shape[0]
+    assert weight.shape[1] == K and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.is_contiguous()
+    if rows > BIGN_MAX_ROWS:
+        raise RuntimeError(f"big_out_linear: {rows} rows > {BIGN_MAX_ROWS} (AST_BIGN_MAX_ROWS)")
+    if S < 1 or rows % S:
+        raise ValueError(f"big_out_linear: {rows} rows are not a whole number of clips of {S} sections")
+    if lengths is not None and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (rows // S,) or not lengths.is_contiguous()):
+        raise ValueError(f"lengths must be a contiguous int32 tensor of shape ({rows // S},), got {lengths.dtype} {tuple(lengths.shape)}")
+    y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+    check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
+          "ast_bign_gemm_len")
+    return y
+
+
 class FFNFn(torch.autograd.Function):
     """linear2(dropout(relu(linear1(x)))) on <= 64 token rows (deterministic mode: <= 1024, the wide entries) in two launches forward and two backward
     (transformer.py _ff_block as style_encoder.py:181-187 / new_decoder.py:111-118 use it): the dropout mask is

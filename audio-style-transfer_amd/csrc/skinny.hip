@@ -116,6 +116,113 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_kernel(const float* __res
   }
 }
 
+// ---- ast_bign_gemm_len: embedding_to_stft at inference, any row count up to AST_BIGN_MAX_ROWS, per-clip section counts ----------
+// skinny_gemm_kernel's tile with a row mask and none of the training epilogues.  Row m = b S + s counts iff
+// s < clamp(n_valid[b], 1, S) (n_valid == null: every row counts).  A row that does not count is masked like a row >= M (its x
+// row is never read: clamped address, operand selected to zero) and stored as exactly 0; a 16-row tile without a row that counts
+// issues no x load and no MFMA, and a workgroup whose RT tiles are all such tiles stores its zeros and leaves before any load.
+// Both tests are wave-uniform (a ballot over the tile's rows).  Fragment layout, K slices per wave, MFMA order and the order of
+// the partial sums (sum_partials) are skinny_gemm_kernel's, so a row that counts has the same bits from either kernel.  The text
+// is a second copy because the existing kernels must compile to the code they had: sharing one inlined body reordered commutative
+// operands in all eight of them (profiles/simple_infer/README.md).
+// grid = (row blocks of 64, n tiles of 16): the row blocks are the fast index, so the up to 64 workgroups that share a 16 x K
+// weight slice are dispatched next to each other and the slice comes from HBM about once; x (<= 4 MB) is re-read by every n tile
+// and lives in L2 / Infinity Cache.
+template <int NS, int NW>
+__global__ __launch_bounds__(64 * NW) void bign_gemm_len_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ y, int M, int N,
+                                                             int K, int ldw, int ldy, int S, const int32_t* __restrict__ n_valid) {
+  constexpr int RT = 4;
+  __shared__ f32x4 part[NW][RT][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.y * 16, m0 = blockIdx.x * 16 * RT;
+  const int kb = wave * NS * 16;
+  const bool nv = n0 + i < N;
+  const float* wr = w + (size_t)(nv ? n0 + i : 0) * ldw;
+  const float* xr[RT];
+  bool mv[RT], live[RT];                              // lane's row of tile t counts; tile t holds such a row (wave-uniform)
+  bool any_live = false;
+  f32x4 acc[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    const int m = m0 + 16 * t + i;
+    mv[t] = m < M;
+    if (mv[t] && n_valid) {
+      const int b = m / S, nb = n_valid[b];
+      mv[t] = m - b * S < (nb < 1 ? 1 : nb > S ? S : nb);
+    }
+    live[t] = __any(mv[t]);
+    any_live = any_live || live[t];
+    xr[t] = x + (size_t)(mv[t] ? m : 0) * K;
+    acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (!any_live) {                                    // the same answer in every wave: the whole workgroup leaves
+    const int m = m0 + 16 * wave + i;
+    if (wave < RT && m < M) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (n0 + 4 * g + q < N) y[(size_t)m * ldy + n0 + 4 * g + q] = 0.f;
+    }
+    return;
+  }
+  float bq[4] = {0.f, 0.f, 0.f, 0.f};
+  if (bias) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int n = n0 + 4 * g + q; bq[q] = bias[n < N ? n : 0]; }
+  }
+  f32x4 wl[NS], xl[RT][NS];                           // every load of the wave's K slice is issued before the first MFMA
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int k = kb + s * 16 + 4 * g;
+    const int kc = k < K ? k : 0;
+    wl[s] = *reinterpret_cast<const f32x4*>(wr + kc);
+  }
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) xl[t][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!live[t]) continue;                           // one uniform branch per row tile
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int k = kb + s * 16 + 4 * g;
+      xl[t][s] = *reinterpret_cast<const f32x4*>(xr[t] + (k < K ? k : 0));
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);                  // see skinny_gemm_kernel
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const bool kv = kb + s * 16 + 4 * g < K;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 a = (kv && nv) ? wl[s] : z;
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      if (!live[t]) continue;
+      const f32x4 b = (kv && mv[t]) ? xl[t][s] : z;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], acc[t], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < RT; ++t) part[wave][t][lane] = acc[t];
+  __syncthreads();
+  if (wave >= RT) return;
+  const int m = m0 + 16 * wave + i, nb = n0 + 4 * g;  // wave t finishes row tile t: D[row = 4 g + r (n)][col = i (m)]
+  if (m >= M) return;
+  bool counts = false;
+#pragma unroll
+  for (int t = 0; t < RT; ++t) counts = counts || (t == wave && mv[t]);
+  f32x4 r = {0.f, 0.f, 0.f, 0.f};                     // a row that does not count: exactly 0, no bias
+  if (counts) {
+    r = sum_partials(part, wave, lane);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] += bq[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (nb + q < N) y[(size_t)m * ldy + nb + q] = r[q];
+}
+
 // dW[n][k] += sum_m dy[m][n] x[m][k] ; db[n] += sum_m dy[m][n]   (contraction over the token rows).
 // One wave = 16 n x 64 k of dW (n tile nt of 64 split over the workgroup's 4 waves, k tile kt): A[i][g] = dy[4s+g][n0+i],
 // B[g][j] = x[4s+g][k0+j] (16 lanes read 16 consecutive floats), the A fragment reused by 4 k-tiles.  The rows are walked in
@@ -401,6 +508,28 @@ int skinny_gemm_launch(const char* name, const float* x, const float* w, const f
   return 0;
 }
 
+// any row count up to AST_BIGN_MAX_ROWS, per-clip counts on the device; K / ldw / ldy / alignment rules of the wide entry
+int bign_gemm_len_launch(const char* name, const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw,
+                         int ldy, int S, const int32_t* n_valid, void* stream) {
+  if (!x || !w || !y || M < 1 || M > AST_BIGN_MAX_ROWS || S < 1 || M % S || N < 1 || K < 4 || (K & 3) || (ldw & 3) || ldw < K || ldy < N)
+    AST_FAIL("%s: bad args M=%d (1..%d) S=%d (M %% S == 0) N=%d K=%d ldw=%d ldy=%d", name, M, AST_BIGN_MAX_ROWS, S, N, K, ldw, ldy);
+  if ((((uintptr_t)x) | ((uintptr_t)w)) & 15) AST_FAIL("%s: operands must be 16-byte aligned", name);
+  if ((((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)n_valid)) & 3) AST_FAIL("%s: y, bias and n_valid must be 4-byte aligned", name);
+  const int steps = (K + 63) / 64;
+  if (steps > 16) AST_FAIL("%s: K=%d too large for the token path (<= 1024)", name, K);
+  if ((N + 15) / 16 > 65535) AST_FAIL("%s: N=%d too large (<= %d)", name, N, 65535 * 16);
+  dim3 grid((M + 63) / 64, (N + 15) / 16);
+#define AST_BL(NS_, NW_) hipLaunchKernelGGL((bign_gemm_len_kernel<NS_, NW_>), grid, dim3(64 * NW_), 0, (hipStream_t)stream, x, w, bias, y, \
+                                            M, N, K, ldw, ldy, S, n_valid)
+  if (steps <= 2) AST_BL(2, 4);
+  else if (steps <= 4) AST_BL(4, 4);
+  else if (steps <= 8) AST_BL(8, 4);
+  else AST_BL(8, 8);
+#undef AST_BL
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
 template <int RT>
 int linear_wgrad_launch(const char* name, const float* dy, const float* x, float* dW, float* db, int M, int N, int K, int lddy, int ldw,
                         void* stream) {
@@ -559,4 +688,10 @@ extern "C" long ast_bign_dgrad_wide_det_ws_floats(int M, int N, int K) {
 extern "C" int ast_bign_dgrad_wide_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, float* ws,
                                        long ws_floats, void* stream) {
   return bign_dgrad_launch<4, true>("ast_bign_dgrad_wide_det", dy, w, dx, M, N, K, lddy, ws, ws_floats, stream);
+}
+
+// ---- embedding_to_stft at inference: any row count, per-clip section counts (include/ast_hip.h) ---------------------------------
+extern "C" int ast_bign_gemm_len(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw, int ldy, int S,
+                                 const int32_t* n_valid, void* stream) {
+  return bign_gemm_len_launch("ast_bign_gemm_len", x, w, bias, y, M, N, K, ldw, ldy, S, n_valid, stream);
 }

@@ -17,7 +17,11 @@
  *   - activations are NHWC with the channel count padded to a multiple of 8;
  *     `dtype` selects their storage / MFMA operand type: AST_F32 (exact f32
  *     MFMA) or AST_BF16 (bf16 MFMA, f32 accumulate); parameters, statistics and
- *     losses are always f32.
+ *     losses are always f32;
+ *   - per-clip lengths of a padded inference batch (the ast_*_len entries,
+ *     ast_bign_gemm_len) are int32 DEVICE arrays that the kernels read and
+ *     clamp, so one captured graph serves every mix of lengths; both decoders
+ *     take them.
  */
 #ifndef AST_HIP_H
 #define AST_HIP_H
@@ -531,6 +535,25 @@ int ast_bign_dgrad_wide(const float* dy, const float* w, float* dx, int M, int N
 long ast_bign_dgrad_wide_det_ws_floats(int M, int N, int K);
 int ast_bign_dgrad_wide_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, float* ws, long ws_floats,
                             void* stream);
+
+/* ---- embedding_to_stft at inference: any row count, per-clip section counts (f32) ---------------------------------------------
+ * y[m][n] = bias[n] + sum_k x[m][k] w[n][k] for the rows m = b S + s of a padded batch with s < clamp(n_valid[b], 1, S); every other
+ * row is written as exactly 0 in every column n < N (no bias), and its x row is never read (NaN there reaches nothing).  Columns
+ * >= N of y are not touched.  n_valid is an int32 (M / S,) DEVICE array read by the kernel, so one captured graph serves every mix
+ * of lengths; the values cannot be checked without a sync, so the kernel clamps them (as ast_attn_fwd_len does).  n_valid == NULL:
+ * every row counts (S must still divide M).  Replaces generate_output (SimpleDecoder_TransformerOnly.py:17,62-66) where
+ * ast_skinny_gemm[_wide] cannot run: more than AST_WIDE_MAX_ROWS rows, or a padded batch.
+ * Checked on the host (ast_last_error names the entry): x, w, y non-null; 1 <= M <= AST_BIGN_MAX_ROWS; S >= 1 and M % S == 0;
+ * 1 <= N <= 16 * 65535; K, ldw, ldy and alignment as ast_skinny_gemm_wide (K % 4 == 0, 4 <= K <= 1024, ldw % 4 == 0, ldw >= K,
+ * ldy >= N, x and w 16-byte aligned; x rows are K apart).
+ * The kernel is the body of ast_skinny_gemm_wide (csrc/skinny.hip: v_mfma_f32_16x16x4_f32, 64 rows x 16 n per workgroup, no float
+ * atomics) with the row mask added: each element is one dot product in a k order that depends on K alone, so a row has the same
+ * bits whatever batch it sits in, repeats are bitwise equal, and with every row counting the result equals ast_skinny_gemm[_wide]
+ * bit for bit.  A 16-row tile without a row that counts issues no load of x and no MFMA; a workgroup of four such tiles loads
+ * nothing and only stores zeros.  Inference only: no backward. */
+#define AST_BIGN_MAX_ROWS 4096          /* 8 clips x 500 sections, rounded up */
+int ast_bign_gemm_len(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw, int ldy, int S,
+                      const int32_t* n_valid /* (M/S,) device, or NULL */, void* stream);
 
 /* ---- token programs: transformer layers in one launch (csrc/tokprog.hip) ------------------------------------------------
  * Replaces, for the <= 64 token rows of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
