@@ -157,6 +157,8 @@ _SIGS = {
     "ast_cqt_sections_len": ([vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp], i32),
     # embedding_to_stft at inference: up to AST_BIGN_MAX_ROWS rows, per-clip section counts read from the device (include/ast_hip.h)
     "ast_bign_gemm_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
+    # native-rate, stereo clips: load_audio's resample + channel mean per clip length read from the device (include/ast_hip.h)
+    "ast_resample_poly_len": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

@@ -233,6 +233,54 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int):
     return y.reshape(shape[:-1] + (m,))
 
 
+@functools.lru_cache(maxsize=None)
+def _device_sinc_bank(orig: int, new: int, device: str):
+    kern, width = _sinc_bank(orig, new)
+    return torch.from_numpy(kern).to(torch.device(device)), width
+
+
+def resampled_length(n: int, orig_freq: int, new_freq: int) -> int:
+    """samples `resample` returns for n: ceil(n * new / orig) in integers (the frequencies divided by their gcd)"""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    return -(-int(n) * new // orig)
+
+
+def resample_batch(waves: torch.Tensor, n_samples, orig_freq: int, new_freq: int = 22050):
+    """load_audio's `resample` and stereo mean (utilityFunctions.py:116-120) for a padded batch in one launch (two for stereo at
+    2:1), no length read on the host: waves (B, n) or (B, C, n) f32 on the device, C <= 2; n_samples int32 (B,) on the device
+    (clamped there to [1, n]) or None, every clip n long.  -> (y (B, m), n_out int32 (B,)), m = ceil(n * new / orig):
+    y[b, :n_out[b]] is `resample` (and torch.mean over the channels) of clip b alone, bit for bit, the rest of the row is 0,
+    n_out[b] = ceil(n_samples[b] * new / orig).  Equal frequencies and one channel return the inputs untouched."""
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError("Original frequency and desired frequency should be positive")
+    if not torch.is_tensor(waves) or waves.dim() not in (2, 3) or waves.dtype != torch.float32 or not waves.is_cuda:
+        raise ValueError("resample_batch: (B, n) or (B, C, n) float32 cuda waveforms expected")
+    B, n = waves.shape[0], waves.shape[-1]
+    C = waves.shape[1] if waves.dim() == 3 else 1
+    if C not in (1, 2):
+        raise ValueError(f"resample_batch: one or two channels expected, got {C}")
+    if n_samples is not None and not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,)
+                                      and n_samples.is_cuda):
+        raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+    if orig_freq == new_freq:
+        if C == 1 and waves.dim() == 2:
+            return waves, n_samples
+        n_out = torch.full((B,), n, dtype=torch.int32, device=waves.device) if n_samples is None else n_samples.clamp(1, n)
+        keep = torch.arange(n, device=waves.device)[None, :] < n_out[:, None]
+        return torch.where(keep, waves.mean(dim=1), 0.0), n_out
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    kern, width = _device_sinc_bank(orig, new, str(waves.device))
+    m = -(-n * new // orig)
+    y = torch.empty((B, m), dtype=torch.float32, device=waves.device)
+    n_out = torch.empty((B,), dtype=torch.int32, device=waves.device)
+    x, n_in = waves.contiguous(), None if n_samples is None else n_samples.contiguous()
+    check(lib().ast_resample_poly_len(ptr(x), B, C, n, ptr(kern), orig, new, kern.shape[1], width, ptr(y), m, 1.0, ptr(n_in), ptr(n_out),
+                                      stream()), "ast_resample_poly_len")
+    return y, n_out
+
+
 def _decode_wav(path):
     """PCM WAV -> (channels, samples) f32 in [-1, 1) with torchaudio.load's integer scaling, and the file's rate."""
     with _wave.open(path, "rb") as f:

@@ -12,13 +12,18 @@ every mix of lengths ("Ragged inference batches").
 
 From waveforms, as `process_audio` starts: `waves, n = utilityFunctions.pad_waveforms(clips)`, then
 `session.transfer(waves, class_emb, n_samples=n)` runs front end, models and reconstruction as one graph per (B, n_max); the
-per-clip sample counts stay on the device as well ("Ragged waveforms")."""
+per-clip sample counts stay on the device as well ("Ragged waveforms").  Recordings as they are decoded, at 44.1 or
+48 kHz and stereo: `waves, n = utilityFunctions.pad_waveforms(clips, channels=2)`, then
+`session.transfer(waves, class_emb, n_samples=n, sample_rate=48000)`; the resample and the channel mean run inside the same graph
+("Native-rate, stereo recordings")."""
 from __future__ import annotations
 
 import torch
 
 from . import config
 from . import utilityFunctions as U
+
+SAMPLE_RATE = 22050                                      # the models' rate: what load_audio resamples to
 
 
 class StyleTransferSession:
@@ -110,11 +115,14 @@ class StyleTransferSession:
         g.replay()
         return outs
 
-    def _run_wave(self, waves, class_emb, n_samples, frames, stft_stats, cqt_stats):
+    def _run_wave(self, waves, class_emb, n_samples, frames, stft_stats, cqt_stats, sample_rate=None):
+        if sample_rate is not None:                                  # native-rate and / or stereo rows: load_audio's resample + mean
+            waves, n_samples = U.resample_batch(waves, n_samples, sample_rate, SAMPLE_RATE)
         x, n_sections, n_frames = U.frontend_sections(waves, n_samples, stft_stats, cqt_stats)
         return self._run_ragged(x, class_emb, frames, n_sections, n_frames)
 
-    def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None):
+    def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None,
+                 sample_rate: int = SAMPLE_RATE):
         """Waveform in, waveform out (evaluation_style_transfer.py:135-159 for a batch): waves (B, n_max) f32 and class_emb
         (B, d) f32 on the device -> (waveforms (B, 256 * (frames - 1)), stft sections (B, S_max, 2, 287, 513), lengths).
 
@@ -124,12 +132,35 @@ class StyleTransferSession:
         its sections cover); the rest of its row is 0.  `frames` above is that count for a clip of n_max samples.  Without
         n_samples every clip is n_max long (the same path, the counts filled in on the device).  stft_stats / cqt_stats:
         (mean, std) of the z-score, (2, 513) / (2, 84), default none.  No length is read on the host: every mix of durations
-        at one (B, n_max) replays the same graph."""
-        if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
-            raise ValueError("transfer: (B, n) float32 cuda waveforms expected")
-        B, n = waves.shape
+        at one (B, n_max) replays the same graph.
+
+        sample_rate: the rate of `waves`, which may then be (B, C, n_max) with C <= 2 channels (a recording as it is decoded:
+        evaluation_style_transfer.py:162-171, load_audio).  n_samples counts samples at that rate.  Anything but (B, n) rows at
+        22 050 Hz goes through cqt.resample_batch first, inside the graph: clip b becomes the ceil(n_b * 22050 / sample_rate)
+        samples that `resample` and the mean over its channels give it alone, and everything above holds for those; the outputs
+        are at 22 050 Hz."""
+        if not torch.is_tensor(waves) or waves.dim() not in (2, 3) or waves.dtype != torch.float32:
+            raise ValueError("transfer: (B, n) or (B, C, n) float32 cuda waveforms expected")
+        if int(sample_rate) != sample_rate or sample_rate <= 0:
+            raise ValueError(f"transfer: sample_rate must be a positive integer, got {sample_rate}")
+        B, n = waves.shape[0], waves.shape[-1]
+        native = None if (sample_rate == SAMPLE_RATE and waves.dim() == 2) else int(sample_rate)
+        if native is not None:
+            C = waves.shape[1] if waves.dim() == 3 else 1
+            if C not in (1, 2):
+                raise ValueError(f"transfer: one or two channels expected, got {C}")
+            n = U.resampled_length(n, native, SAMPLE_RATE)
+            ns_min = max(513, 256 * ((U.WINDOW_SIZE + 1) // 2 - 1))
+            if n < ns_min:
+                raise ValueError(f"transfer: {waves.shape[-1]} samples at {native} Hz give {n} at {SAMPLE_RATE} Hz, the front end needs "
+                                 f"{ns_min}")
+        if not waves.is_cuda:
+            raise ValueError("transfer: (B, n) or (B, C, n) float32 cuda waveforms expected")
         if n_samples is None:
-            n_samples = torch.full((B,), n, dtype=torch.int32, device=waves.device)
+            if native is None:
+                n_samples = torch.full((B,), n, dtype=torch.int32, device=waves.device)
+            else:
+                n_samples = torch.full((B,), waves.shape[-1], dtype=torch.int32, device=waves.device)
         elif not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
             raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
         if len(U.section_starts(1 + n // 256)) < 1:
@@ -137,9 +168,11 @@ class StyleTransferSession:
         frames = U.clip_lengths(n, n, U.WINDOW_SIZE, self.overlap)[3]
         stats = tuple(t for pair in (stft_stats, cqt_stats) if pair is not None for t in pair)
         if not self.use_graph:
-            return self._run_wave(waves, class_emb, n_samples, frames, stft_stats, cqt_stats)
+            return self._run_wave(waves, class_emb, n_samples, frames, stft_stats, cqt_stats, native)
         key = (tuple(waves.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged", "waves",
                stft_stats is not None, cqt_stats is not None)
+        if native is not None:
+            key += (native, C)
         if key not in self._graphs:
             s_wav, s_cls, s_n = waves.clone(), class_emb.clone(), n_samples.clone()
             s_stats = [t.detach().clone() for t in stats]
@@ -149,12 +182,12 @@ class StyleTransferSession:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt)
+                    self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt, native)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                outs = self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt)
+                outs = self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt, native)
             self._graphs[key] = (g, [s_wav, s_cls, s_n] + s_stats, outs)
         g, static, outs = self._graphs[key]
         for dst, src in zip(static, (waves, class_emb, n_samples) + stats):

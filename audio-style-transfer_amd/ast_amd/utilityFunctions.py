@@ -115,11 +115,25 @@ def pad_sections(clips):
     return out, torch.tensor(n, dtype=torch.int32, device=out.device)
 
 
-def pad_waveforms(clips):
+def pad_waveforms(clips, channels=None):
     """Clips of different durations, a list of (n_i,) or (1, n_i) f32 tensors on one device, as one zero-padded batch:
-    -> (waves (B, n_max), n_samples int32 (B,)), both on that device."""
+    -> (waves (B, n_max), n_samples int32 (B,)), both on that device.
+    channels = C (1 or 2): every clip is (C, n_i), as a decoder delivers it (stereo recordings for `transfer(..., sample_rate=)`)
+    -> (waves (B, C, n_max), n_samples).  Without it a (2, n_i) clip is refused as before."""
     if not clips:
         raise ValueError("pad_waveforms needs at least one clip")
+    if channels is not None:
+        if channels not in (1, 2):
+            raise ValueError(f"pad_waveforms: one or two channels expected, got {channels}")
+        if any(not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != channels or c.shape[1] < 1 or c.dtype != torch.float32
+               or c.device != clips[0].device for c in clips):
+            raise ValueError(f"every clip must be a float32 ({channels}, n_i >= 1) tensor on one device, got "
+                             f"{[(tuple(c.shape), c.dtype, str(c.device)) if torch.is_tensor(c) else type(c).__name__ for c in clips]}")
+        n = [int(c.shape[1]) for c in clips]
+        out = clips[0].new_zeros((len(clips), channels, max(n)))
+        for b, c in enumerate(clips):
+            out[b, :, :n[b]] = c
+        return out, torch.tensor(n, dtype=torch.int32, device=out.device)
     flat = [c.reshape(-1) if torch.is_tensor(c) and (c.dim() == 1 or (c.dim() == 2 and c.shape[0] == 1)) else None for c in clips]
     if any(f is None or f.numel() < 1 or f.dtype != torch.float32 or f.device != flat[0].device for f in flat):
         raise ValueError("every clip must be a float32 (n_i >= 1,) or (1, n_i) tensor on one device, got "
@@ -223,7 +237,7 @@ def inverse_STFT_batch(spec, n_frames=None):
     return wave
 
 
-from .cqt import get_CQT, load_audio, resample, cqt_batch, cqt_sections  # noqa: E402,F401  (utilityFunctions.py:39-60,105-122)
+from .cqt import get_CQT, load_audio, resample, resample_batch, resampled_length, cqt_batch, cqt_sections  # noqa: E402,F401  (utilityFunctions.py:39-60,105-122)
 
 
 def inverse_CQT(*a, **k):

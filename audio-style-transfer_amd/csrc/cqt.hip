@@ -185,9 +185,12 @@ __global__ __launch_bounds__(256) void resample_poly_kernel(const float* __restr
 // (an LDS broadcast).  R outputs per thread (j, j+256, ...) share each tap.  8 x 44100 outputs x 359 taps: 151 -> ~10 us.
 // `nb`: input sample s of row blockIdx.y counts iff s < nb.  decimate2_kernel passes the row's width n, decimate2_len_kernel
 // (halving level o) the clip's ceil(ns_b / 2^o).
-template <int R>
+// EPI (decimate2_clip_kernel): 1 writes 0 for j >= mb, the clip's own output count; 2 also replaces what y holds (the first
+// channel) by the mean of that and this channel.  Neither touches the sum itself.
+template <int R, int EPI = 0>
 __device__ __forceinline__ void decimate2_body(const float* __restrict__ x, const int n, const float* __restrict__ h, const int klen,
-                                               const int width, float* __restrict__ y, const int m, const float gain, const int nb) {
+                                               const int width, float* __restrict__ y, const int m, const float gain, const int nb,
+                                               const int mb = 0) {
   extern __shared__ float sm[];
   const int b = blockIdx.y, t = threadIdx.x;
   const float* xb = x + (size_t)b * n;
@@ -225,7 +228,14 @@ __device__ __forceinline__ void decimate2_body(const float* __restrict__ x, cons
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int j = j0 + t + 256 * r;
-    if (j < m) y[(size_t)b * m + j] = acc[r] * gain;
+    if (EPI == 0) {
+      if (j < m) y[(size_t)b * m + j] = acc[r] * gain;
+    } else if (j < m) {
+#pragma clang fp contract(off)                                  // the mean adds two rounded products: no fma
+      float v = acc[r] * gain;
+      if (EPI == 2) v = (y[(size_t)b * m + j] + v) * 0.5f;
+      y[(size_t)b * m + j] = j < mb ? v : 0.0f;
+    }
   }
 }
 template <int R>
@@ -239,6 +249,195 @@ __global__ __launch_bounds__(256) void decimate2_len_kernel(const float* __restr
                                                             const float gain, const int32_t* __restrict__ n_samples, const int nsamp,
                                                             const int win, const int step, const int o) {
   decimate2_body<R>(x, n, h, klen, width, y, m, gain, min(n, ast_halved(ast_clip_len(n_samples[blockIdx.y], nsamp, win, step).ns, o)));
+}
+
+// ---- load_audio's resample + stereo mean for a padded batch of clips at their native rate (ast_resample_poly_len):
+// x (B, C, n), clip b holds nb = n_in[b] samples per channel (clamped to [1, n]; all n without n_in) and comes out as the
+// mb = ceil(nb * nnew / orig) samples it gives alone, 0 behind them.  Samples s >= nb are never read.
+#define AST_RS_THREADS 512                // 8 waves: two per SIMD
+#define AST_RS_P 4                        // phases a wave runs per pass over its rows' samples
+#define AST_RS_MAX_PITCH 640              // 64 rows x 640 floats = the 160 KiB of LDS
+
+__device__ __forceinline__ int resample_clip_n(const int32_t* __restrict__ n_in, const int b, const int n) {
+  return n_in ? min(max(n_in[b], 1), n) : n;
+}
+__device__ __forceinline__ int resample_clip_m(const int nb, const int orig, const int nnew) {
+  return (int)(((long long)nb * nnew + orig - 1) / orig);
+}
+
+// The 2:1 case: decimate2_body on channel `x` of every clip (row pitch `ld` = C * n), its outputs past mb zeroed.  AVG: the
+// second channel's launch, y becomes the mean of what the first wrote and this one.  A tile wholly past mb leaves before the
+// body's barrier (the first launch stores its zeros, the second finds them).
+template <int R, bool AVG>
+__global__ __launch_bounds__(256) void decimate2_clip_kernel(const float* __restrict__ x, const int ld, const int n,
+                                                             const float* __restrict__ h, const int klen, const int width,
+                                                             float* __restrict__ y, const int m, const float gain,
+                                                             const int32_t* __restrict__ n_in, int32_t* __restrict__ n_out) {
+  const int b = blockIdx.y;
+  const int nb = resample_clip_n(n_in, b, n), mb = resample_clip_m(nb, 2, 1);
+  if (!AVG && n_out && blockIdx.x == 0 && threadIdx.x == 0) n_out[b] = mb;
+  const int j0 = blockIdx.x * (256 * R);
+  if (j0 >= mb) {
+    if (!AVG) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int j = j0 + threadIdx.x + 256 * r;
+        if (j < m) y[(size_t)b * m + j] = 0.0f;
+      }
+    }
+    return;
+  }
+  decimate2_body<R, AVG ? 2 : 1>(x, ld, h, klen, width, y, m, gain, nb, mb);
+}
+
+// resample_poly_kernel's sum for P phases of one polyphase row i: a[q][(k - k0) mod 8] over k0 <= k < k1, the scalar tail into
+// a[q][0], the same tree.  xs[k] = x[i * orig - width + k] (LDS, or global in the unstaged kernel), kp = kern + p0 * klen.
+// UNI: k0 = 0 and k1 = klen for the whole wave, so k and the tap addresses are wave-uniform (scalar loads) and xs, a row of
+// even pitch, is read as 8-byte pairs.
+template <bool UNI, int P, typename XP>
+__device__ __forceinline__ void resample_rows(XP xs, const float* __restrict__ kp, const int klen, const int k0, const int k1,
+                                              float (&out)[P]) {
+  const int kb = UNI ? 0 : k0, ke = UNI ? klen : k1;
+  float a[P][8];
+#pragma unroll
+  for (int q = 0; q < P; ++q)
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[q][u] = 0.f;
+  int k = kb;
+  for (; k + 8 <= ke; k += 8) {
+    float xv[8];
+    if (UNI) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f32x2 v = *reinterpret_cast<const f32x2*>(&xs[k + 2 * u]);
+        xv[2 * u] = v[0]; xv[2 * u + 1] = v[1];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) xv[u] = xs[k + u];
+    }
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      float kv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) kv[u] = kp[(size_t)q * klen + k + u];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) a[q][u] = __builtin_fmaf(kv[u], xv[u], a[q][u]);
+    }
+  }
+  for (; k < ke; ++k) {
+    const float xv = xs[k];
+#pragma unroll
+    for (int q = 0; q < P; ++q) a[q][0] = __builtin_fmaf(kp[(size_t)q * klen + k], xv, a[q][0]);
+  }
+#pragma unroll
+  for (int q = 0; q < P; ++q) out[q] = ((a[q][0] + a[q][1]) + (a[q][2] + a[q][3])) + ((a[q][4] + a[q][5]) + (a[q][6] + a[q][7]));
+}
+
+// Any other ratio, staged.  A workgroup owns TI = 64 / C consecutive polyphase rows i of one clip, i.e. the TI * nnew
+// consecutive outputs j = i * nnew + p.  Output (i, p) reads x[i * orig - width + k], k < klen, whatever p is: lane l of every
+// wave keeps row l of an LDS image -- its own klen samples, zero-filled outside [0, nb) -- at a pitch of 2 mod 4 floats (8-byte
+// aligned rows on 32 distinct bank pairs per half wave: conflict-free ds_read_b64).  C = 2: rows 0..31 are channel 0 and rows
+// 32..63 channel 1 of the same 32 i, and the two halves of the wave swap their results for the mean.  The waves share out the
+// phases, AST_RS_P at a time: all 64 lanes of a wave are at one phase, so a tap is one scalar load for the wave (the bank,
+// 147 x 348 floats at 48 kHz, stays in L2), and a sample pair read from LDS serves AST_RS_P phases.
+template <int C>
+__global__ __launch_bounds__(AST_RS_THREADS) void resample_poly_len_kernel(const float* __restrict__ x, const int n,
+                                                                           const float* __restrict__ kern, const int orig, const int nnew,
+                                                                           const int klen, const int width, const int pitch,
+                                                                           float* __restrict__ y, const int m, const float gain,
+                                                                           const int32_t* __restrict__ n_in, int32_t* __restrict__ n_out) {
+#pragma clang fp contract(off)                                  // the sums are explicit fmas; the mean adds two rounded products
+  extern __shared__ f32x2 rs_sm[];                              // 8-byte aligned: the rows are read as pairs
+  float* sm = reinterpret_cast<float*>(rs_sm);
+  constexpr int TI = 64 / C;
+  const int b = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nb = resample_clip_n(n_in, b, n), mb = resample_clip_m(nb, orig, nnew);
+  if (n_out && blockIdx.x == 0 && t == 0) n_out[b] = mb;
+  const int i0 = blockIdx.x * TI;
+  const long long j0 = (long long)i0 * nnew;
+  float* yb = y + (size_t)b * m;
+  if (j0 >= mb) {                                               // workgroup-uniform: a tile behind the clip's end stores zeros
+    const int je = (int)min((long long)m - j0, (long long)TI * nnew);
+    for (int j = t; j < je; j += AST_RS_THREADS) yb[j0 + j] = 0.0f;
+    return;
+  }
+  for (int r = wv; r < 64; r += AST_RS_THREADS / 64) {
+    const int c = C == 2 ? r >> 5 : 0;
+    const int s0 = (i0 + (C == 2 ? r & 31 : r)) * orig - width;
+    const float* xr = x + ((size_t)b * C + c) * n;
+    float* row = sm + r * pitch;
+    for (int k = lane; k < klen; k += 64) {
+      const int s = s0 + k;
+      row[k] = (s >= 0 && s < nb) ? xr[s] : 0.0f;
+    }
+  }
+  __syncthreads();
+  const int i = i0 + (C == 2 ? lane & 31 : lane);
+  const long long jb = (long long)i * nnew;
+  const int s0 = i * orig - width;
+  const bool live = jb < mb;
+  const int k0 = live ? max(-s0, 0) : 0, k1 = live ? min(klen, nb - s0) : 0;
+  const bool uni = __all(k0 == 0 && k1 == klen);
+  const float* row = sm + lane * pitch;
+  auto store = [&](const int p, const float sum) {
+#pragma clang fp contract(off)
+    float v = sum * gain;
+    if (C == 2) v = (v + __shfl_xor(v, 32)) * 0.5f;
+    const long long j = jb + p;
+    if ((C == 1 || lane < 32) && j < m) yb[j] = j < mb ? v : 0.0f;
+  };
+  const int ngroups = nnew / AST_RS_P;
+  for (int g = wv; g < ngroups; g += AST_RS_THREADS / 64) {
+    const float* kp = kern + (size_t)g * AST_RS_P * klen;
+    float r[AST_RS_P];
+    if (uni)
+      resample_rows<true, AST_RS_P>(row, kp, klen, 0, klen, r);
+    else
+      resample_rows<false, AST_RS_P>(row, kp, klen, k0, k1, r);
+#pragma unroll
+    for (int q = 0; q < AST_RS_P; ++q) store(g * AST_RS_P + q, r[q]);
+  }
+  for (int p = ngroups * AST_RS_P + wv; p < nnew; p += AST_RS_THREADS / 64) {
+    float r[1];
+    if (uni)
+      resample_rows<true, 1>(row, kern + (size_t)p * klen, klen, 0, klen, r);
+    else
+      resample_rows<false, 1>(row, kern + (size_t)p * klen, klen, k0, k1, r);
+    store(p, r[0]);
+  }
+}
+
+// The same entry where a row of klen samples per lane does not fit in LDS (klen > AST_RS_MAX_PITCH: 96 kHz -> 22.05 kHz has
+// 694 taps): resample_poly_kernel's one thread per output on the clip's own counts.
+template <int C>
+__global__ __launch_bounds__(256) void resample_poly_len_direct_kernel(const float* __restrict__ x, const int n,
+                                                                       const float* __restrict__ kern, const int orig, const int nnew,
+                                                                       const int klen, const int width, float* __restrict__ y, const int m,
+                                                                       const float gain, const int32_t* __restrict__ n_in,
+                                                                       int32_t* __restrict__ n_out) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y;
+  const int nb = resample_clip_n(n_in, b, n), mb = resample_clip_m(nb, orig, nnew);
+  if (n_out && blockIdx.x == 0 && threadIdx.x == 0) n_out[b] = mb;
+  const float* xb = x + (size_t)b * C * n;
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
+    float v = 0.0f;
+    if (j < mb) {
+      const int i = j / nnew, p = j - i * nnew;
+      const int s0 = i * orig - width;
+      const int k0 = s0 < 0 ? -s0 : 0, k1 = min(klen, nb - s0);
+      float r[1];
+      resample_rows<false, 1>(xb + s0, kern + (size_t)p * klen, klen, k0, k1, r);
+      v = r[0] * gain;
+      if (C == 2) {
+        resample_rows<false, 1>(xb + n + s0, kern + (size_t)p * klen, klen, k0, k1, r);
+        v = (v + r[0] * gain) * 0.5f;
+      }
+    }
+    y[(size_t)b * m + j] = v;
+  }
 }
 
 // z-score + overlap windows of the CQT planes into the bins behind the STFT's (dataloader.py:9-18,
@@ -409,6 +608,67 @@ extern "C" int ast_resample_poly(const float* x, int B, int n, const float* kern
   if (orig == 2 && nnew == 1 && klen <= 4096) return decimate2_launch(x, B, n, kern, klen, width, y, m, gain, nullptr, 0, stream);
   hipLaunchKernelGGL(resample_poly_kernel, dim3(std::min((m + 255) / 256, 4096), B), dim3(256), 0, (hipStream_t)stream, x, n, kern, orig, nnew,
                      klen, width, y, m, gain);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+template <int R>
+void decimate2_clip_launch(const float* x, int B, int C, int n, const float* h, int klen, int width, float* y, int m, float gain,
+                           const int32_t* n_in, int32_t* n_out, hipStream_t s) {
+  const size_t lds = (2 * (size_t)(256 * R + (klen + 1) / 2) + klen) * sizeof(float);
+  const dim3 grid((m + 256 * R - 1) / (256 * R), B);
+  hipLaunchKernelGGL((decimate2_clip_kernel<R, false>), grid, dim3(256), lds, s, x, C * n, n, h, klen, width, y, m, gain, n_in, n_out);
+  if (C == 2)
+    hipLaunchKernelGGL((decimate2_clip_kernel<R, true>), grid, dim3(256), lds, s, x + n, C * n, n, h, klen, width, y, m, gain, n_in, n_out);
+}
+}  // namespace
+
+extern "C" int ast_resample_poly_len(const float* x, int B, int C, int n, const float* kern, int orig, int nnew, int klen, int width,
+                                     float* y, int m, float gain, const int32_t* n_in, int32_t* n_out, void* stream) {
+  if (!x || !kern || !y) AST_FAIL("ast_resample_poly_len: null pointer");
+  if (B < 1 || B > 65535 || n < 1 || orig < 1 || nnew < 1 || klen < 1 || width < 0 || m < 1)
+    AST_FAIL("ast_resample_poly_len: bad shape (B=%d n=%d orig=%d new=%d klen=%d width=%d m=%d)", B, n, orig, nnew, klen, width, m);
+  if (C != 1 && C != 2) AST_FAIL("ast_resample_poly_len: bad shape (C=%d: one or two channels)", C);
+  // n * nnew is the numerator of every clip's output count, C * n the pitch of a clip; row i starts at i * orig - width and
+  // the last tile's rows run up to 64 past the last output's
+  if ((long)n * nnew >= (1L << 31) || (long)C * n >= (1L << 31) || (long)n + 66L * orig + klen >= (1L << 31))
+    AST_FAIL("ast_resample_poly_len: signal too long (n=%d orig=%d new=%d)", n, orig, nnew);
+  if ((long)m != ((long)n * nnew + orig - 1) / orig)
+    AST_FAIL("ast_resample_poly_len: bad shape (m=%d is not ceil(n * new / orig) at n=%d orig=%d new=%d)", m, n, orig, nnew);
+  if ((long)((m - 1) / nnew) * orig + klen >= (1L << 31)) AST_FAIL("ast_resample_poly_len: signal too long");
+  const hipStream_t s = (hipStream_t)stream;
+  if (orig == 2 && nnew == 1 && klen <= 4096) {
+    if ((long)m * B >= 256 * 1024)
+      decimate2_clip_launch<4>(x, B, C, n, kern, klen, width, y, m, gain, n_in, n_out, s);
+    else
+      decimate2_clip_launch<1>(x, B, C, n, kern, klen, width, y, m, gain, n_in, n_out, s);
+    AST_CHECK_LAUNCH();
+    return 0;
+  }
+  const int pitch = ((klen + 1) & ~3) + 2;                      // the smallest count >= klen that is 2 mod 4
+  if (pitch > AST_RS_MAX_PITCH) {
+    const dim3 grid(std::min((m + 255) / 256, 4096), B);
+    if (C == 2)
+      hipLaunchKernelGGL(resample_poly_len_direct_kernel<2>, grid, dim3(256), 0, s, x, n, kern, orig, nnew, klen, width, y, m, gain, n_in, n_out);
+    else
+      hipLaunchKernelGGL(resample_poly_len_direct_kernel<1>, grid, dim3(256), 0, s, x, n, kern, orig, nnew, klen, width, y, m, gain, n_in, n_out);
+    AST_CHECK_LAUNCH();
+    return 0;
+  }
+  const int lds = 64 * pitch * (int)sizeof(float);
+  static LdsAttrOnce attr;
+  if (attr.set(64 * AST_RS_MAX_PITCH * (int)sizeof(float),
+               {(const void*)resample_poly_len_kernel<1>, (const void*)resample_poly_len_kernel<2>}))
+    return -3;
+  const int tile = (64 / C) * nnew;                             // outputs per workgroup
+  const dim3 grid((unsigned)(((long)m + tile - 1) / tile), B);
+  if (C == 2)
+    hipLaunchKernelGGL(resample_poly_len_kernel<2>, grid, dim3(AST_RS_THREADS), lds, s, x, n, kern, orig, nnew, klen, width, pitch, y, m, gain,
+                       n_in, n_out);
+  else
+    hipLaunchKernelGGL(resample_poly_len_kernel<1>, grid, dim3(AST_RS_THREADS), lds, s, x, n, kern, orig, nnew, klen, width, pitch, y, m, gain,
+                       n_in, n_out);
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -459,6 +459,17 @@ int ast_cqt_sections_len(const float* cqt, int Bc, int T, int nb, const float* m
  * kern = its sinc_interp_hann bank) and the halving resample between CQT octaves (orig=2, nnew=1). */
 int ast_resample_poly(const float* x, int B, int n, const float* kern, int orig, int nnew, int klen, int width, float* y, int m,
                       float gain, void* stream);
+/* load_audio's resample and stereo mean (utilityFunctions.py:116-120) for a padded batch of clips at their native rate, before
+ * the ragged front end above.  x (B, C, n) f32, C = 1 or 2; the channel rows of clip b hold n_in[b] samples (int32 (B,) DEVICE
+ * array, clamped on the device to [1, n]; NULL: every clip is n long).  y (B, m) mono, m == ceil(n * nnew / orig).  With nb the
+ * clamped count and mb = ceil(nb * nnew / orig): y[b][j], j < mb, is ast_resample_poly's sum on x[b][c][0..nb) alone -- samples
+ * s >= nb count as 0 and are never read -- in the same order (bit-equal for C = 1; for C = 2 the two channels' results are added
+ * and halved, torch.mean's order); y[b][j] = 0 for j >= mb; n_out[b] = mb (int32 (B,) device array, may be NULL).
+ * orig = 2, nnew = 1, klen <= 4096 runs the staged halving (one launch per channel); other ratios stage each workgroup's
+ * sample span in LDS (64 rows of klen <= 638 samples), longer filters run one thread per output.  n * nnew, C * n and
+ * n + 66 * orig + klen must stay below 2^31. */
+int ast_resample_poly_len(const float* x, int B, int C, int n, const float* kern, int orig, int nnew, int klen, int width,
+                          float* y, int m, float gain, const int32_t* n_in, int32_t* n_out, void* stream);
 
 /* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
  * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
