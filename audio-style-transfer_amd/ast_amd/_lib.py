@@ -266,3 +266,18 @@ def ptr(t):
     if not t.is_cuda:
         raise RuntimeError("libast_hip needs device tensors (got a CPU tensor); there is no CPU path")
     return t.data_ptr()
+
+
+def len_tensor(t, B, what, device=False, contiguous=False, training=False):
+    """The one check of a per-clip count argument (lengths, key_len, n_sections, n_frames, n_samples): None passes through; anything
+    but an int32 tensor of shape (B,) is a ValueError naming `what`.  The kernels read it as int32, so nothing else may reach them.
+    device: it must be on the GPU as well (the entry points that never reach ptr() with it).  contiguous: return it contiguous.
+    training: the caller's module is in training mode, where per-clip lengths do not exist; refused before the tensor is looked at."""
+    if t is None:
+        return None
+    if training:
+        raise ValueError("per-clip lengths are an inference feature: call .eval() first (training takes equal-length batches)")
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (B,) and (t.is_cuda or not device)):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what} must be an int32 {'device ' if device else ''}tensor of shape ({B},), got {got}")
+    return t.contiguous() if contiguous else t

@@ -5,7 +5,8 @@ import torch
 import torch.nn as nn
 
 from . import layers as L
-from . import config, ops, tokprog
+from . import ops, tokprog
+from ._lib import len_tensor
 from .style_encoder import (CHANNELS, ResBlock, SinusoidalPositionalEncoding, _module_bank, build_resnet,
                             initialize_weights, run_resnet)  # noqa: F401
 
@@ -37,8 +38,7 @@ class ContentEncoder(nn.Module):
         """lengths: None, or an int32 (B,) device tensor for a zero-padded batch at inference -- clip b holds lengths[b] real
         sections, and its transformer attends to those only.  Rows s >= lengths[b] of the result are finite and unspecified."""
         B, S, C, T, F = x.shape
-        if lengths is not None and self.training:
-            raise ValueError("per-clip lengths are an inference feature: call .eval() first (training takes equal-length batches)")
+        len_tensor(lengths, B, "lengths", training=self.training)
         bank = _module_bank(self)
         bank.prepare(self.training)
         feat = run_resnet(self.cnn, ops.cached_nhwc(x, L.img_dtype()), self.training)
@@ -46,12 +46,4 @@ class ContentEncoder(nn.Module):
         if self._inp is not None:
             feat = L.linear(feat, self._inp)
         seq = L.layer_norm(self.pos_encoder(feat.view(B, S, -1)), self.norm)
-        if lengths is not None:                       # the token programs have no key mask: per-operator layers
-            for lyr in self._layers:
-                seq = lyr(seq, self.training, lengths)
-        elif config.tok_programs > 0 and tokprog.encoder_stack_ok(seq, self._layers):
-            seq = tokprog.encoder_stack(seq, self._layers, self.training, xcd=1)
-        else:
-            for lyr in self._layers:
-                seq = lyr(seq, self.training)
-        return seq
+        return tokprog.run_encoder_stack(self._layers, seq, self.training, lengths, xcd=1)

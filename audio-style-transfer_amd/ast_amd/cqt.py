@@ -25,7 +25,7 @@ import wave as _wave
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream
+from ._lib import check, len_tensor, lib, ptr, stream
 
 HANN_BANDWIDTH = 1.50018310546875          # librosa.filters.window_bandwidth("hann")
 C1_HZ = 32.70319566257483                  # librosa.note_to_hz("C1"), cqt's default fmin
@@ -120,11 +120,10 @@ def _len_call(name, args, len_tail=None):
 
 
 def _n_samples_arg(n_samples, B, hop_length, window_size, overlap_frames):
-    if not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
-        raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+    n_samples = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
     if hop_length != 256:
         raise ValueError("n_samples: the per-clip length arithmetic is built for hop_length=256 (the reference's only configuration)")
-    return n_samples.contiguous(), window_size, window_size - overlap_frames
+    return n_samples, window_size, window_size - overlap_frames
 
 
 def cqt_batch(waves: torch.Tensor, sample_rate=22050, n_bins=84, hop_length=256, out=None, bin0=0, n_samples=None, window_size=287,
@@ -260,9 +259,7 @@ def resample_batch(waves: torch.Tensor, n_samples, orig_freq: int, new_freq: int
     C = waves.shape[1] if waves.dim() == 3 else 1
     if C not in (1, 2):
         raise ValueError(f"resample_batch: one or two channels expected, got {C}")
-    if n_samples is not None and not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,)
-                                      and n_samples.is_cuda):
-        raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+    n_in = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
     if orig_freq == new_freq:
         if C == 1 and waves.dim() == 2:
             return waves, n_samples
@@ -275,7 +272,7 @@ def resample_batch(waves: torch.Tensor, n_samples, orig_freq: int, new_freq: int
     m = -(-n * new // orig)
     y = torch.empty((B, m), dtype=torch.float32, device=waves.device)
     n_out = torch.empty((B,), dtype=torch.int32, device=waves.device)
-    x, n_in = waves.contiguous(), None if n_samples is None else n_samples.contiguous()
+    x = waves.contiguous()
     check(lib().ast_resample_poly_len(ptr(x), B, C, n, ptr(kern), orig, new, kern.shape[1], width, ptr(y), m, 1.0, ptr(n_in), ptr(n_out),
                                       stream()), "ast_resample_poly_len")
     return y, n_out

@@ -22,6 +22,7 @@ import torch
 
 from . import config
 from . import utilityFunctions as U
+from ._lib import len_tensor
 
 SAMPLE_RATE = 22050                                      # the models' rate: what load_audio resamples to
 
@@ -32,21 +33,46 @@ class StyleTransferSession:
         self.use_graph, self.overlap = use_graph, overlap
         self._graphs = {}
 
-    def _run(self, sections, class_emb, frames):
+    def _run(self, sections, class_emb, frames, n_sections=None, n_frames=None):
+        """frames: the batch's frame count (int, from S_max).  n_sections, n_frames: int32 (B,) on the device for a padded batch
+        (-> waveforms, stft sections, lengths), or both None for equal clips (-> waveforms, stft sections)."""
         with torch.no_grad():
-            content_emb = self.content(sections)
-            out = self.decoder(content_emb, class_emb, target_length=content_emb.size(1))       # (B,S,2,287,513)
-            spec = U.sections2spectrogram_batch(out, frames, self.overlap)
-            return U.inverse_STFT_batch(spec), out
-
-    def _run_ragged(self, sections, class_emb, frames, n_sections, n_frames):
-        """frames: the batch's frame count (int, from S_max); n_sections, n_frames: int32 (B,) on the device."""
-        with torch.no_grad():
+            if n_sections is None:
+                content_emb = self.content(sections)
+                out = self.decoder(content_emb, class_emb, target_length=content_emb.size(1))   # (B,S,2,287,513)
+                spec = U.sections2spectrogram_batch(out, frames, self.overlap)
+                return U.inverse_STFT_batch(spec), out
             content_emb = self.content(sections, n_sections)
             out = self.decoder(content_emb, class_emb, target_length=content_emb.size(1), lengths=n_sections)
             nf = n_frames.clamp(2, frames)              # what the two kernels clamp to, so `lengths` says what they wrote
             spec = U.sections2spectrogram_batch(out, frames, self.overlap, n_sections=n_sections, n_frames=nf)
             return U.inverse_STFT_batch(spec, nf), out, (nf - 1) * 256
+
+    def _replay(self, key, fn, inputs):
+        """fn(*inputs), as one hipGraph per key: captured on first use over clones of the inputs (after two warm-up runs on a side
+        stream: weight banks -- eval: sigma from the stored u, v -- and caches), then replayed, with every input that is not its
+        clone already copied in first.  Returns the captured outputs.  Without use_graph: fn(*inputs)."""
+        if not self.use_graph:
+            return fn(*inputs)
+        if key not in self._graphs:
+            static = [t.detach().clone() for t in inputs]
+            side = torch.cuda.Stream(device=inputs[0].device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    fn(*static)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                outs = fn(*static)
+            self._graphs[key] = (g, static, outs)
+        g, static, outs = self._graphs[key]
+        for dst, src in zip(static, inputs):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src)
+        g.replay()
+        return outs
 
     def __call__(self, sections: torch.Tensor, class_emb: torch.Tensor, original_frames=None, n_sections: torch.Tensor = None):
         """sections (B,S,2,287,597) f32, class_emb (B,d) f32 on the device -> (waveforms (B, 256*(T-1)), stft sections).
@@ -61,65 +87,23 @@ class StyleTransferSession:
         if n_sections is not None:
             return self._call_ragged(sections, class_emb, original_frames, n_sections)
         frames = original_frames or (wind - self.overlap) * (S - 1) + wind
-        if not self.use_graph:
-            return self._run(sections, class_emb, frames)
         key = (tuple(sections.shape), tuple(class_emb.shape), frames, config.compute_dtype)
-        if key not in self._graphs:
-            s_sec, s_cls = sections.clone(), class_emb.clone()
-            side = torch.cuda.Stream(device=sections.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):                    # warm-up: weight banks (eval: sigma from the stored u, v), caches
-                    self._run(s_sec, s_cls, frames)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                outs = self._run(s_sec, s_cls, frames)
-            self._graphs[key] = (g, s_sec, s_cls, outs)
-        g, s_sec, s_cls, outs = self._graphs[key]
-        if s_sec.data_ptr() != sections.data_ptr():
-            s_sec.copy_(sections)
-        if s_cls.data_ptr() != class_emb.data_ptr():
-            s_cls.copy_(class_emb)
-        g.replay()
-        return outs
+        return self._replay(key, lambda sec, cls: self._run(sec, cls, frames), [sections, class_emb])
 
     def _call_ragged(self, sections, class_emb, original_frames, n_sections):
         B, S, _, wind, _ = sections.shape
         frames = (wind - self.overlap) * (S - 1) + wind
         for name, t in (("n_sections", n_sections), ("original_frames", original_frames)):
-            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (B,) and t.is_cuda):
-                raise ValueError(f"with n_sections, {name} must be an int32 device tensor of shape ({B},)")
+            len_tensor(t, B, f"with n_sections, {name}", device=True)
         n_frames = U.default_frames(n_sections, wind, self.overlap) if original_frames is None else original_frames
-        if not self.use_graph:
-            return self._run_ragged(sections, class_emb, frames, n_sections, n_frames)
         key = (tuple(sections.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged")
-        if key not in self._graphs:
-            s_sec, s_cls, s_n, s_f = sections.clone(), class_emb.clone(), n_sections.clone(), n_frames.clone()
-            side = torch.cuda.Stream(device=sections.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._run_ragged(s_sec, s_cls, frames, s_n, s_f)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                outs = self._run_ragged(s_sec, s_cls, frames, s_n, s_f)
-            self._graphs[key] = (g, s_sec, s_cls, s_n, s_f, outs)
-        g, *static, outs = self._graphs[key]
-        for dst, src in zip(static, (sections, class_emb, n_sections, n_frames)):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src)
-        g.replay()
-        return outs
+        return self._replay(key, lambda sec, cls, n, f: self._run(sec, cls, frames, n, f), [sections, class_emb, n_sections, n_frames])
 
     def _run_wave(self, waves, class_emb, n_samples, frames, stft_stats, cqt_stats, sample_rate=None):
         if sample_rate is not None:                                  # native-rate and / or stereo rows: load_audio's resample + mean
             waves, n_samples = U.resample_batch(waves, n_samples, sample_rate, SAMPLE_RATE)
         x, n_sections, n_frames = U.frontend_sections(waves, n_samples, stft_stats, cqt_stats)
-        return self._run_ragged(x, class_emb, frames, n_sections, n_frames)
+        return self._run(x, class_emb, frames, n_sections, n_frames)
 
     def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None,
                  sample_rate: int = SAMPLE_RATE):
@@ -156,42 +140,20 @@ class StyleTransferSession:
                                  f"{ns_min}")
         if not waves.is_cuda:
             raise ValueError("transfer: (B, n) or (B, C, n) float32 cuda waveforms expected")
-        if n_samples is None:
-            if native is None:
-                n_samples = torch.full((B,), n, dtype=torch.int32, device=waves.device)
-            else:
-                n_samples = torch.full((B,), waves.shape[-1], dtype=torch.int32, device=waves.device)
-        elif not (torch.is_tensor(n_samples) and n_samples.dtype == torch.int32 and tuple(n_samples.shape) == (B,) and n_samples.is_cuda):
-            raise ValueError(f"n_samples must be an int32 device tensor of shape ({B},)")
+        if n_samples is None:                                        # every clip fills its row (counted at the rate of `waves`)
+            n_samples = torch.full((B,), waves.shape[-1], dtype=torch.int32, device=waves.device)
+        len_tensor(n_samples, B, "n_samples", device=True)
         if len(U.section_starts(1 + n // 256)) < 1:
             raise ValueError(f"transfer: {n} samples give no section")
         frames = U.clip_lengths(n, n, U.WINDOW_SIZE, self.overlap)[3]
-        stats = tuple(t for pair in (stft_stats, cqt_stats) if pair is not None for t in pair)
-        if not self.use_graph:
-            return self._run_wave(waves, class_emb, n_samples, frames, stft_stats, cqt_stats, native)
+        stats = [t for pair in (stft_stats, cqt_stats) if pair is not None for t in pair]
+        k = 2 if stft_stats is not None else 0
+
+        def run(wav, cls, n, *st):                                   # st: the (mean, std) pairs that were given, flattened as `stats`
+            return self._run_wave(wav, cls, n, frames, st[:k] or None, st[k:] or None, native)
+
         key = (tuple(waves.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged", "waves",
                stft_stats is not None, cqt_stats is not None)
         if native is not None:
             key += (native, C)
-        if key not in self._graphs:
-            s_wav, s_cls, s_n = waves.clone(), class_emb.clone(), n_samples.clone()
-            s_stats = [t.detach().clone() for t in stats]
-            k = 2 if stft_stats is not None else 0
-            s_stft, s_cqt = (tuple(s_stats[:2]) if stft_stats is not None else None), (tuple(s_stats[k:k + 2]) if cqt_stats is not None else None)
-            side = torch.cuda.Stream(device=waves.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt, native)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                outs = self._run_wave(s_wav, s_cls, s_n, frames, s_stft, s_cqt, native)
-            self._graphs[key] = (g, [s_wav, s_cls, s_n] + s_stats, outs)
-        g, static, outs = self._graphs[key]
-        for dst, src in zip(static, (waves, class_emb, n_samples) + stats):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src)
-        g.replay()
-        return outs
+        return self._replay(key, run, [waves, class_emb, n_samples] + stats)

@@ -15,7 +15,7 @@ import math
 import torch
 
 from . import _lib, config
-from ._lib import Gather, check, dcode, lib, ptr, stream
+from ._lib import Gather, check, dcode, len_tensor, lib, ptr, stream
 
 
 @functools.lru_cache(maxsize=None)
@@ -608,8 +608,7 @@ def big_out_linear(x, weight, bias, S, lengths=None):
         raise RuntimeError(f"big_out_linear: {rows} rows > {BIGN_MAX_ROWS} (AST_BIGN_MAX_ROWS)")
     if S < 1 or rows % S:
         raise ValueError(f"big_out_linear: {rows} rows are not a whole number of clips of {S} sections")
-    if lengths is not None and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (rows // S,) or not lengths.is_contiguous()):
-        raise ValueError(f"lengths must be a contiguous int32 tensor of shape ({rows // S},), got {lengths.dtype} {tuple(lengths.shape)}")
+    lengths = len_tensor(lengths, rows // S, "lengths", contiguous=True)
     y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
     check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
           "ast_bign_gemm_len")
@@ -1264,8 +1263,7 @@ class AttnCoreFn(torch.autograd.Function):
         if key_len is not None:
             if p_drop > 0.0:
                 raise RuntimeError("the key-masked attention core (key_len) has no dropout: p_drop must be 0")
-            if key_len.dtype != torch.int32 or tuple(key_len.shape) != (B,) or not key_len.is_contiguous():
-                raise ValueError(f"key_len must be a contiguous int32 tensor of shape ({B},), got {key_len.dtype} {tuple(key_len.shape)}")
+            key_len = len_tensor(key_len, B, "key_len", contiguous=True)
             check(lib().ast_attn_fwd_len(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
                                          B, H, Lq, Lk, dh, ldq, ldk, d, int(causal), ptr(key_len), int(key_period), stream()),
                   "ast_attn_fwd_len")

@@ -14,7 +14,8 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import layers as L
-from . import config, ops, tokprog
+from . import ops, tokprog
+from ._lib import len_tensor
 
 CHANNELS = (32, 64, 128, 256, 512, 512)
 
@@ -161,11 +162,7 @@ class StyleEncoder(nn.Module):
         """lengths: None, or an int32 (B,) device tensor for a zero-padded batch at inference -- clip b holds lengths[b] real
         sections; its CLS token (or, without one, the mean) sees those only.  Nothing is read on the host."""
         B, S, C, T, F = x.shape
-        if lengths is not None:
-            if self.training:
-                raise ValueError("per-clip lengths are an inference feature: call .eval() first (training takes equal-length batches)")
-            if not (torch.is_tensor(lengths) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (B,)):
-                raise ValueError(f"lengths must be an int32 tensor of shape ({B},)")
+        len_tensor(lengths, B, "lengths", training=self.training)
         bank = _module_bank(self)
         bank.prepare(self.training)
         feat = self.cnn.run(ops.cached_nhwc(x, L.img_dtype()), self.training)
@@ -175,27 +172,19 @@ class StyleEncoder(nn.Module):
         if self.use_cls:
             seq = torch.cat([self.cls_token.expand(B, -1, -1), seq], dim=1)
         seq = L.layer_norm(self.pos_encoder(seq), self.norm)
-        if lengths is not None:                       # the token programs have no key mask: per-operator layers
-            # CLS sits at position 0, so the valid keys are a prefix of lengths + 1 tokens (formed on the device)
-            key_len = lengths + 1 if self.use_cls else lengths
-            for lyr in self._layers:
-                seq = lyr(seq, self.training, key_len)
-            if self.use_cls:
-                style_emb = seq[:, 0, :]
-            else:
-                # mean over the clip's own rows, as seq.mean(dim=1) forms it for the clip alone: the sum (padded rows add an
-                # exact 0) times the f32 reciprocal of the count, looked up on the device in a table built once per (S, device)
-                n = lengths.clamp(1, S)               # what the attention core clamps to
-                keep = torch.arange(S, device=seq.device)[None, :] < n[:, None]
-                style_emb = torch.where(keep[:, :, None], seq, torch.zeros_like(seq)).sum(dim=1) * self._recip(S, seq.device)[n.long() - 1][:, None]
-            class_emb = class_prototypes(style_emb, labels) if labels is not None else None
-            return style_emb, class_emb
-        if config.tok_programs > 0 and tokprog.encoder_stack_ok(seq, self._layers):
-            seq = tokprog.encoder_stack(seq, self._layers, self.training, xcd=0)
+        # CLS sits at position 0, so the valid keys are a prefix of lengths + 1 tokens (formed on the device)
+        key_len = lengths + 1 if self.use_cls and lengths is not None else lengths
+        seq = tokprog.run_encoder_stack(self._layers, seq, self.training, key_len, xcd=0)
+        if self.use_cls:
+            style_emb = seq[:, 0, :]
+        elif lengths is None:
+            style_emb = seq.mean(dim=1)
         else:
-            for lyr in self._layers:
-                seq = lyr(seq, self.training)
-        style_emb = seq[:, 0, :] if self.use_cls else seq.mean(dim=1)
+            # mean over the clip's own rows, as seq.mean(dim=1) forms it for the clip alone: the sum (padded rows add an
+            # exact 0) times the f32 reciprocal of the count, looked up on the device in a table built once per (S, device)
+            n = lengths.clamp(1, S)               # what the attention core clamps to
+            keep = torch.arange(S, device=seq.device)[None, :] < n[:, None]
+            style_emb = torch.where(keep[:, :, None], seq, torch.zeros_like(seq)).sum(dim=1) * self._recip(S, seq.device)[n.long() - 1][:, None]
         class_emb = class_prototypes(style_emb, labels) if labels is not None else None
         return style_emb, class_emb
 

@@ -18,7 +18,7 @@ import ctypes
 
 import torch
 
-from . import ops
+from . import config, ops
 from ._lib import check, lib, ptr, stream
 
 GEMM, ATTN_FWD, ATTN_BWD, ADLN_FWD, ADLN_BWD = 1, 2, 3, 4, 5
@@ -271,6 +271,17 @@ class EncoderStackFn(torch.autograd.Function):
 
 def encoder_stack(x, layers, training, xcd=0):
     return EncoderStackFn.apply(x, layers[0].ff1.weight, layers, bool(training), int(xcd))
+
+
+def run_encoder_stack(layers, seq, training, lengths=None, xcd=0):
+    """The stack of `layers` (layers.EncoderLayer) over seq (B, L, d), however it runs: as one token program when they are enabled
+    and take this shape, else layer by layer.  lengths (None, or int32 (B,): row b attends to its first lengths[b] tokens) always
+    goes layer by layer: the token programs have no key mask.  The decoders' counterpart is decoder_trunk.DecoderTrunk._stack."""
+    if lengths is None and config.tok_programs > 0 and encoder_stack_ok(seq, layers):
+        return encoder_stack(seq, layers, training, xcd=xcd)
+    for lyr in layers:
+        seq = lyr(seq, training, lengths)
+    return seq
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import check, lib, ptr, stream
+from ._lib import check, len_tensor, lib, ptr, stream
 from .cqt import _len_call
 
 WINDOW_SIZE = 287
@@ -37,7 +37,7 @@ def stft_sections(waves: torch.Tensor, mean=None, std=None, n_sections=None, F_t
         out = torch.zeros((Bc, n_sections, 2, WINDOW_SIZE, F_total), dtype=torch.float32, device=waves.device)
     _len_call("ast_stft_sections", (ptr(waves.contiguous()), Bc, n, ptr(mean.contiguous()), ptr(std.contiguous()), ptr(out), n_sections,
                                     WINDOW_SIZE, step, F_total),
-              None if n_samples is None else (ptr(_len_tensor(n_samples, Bc, "n_samples")),))
+              None if n_samples is None else (ptr(len_tensor(n_samples, Bc, "n_samples", contiguous=True)),))
     # version bump: the kernel wrote through the raw pointer (keeps version-keyed caches honest).  NOT `out.add_(0)`: that is a
     # read-modify-write of ALL bins on this stream, and the CQT kernel fills bins >= 513 of the same tensor on another stream
     # (train.Trainer._run_frontend) -- the no-op add wrote stale CQT bins back now and then (found by the mixed-length oracle test)
@@ -87,12 +87,6 @@ def sections2spectrogram(sections, original_size, overlap=OVERLAP_FRAMES):
     """utilityFunctions.py:265-283: count-normalised overlap-average, (S,2,wind,F) -> (2,original_size,F), as one
     HIP kernel (ast_sections_overlap_avg)."""
     return sections2spectrogram_batch(sections.unsqueeze(0), original_size, overlap)[0]
-
-
-def _len_tensor(t, B, what):
-    if t.dtype != torch.int32 or tuple(t.shape) != (B,):
-        raise ValueError(f"{what} must be an int32 tensor of shape ({B},), got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
 
 
 def default_frames(n_sections, wind=WINDOW_SIZE, overlap=OVERLAP_FRAMES):
@@ -158,7 +152,7 @@ def clip_lengths(ns, nsamp, window_size=WINDOW_SIZE, overlap_frames=OVERLAP_FRAM
 def frontend_lengths(n_samples, nsamp):
     """n_samples int32 (B,) on the device -> (n_sections, n_frames) int32 (B,) on the device, no sync (ast_frontend_lengths)."""
     B = n_samples.shape[0]
-    n_samples = _len_tensor(n_samples, B, "n_samples")
+    n_samples = len_tensor(n_samples, B, "n_samples", contiguous=True)
     n_sec, n_fr = torch.empty_like(n_samples), torch.empty_like(n_samples)
     check(lib().ast_frontend_lengths(ptr(n_samples), B, int(nsamp), WINDOW_SIZE, WINDOW_SIZE - OVERLAP_FRAMES, ptr(n_sec), ptr(n_fr), stream()),
           "ast_frontend_lengths")
@@ -201,8 +195,8 @@ def sections2spectrogram_batch(sections, original_size, overlap=OVERLAP_FRAMES, 
         raise ValueError("n_frames needs n_sections")
     tail = None
     if n_sections is not None:
-        n_sections = _len_tensor(n_sections, B, "n_sections")
-        n_frames = default_frames(n_sections, wind, overlap) if n_frames is None else _len_tensor(n_frames, B, "n_frames")
+        n_sections = len_tensor(n_sections, B, "n_sections", contiguous=True)
+        n_frames = default_frames(n_sections, wind, overlap) if n_frames is None else len_tensor(n_frames, B, "n_frames", contiguous=True)
         tail = (ptr(n_sections), ptr(n_frames))
     _len_call("ast_sections_overlap_avg", (ptr(sec), ptr(out), B, S, wind, hop, F, n_bins, out_T), tail)
     return out
@@ -233,7 +227,7 @@ def inverse_STFT_batch(spec, n_frames=None):
     frames = torch.empty((B, T, 1024), dtype=torch.float32, device=spec.device)
     wave = torch.empty((B, 256 * (T - 1)), dtype=torch.float32, device=spec.device)
     _len_call("ast_istft", (ptr(spec), B, T, ptr(frames), ptr(wave)),
-              None if n_frames is None else (ptr(_len_tensor(n_frames, B, "n_frames")),))
+              None if n_frames is None else (ptr(len_tensor(n_frames, B, "n_frames", contiguous=True)),))
     return wave
 
 
