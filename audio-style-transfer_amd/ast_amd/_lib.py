@@ -159,6 +159,13 @@ _SIGS = {
     "ast_bign_gemm_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
     # native-rate, stereo clips: load_audio's resample + channel mean per clip length read from the device (include/ast_hip.h)
     "ast_resample_poly_len": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp], i32),
+    # spectrogram metrics of the evaluation scripts for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
+    "ast_spec_mse_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_spec_mse_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
+    "ast_band_energy_ws_floats": ([i32, i32], C.c_long),
+    "ast_band_energy_len": ([vp, i32, i32, vp, i32, vp, C.c_long, vp, vp], i32),
+    "ast_band_energy_run_frames": ([], i32),
+    "ast_pearson_rows": ([vp, vp, i32, i32, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

@@ -105,24 +105,8 @@ class StyleTransferSession:
         x, n_sections, n_frames = U.frontend_sections(waves, n_samples, stft_stats, cqt_stats)
         return self._run(x, class_emb, frames, n_sections, n_frames)
 
-    def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None,
-                 sample_rate: int = SAMPLE_RATE):
-        """Waveform in, waveform out (evaluation_style_transfer.py:135-159 for a batch): waves (B, n_max) f32 and class_emb
-        (B, d) f32 on the device -> (waveforms (B, 256 * (frames - 1)), stft sections (B, S_max, 2, 287, 513), lengths).
-
-        n_samples (int32 (B,) device tensor, e.g. from utilityFunctions.pad_waveforms): row b of waves is a zero-padded clip of
-        n_samples[b] samples, clamped on the device to [36 608, n_max].  Clip b has T_b = 1 + n_b // 256 frames, the sections
-        the reference cuts from them, and comes back as lengths[b] = 256 * (frames_b - 1) samples, frames_b = min(T_b, what
-        its sections cover); the rest of its row is 0.  `frames` above is that count for a clip of n_max samples.  Without
-        n_samples every clip is n_max long (the same path, the counts filled in on the device).  stft_stats / cqt_stats:
-        (mean, std) of the z-score, (2, 513) / (2, 84), default none.  No length is read on the host: every mix of durations
-        at one (B, n_max) replays the same graph.
-
-        sample_rate: the rate of `waves`, which may then be (B, C, n_max) with C <= 2 channels (a recording as it is decoded:
-        evaluation_style_transfer.py:162-171, load_audio).  n_samples counts samples at that rate.  Anything but (B, n) rows at
-        22 050 Hz goes through cqt.resample_batch first, inside the graph: clip b becomes the ceil(n_b * 22050 / sample_rate)
-        samples that `resample` and the mean over its channels give it alone, and everything above holds for those; the outputs
-        are at 22 050 Hz."""
+    def _transfer_plan(self, waves, class_emb, n_samples, stft_stats, cqt_stats, sample_rate):
+        """transfer's argument checks -> (graph key, inputs, frames, native rate or None, number of STFT statistics tensors)"""
         if not torch.is_tensor(waves) or waves.dim() not in (2, 3) or waves.dtype != torch.float32:
             raise ValueError("transfer: (B, n) or (B, C, n) float32 cuda waveforms expected")
         if int(sample_rate) != sample_rate or sample_rate <= 0:
@@ -149,11 +133,80 @@ class StyleTransferSession:
         stats = [t for pair in (stft_stats, cqt_stats) if pair is not None for t in pair]
         k = 2 if stft_stats is not None else 0
 
-        def run(wav, cls, n, *st):                                   # st: the (mean, std) pairs that were given, flattened as `stats`
-            return self._run_wave(wav, cls, n, frames, st[:k] or None, st[k:] or None, native)
-
         key = (tuple(waves.shape), tuple(class_emb.shape), frames, config.compute_dtype, "ragged", "waves",
                stft_stats is not None, cqt_stats is not None)
         if native is not None:
             key += (native, C)
-        return self._replay(key, run, [waves, class_emb, n_samples] + stats)
+        return key, [waves, class_emb, n_samples] + stats, frames, native, k
+
+    def transfer(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, stft_stats=None, cqt_stats=None,
+                 sample_rate: int = SAMPLE_RATE):
+        """Waveform in, waveform out (evaluation_style_transfer.py:135-159 for a batch): waves (B, n_max) f32 and class_emb
+        (B, d) f32 on the device -> (waveforms (B, 256 * (frames - 1)), stft sections (B, S_max, 2, 287, 513), lengths).
+
+        n_samples (int32 (B,) device tensor, e.g. from utilityFunctions.pad_waveforms): row b of waves is a zero-padded clip of
+        n_samples[b] samples, clamped on the device to [36 608, n_max].  Clip b has T_b = 1 + n_b // 256 frames, the sections
+        the reference cuts from them, and comes back as lengths[b] = 256 * (frames_b - 1) samples, frames_b = min(T_b, what
+        its sections cover); the rest of its row is 0.  `frames` above is that count for a clip of n_max samples.  Without
+        n_samples every clip is n_max long (the same path, the counts filled in on the device).  stft_stats / cqt_stats:
+        (mean, std) of the z-score, (2, 513) / (2, 84), default none.  No length is read on the host: every mix of durations
+        at one (B, n_max) replays the same graph.
+
+        sample_rate: the rate of `waves`, which may then be (B, C, n_max) with C <= 2 channels (a recording as it is decoded:
+        evaluation_style_transfer.py:162-171, load_audio).  n_samples counts samples at that rate.  Anything but (B, n) rows at
+        22 050 Hz goes through cqt.resample_batch first, inside the graph: clip b becomes the ceil(n_b * 22050 / sample_rate)
+        samples that `resample` and the mean over its channels give it alone, and everything above holds for those; the outputs
+        are at 22 050 Hz."""
+        key, inputs, frames, native, k = self._transfer_plan(waves, class_emb, n_samples, stft_stats, cqt_stats, sample_rate)
+
+        def run(wav, cls, n, *st):                                   # st: the (mean, std) pairs that were given, flattened as `stats`
+            return self._run_wave(wav, cls, n, frames, st[:k] or None, st[k:] or None, native)
+
+        return self._replay(key, run, inputs)
+
+    def transfer_and_score(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, reference: torch.Tensor = None,
+                           n_reference: torch.Tensor = None, **transfer_kw):
+        """`transfer` and the spectrogram metrics of its output (ast_amd.metrics) as one graph under a key of its own
+        -> (waveforms, stft sections, lengths, scores); the first three are what `transfer` returns for the same arguments
+        (transfer_kw: stft_stats, cqt_stats, sample_rate).
+
+        scores["mse_spectrogram"] (B,): the output against the input at 22 050 Hz, clip b over min(its input count -- after
+        resample_batch, the device-side n_out, when sample_rate is given --, lengths[b]) samples
+        (evaluation_reconstruction.py:193-204, 105-118).
+        reference (B, m) f32 device rows at 22 050 Hz, n_reference int32 (B,) device tensor or None for full rows:
+        scores["instrumentation_similarity"] (B,) scores the output, over lengths[b] samples, against it
+        (evaluation_style_transfer.py:111-119).  Both with pad_mode="constant".  No length is read on the host."""
+        from . import metrics as M
+        key, inputs, frames, native, k = self._transfer_plan(waves, class_emb, n_samples, transfer_kw.pop("stft_stats", None),
+                                                             transfer_kw.pop("cqt_stats", None), transfer_kw.pop("sample_rate", SAMPLE_RATE))
+        if transfer_kw:
+            raise TypeError(f"transfer_and_score: unexpected arguments {sorted(transfer_kw)}")
+        B, n_stats = waves.shape[0], len(inputs) - 3
+        if reference is None:
+            if n_reference is not None:
+                raise ValueError("transfer_and_score: n_reference without reference")
+            extra = []
+        else:
+            if not torch.is_tensor(reference) or reference.dim() != 2 or reference.dtype != torch.float32 or reference.shape[0] != B or \
+                    not reference.is_cuda:
+                raise ValueError(f"transfer_and_score: reference must be ({B}, m) float32 cuda rows")
+            if n_reference is None:
+                n_reference = torch.full((B,), reference.shape[1], dtype=torch.int32, device=reference.device)
+            extra = [reference, len_tensor(n_reference, B, "n_reference", device=True)]
+
+        def run(wav, cls, n, *rest):
+            st, ref = rest[:n_stats], rest[n_stats:]
+            if native is not None:                                   # score against what the models see: the clip at 22 050 Hz
+                wav, n = U.resample_batch(wav, n, native, SAMPLE_RATE)
+            out_wave, sections, lengths = self._run_wave(wav, cls, n, frames, st[:k] or None, st[k:] or None)
+            scores = (M.mse_spectrogram(wav, out_wave, n, lengths),)
+            if ref:
+                scores += (M.instrumentation_similarity(out_wave, ref[0], lengths, ref[1]),)
+            return (out_wave, sections, lengths) + scores
+
+        key += ("score", None if reference is None else tuple(reference.shape))
+        res = self._replay(key, run, inputs + extra)
+        scores = {"mse_spectrogram": res[3]}
+        if reference is not None:
+            scores["instrumentation_similarity"] = res[4]
+        return res[0], res[1], res[2], scores

@@ -1,0 +1,77 @@
+"""Spectrogram metrics of the reference's evaluation scripts on the device, for a padded batch of clips of different lengths:
+
+    mse_spectrogram            evaluation_reconstruction.py:105-118 (on the audio truncated to a common length, :193-204)
+    instrumentation_similarity evaluation_style_transfer.py:111-119 (band energies + Pearson's r)
+
+Both are |STFT| plus a reduction (csrc/metrics.hip); the spectrogram is never stored and no length is read on the host, so the
+calls can be captured in a graph (StyleTransferSession.transfer_and_score).  `librosa.stft`'s documented defaults are restated,
+not linked: centred frames, periodic Hann window, T(n) = 1 + n // hop frames; pad_mode "constant" (librosa >= 0.10, the default)
+or "reflect" (librosa < 0.10, get_STFT).  Parity with librosa's own output is unpinned ("Spectrogram metrics")."""
+from __future__ import annotations
+
+import torch
+
+from ._lib import check, len_tensor, lib, ptr, stream
+
+PAD_MODES = {"constant": 0, "reflect": 1}
+MSE_N_FFT, MSE_HOP = 1024, 256                           # N_FFT, HOP_LENGTH of evaluation_reconstruction.py
+BAND_N_FFT, BAND_HOP, BAND_BINS = 2048, 512, 1025        # librosa.stft defaults
+
+
+def _rows(t, name, what, n_fft, pad_mode):
+    if pad_mode not in PAD_MODES:
+        raise ValueError(f"{name}: pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or t.shape[1] < 1:
+        got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{name}: {what} must be (B, n) float32 rows, got {got}")
+    if pad_mode == "reflect" and t.shape[1] < n_fft // 2 + 1:
+        raise ValueError(f"{name}: reflect padding needs rows of at least {n_fft // 2 + 1} samples, {what} has {t.shape[1]}")
+    return t.contiguous()
+
+
+def mse_spectrogram(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
+    """original (B, n), generated (B, m) f32 device rows -> (B,) f32: mean over 513 x T_b of (|A| - |G|)^2 at n_fft 1024, hop 256,
+    both clips cut to L_b = min(n_original[b], n_generated[b]) samples first, T_b = 1 + L_b // 256.
+    n_original, n_generated: int32 (B,) device tensors, clamped on the device to [1, row width] ([513, row width] with
+    pad_mode="reflect"); None: the rows are full."""
+    a = _rows(original, "mse_spectrogram", "original", MSE_N_FFT, pad_mode)
+    g = _rows(generated, "mse_spectrogram", "generated", MSE_N_FFT, pad_mode)
+    B = a.shape[0]
+    if g.shape[0] != B:
+        raise ValueError(f"mse_spectrogram: {B} original and {g.shape[0]} generated rows")
+    na = len_tensor(n_original, B, "n_original", device=True, contiguous=True)
+    ng = len_tensor(n_generated, B, "n_generated", device=True, contiguous=True)
+    L = lib()
+    ws = torch.empty(L.ast_spec_mse_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(L.ast_spec_mse_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(), ptr(out),
+                             stream()), "ast_spec_mse_len")
+    return out
+
+
+def band_energy(waves, n_samples=None, pad_mode="constant"):
+    """waves (B, n) f32 device rows -> (B, 1025) f32: E[b, f] = sum over the clip's own T(n_b) = 1 + n_b // 512 frames of |S_b[f, t]|
+    at n_fft 2048, hop 512.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
+    pad_mode="reflect"); None: the rows are full."""
+    w = _rows(waves, "band_energy", "waves", BAND_N_FFT, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    L = lib()
+    ws = torch.empty(L.ast_band_energy_ws_floats(B, n), dtype=torch.float32, device=w.device)
+    out = torch.empty((B, BAND_BINS), dtype=torch.float32, device=w.device)
+    check(L.ast_band_energy_len(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(ws), ws.numel(), ptr(out), stream()), "ast_band_energy_len")
+    return out
+
+
+def instrumentation_similarity(a, b, n_a=None, n_b=None, pad_mode="constant"):
+    """a (B, n), b (B, m) f32 device rows -> (B,) f32: Pearson's r of band_energy(a)[i] and band_energy(b)[i] over the 1025 bins,
+    exactly 0.0 where r is not finite (a constant energy vector; the reference's nan -> 0.0).  The clips of a pair keep their own
+    lengths."""
+    for t, what in ((a, "a"), (b, "b")):
+        _rows(t, "instrumentation_similarity", what, BAND_N_FFT, pad_mode)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"instrumentation_similarity: {a.shape[0]} and {b.shape[0]} rows")
+    ea, eb = band_energy(a, n_a, pad_mode), band_energy(b, n_b, pad_mode)
+    out = torch.empty(a.shape[0], dtype=torch.float32, device=ea.device)
+    check(lib().ast_pearson_rows(ptr(ea), ptr(eb), a.shape[0], BAND_BINS, ptr(out), stream()), "ast_pearson_rows")
+    return out

@@ -471,6 +471,37 @@ int ast_resample_poly(const float* x, int B, int n, const float* kern, int orig,
 int ast_resample_poly_len(const float* x, int B, int C, int n, const float* kern, int orig, int nnew, int klen, int width,
                           float* y, int m, float gain, const int32_t* n_in, int32_t* n_out, void* stream);
 
+/* ---- spectrogram metrics of the evaluation scripts for a padded batch (csrc/metrics.hip).  |STFT| with librosa.stft's
+ * documented defaults restated: frame t is centred on sample t * hop, periodic Hann window of n_fft, T(n) = 1 + n / hop frames.
+ * pad_mode AST_PAD_CONSTANT: samples outside the clip are 0 (librosa >= 0.10); AST_PAD_REFLECT: reflected at the clip's own ends
+ * (librosa < 0.10, get_STFT).  Per-clip sample counts are int32 (B,) DEVICE arrays, NULL: the row is full; device values are
+ * clamped to [1, n] (constant) or [n_fft / 2 + 1, n] (reflect; the host refuses shorter rows), samples behind a clip's end are
+ * never read.  The spectrogram is never stored: partials go to the caller's workspace ws (f32, the _ws_floats count; every slot
+ * that is read is written first), a second launch sums them in a fixed order in double.  No atomics; results are bit-reproducible
+ * and row b does not depend on the other rows.  B <= 65535, n + 2 n_fft < 2^31. */
+#define AST_PAD_CONSTANT 0
+#define AST_PAD_REFLECT 1
+/* mse_spectrogram (evaluation_reconstruction.py:105-118 on the audio truncated to a common length at :193-204), n_fft 1024,
+ * hop 256: original (B, n_orig), generated (B, n_gen) f32; L_b = min of the two clamped counts, both clips cut to L_b samples
+ * before padding; out[b] = mean over 513 x T(L_b) of (|A| - |G|)^2.  One complex FFT per frame pair: two consecutive frames of
+ * one clip in the real and the imaginary part, split by Hermitian symmetry, first for original, then for generated -- the same
+ * arithmetic for both, so equal clips score exactly 0.  ws: B * ceil(T(min(n_orig, n_gen)) / 2) floats. */
+long ast_spec_mse_ws_floats(int B, int n_orig, int n_gen);
+int ast_spec_mse_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
+                     const int32_t* len_gen, int pad_mode, float* ws, long ws_floats, float* out, void* stream);
+/* the band energies of instrumentation_similarity (evaluation_style_transfer.py:112-115), n_fft 2048, hop 512: waves (B, n) f32,
+ * energy[b][f] = sum_{t < T(n_b)} |S_b[f][t]|, (B, 1025) f32.  A workgroup walks a run of consecutive frames of one clip (the
+ * 2048-point real FFT through the 1024-point network) and stores one (1025,) partial per run.
+ * ws: B * ceil((1 + n / 512) / run) * 1025 floats. */
+long ast_band_energy_ws_floats(int B, int n);
+int ast_band_energy_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, float* ws, long ws_floats,
+                        float* energy, void* stream);
+/* frames per run of the band-energy kernel (what the workspace count above is built on) */
+int ast_band_energy_run_frames(void);
+/* Pearson's r of rows a[b], b[b] of n >= 2 values in double (evaluation_style_transfer.py:117-119: pearsonr, nan -> 0.0):
+ * out[b] is exactly 0 where r is not finite (a constant row).  a, b (B, n), out (B,) f32. */
+int ast_pearson_rows(const float* a, const float* b, int B, int n, float* out, void* stream);
+
 /* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
  * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
  * workgroup's partial into a slot indexed by its workgroup / tile / row id (plain stores; every slot is written on every call, so
