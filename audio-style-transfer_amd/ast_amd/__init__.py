@@ -12,7 +12,7 @@ from .content_encoder import ContentEncoder  # noqa: F401
 from .new_decoder import Decoder, compute_comprehensive_loss  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401
 from .losses import infoNCE_loss, margin_loss, adversarial_loss, disentanglement_loss  # noqa: F401
-from .metrics import mse_spectrogram, band_energy, instrumentation_similarity  # noqa: F401
+from .metrics import mse_spectrogram, band_energy, instrumentation_similarity, mfcc, mfcc_distance  # noqa: F401
 
 
 class deterministic:

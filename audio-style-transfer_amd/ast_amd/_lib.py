@@ -166,6 +166,14 @@ _SIGS = {
     "ast_band_energy_len": ([vp, i32, i32, vp, i32, vp, C.c_long, vp, vp], i32),
     "ast_band_energy_run_frames": ([], i32),
     "ast_pearson_rows": ([vp, vp, i32, i32, vp, vp], i32),
+    # MFCC and mfcc_distance for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
+    "ast_mel_table_words": ([], i32),
+    "ast_mel_table": ([i32, vp], i32),
+    "ast_mfcc_run_frames": ([], i32),
+    "ast_mfcc_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_mfcc_len": ([vp, i32, i32, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
+    "ast_mfcc_distance_ws_floats": ([i32, i32, i32, i32], C.c_long),
+    "ast_mfcc_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

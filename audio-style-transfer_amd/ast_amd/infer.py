@@ -165,7 +165,7 @@ class StyleTransferSession:
         return self._replay(key, run, inputs)
 
     def transfer_and_score(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, reference: torch.Tensor = None,
-                           n_reference: torch.Tensor = None, **transfer_kw):
+                           n_reference: torch.Tensor = None, mfcc: bool = False, **transfer_kw):
         """`transfer` and the spectrogram metrics of its output (ast_amd.metrics) as one graph under a key of its own
         -> (waveforms, stft sections, lengths, scores); the first three are what `transfer` returns for the same arguments
         (transfer_kw: stft_stats, cqt_stats, sample_rate).
@@ -175,7 +175,11 @@ class StyleTransferSession:
         (evaluation_reconstruction.py:193-204, 105-118).
         reference (B, m) f32 device rows at 22 050 Hz, n_reference int32 (B,) device tensor or None for full rows:
         scores["instrumentation_similarity"] (B,) scores the output, over lengths[b] samples, against it
-        (evaluation_style_transfer.py:111-119).  Both with pad_mode="constant".  No length is read on the host."""
+        (evaluation_style_transfer.py:111-119).
+        mfcc=True (needs a reference): scores["mfcc_distance"] (B,) as well, the output over lengths[b] samples against the
+        reference over n_reference[b], at 13 coefficients and hop 256 (evaluation_style_transfer.py:99-109), in the same graph,
+        which then has a key of its own; the default leaves the call as it was.
+        All with pad_mode="constant".  No length is read on the host."""
         from . import metrics as M
         key, inputs, frames, native, k = self._transfer_plan(waves, class_emb, n_samples, transfer_kw.pop("stft_stats", None),
                                                              transfer_kw.pop("cqt_stats", None), transfer_kw.pop("sample_rate", SAMPLE_RATE))
@@ -185,6 +189,8 @@ class StyleTransferSession:
         if reference is None:
             if n_reference is not None:
                 raise ValueError("transfer_and_score: n_reference without reference")
+            if mfcc:
+                raise ValueError("transfer_and_score: mfcc=True scores against a reference, and none was given")
             extra = []
         else:
             if not torch.is_tensor(reference) or reference.dim() != 2 or reference.dtype != torch.float32 or reference.shape[0] != B or \
@@ -202,11 +208,17 @@ class StyleTransferSession:
             scores = (M.mse_spectrogram(wav, out_wave, n, lengths),)
             if ref:
                 scores += (M.instrumentation_similarity(out_wave, ref[0], lengths, ref[1]),)
+                if mfcc:
+                    scores += (M.mfcc_distance(out_wave, ref[0], lengths, ref[1]),)
             return (out_wave, sections, lengths) + scores
 
         key += ("score", None if reference is None else tuple(reference.shape))
+        if mfcc:
+            key += ("mfcc",)
         res = self._replay(key, run, inputs + extra)
         scores = {"mse_spectrogram": res[3]}
         if reference is not None:
             scores["instrumentation_similarity"] = res[4]
+            if mfcc:
+                scores["mfcc_distance"] = res[5]
         return res[0], res[1], res[2], scores

@@ -3,11 +3,15 @@
     mse_spectrogram            evaluation_reconstruction.py:105-118 (on the audio truncated to a common length, :193-204)
     instrumentation_similarity evaluation_style_transfer.py:111-119 (band energies + Pearson's r)
 
-Both are |STFT| plus a reduction (csrc/metrics.hip); the spectrogram is never stored and no length is read on the host, so the
+    mfcc, mfcc_distance        evaluation_style_transfer.py:99-109: librosa.feature.mfcc restated as a formula chain (below)
+
+All are |STFT| plus a reduction (csrc/metrics.hip); the spectrogram is never stored and no length is read on the host, so the
 calls can be captured in a graph (StyleTransferSession.transfer_and_score).  `librosa.stft`'s documented defaults are restated,
 not linked: centred frames, periodic Hann window, T(n) = 1 + n // hop frames; pad_mode "constant" (librosa >= 0.10, the default)
 or "reflect" (librosa < 0.10, get_STFT).  Parity with librosa's own output is unpinned ("Spectrogram metrics")."""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -16,6 +20,7 @@ from ._lib import check, len_tensor, lib, ptr, stream
 PAD_MODES = {"constant": 0, "reflect": 1}
 MSE_N_FFT, MSE_HOP = 1024, 256                           # N_FFT, HOP_LENGTH of evaluation_reconstruction.py
 BAND_N_FFT, BAND_HOP, BAND_BINS = 2048, 512, 1025        # librosa.stft defaults
+MFCC_N_FFT, MFCC_SR, MFCC_HOPS = 2048, 22050, (256, 512)  # librosa.feature.mfcc defaults; HOP_LENGTH of the two evaluation scripts
 
 
 def _rows(t, name, what, n_fft, pad_mode):
@@ -74,4 +79,70 @@ def instrumentation_similarity(a, b, n_a=None, n_b=None, pad_mode="constant"):
     ea, eb = band_energy(a, n_a, pad_mode), band_energy(b, n_b, pad_mode)
     out = torch.empty(a.shape[0], dtype=torch.float32, device=ea.device)
     check(lib().ast_pearson_rows(ptr(ea), ptr(eb), a.shape[0], BAND_BINS, ptr(out), stream()), "ast_pearson_rows")
+    return out
+
+
+_mel_tables = {}
+
+
+def _mel_table(device):
+    """The Slaney mel filter bank at 22 050 Hz as the sparse table the kernels read (ast_mel_table: built on the host in double),
+    on `device`.  Filled on first use per device, which has to happen outside a graph capture: a session's warm-up runs do that."""
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _mel_tables:
+        L = lib()
+        words = (ctypes.c_int32 * L.ast_mel_table_words())()
+        check(L.ast_mel_table(MFCC_SR, ctypes.addressof(words)), "ast_mel_table")
+        _mel_tables[key] = torch.tensor(list(words), dtype=torch.int32).to(device)
+    return _mel_tables[key]
+
+
+def _mfcc_args(name, n_mfcc, hop_length):
+    if not isinstance(n_mfcc, int) or isinstance(n_mfcc, bool) or not 1 <= n_mfcc <= 128:
+        raise ValueError(f"{name}: n_mfcc must be an integer in 1 .. 128, got {n_mfcc!r}")
+    if hop_length not in MFCC_HOPS:
+        raise ValueError(f"{name}: hop_length must be 256 or 512 (the reference's two values), got {hop_length!r}")
+
+
+def mfcc(waves, n_samples=None, n_mfcc=20, hop_length=512, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, n_mfcc, T_max) f32, T_max = 1 + n // hop_length: what
+    librosa.feature.mfcc(y, sr=22050, n_mfcc, hop_length) is documented to compute for clip b over its own n_b samples, in
+    librosa's layout; frames t >= T_b = 1 + n_b // hop_length of clip b are exactly 0.  The chain: |STFT|^2 at n_fft 2048, Slaney
+    mel filter bank (128 bands, 0 .. 11 025 Hz), 10 log10(max(1e-10, .)), clamped from below to the clip's own maximum - 80,
+    orthonormal DCT-II along the bands.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
+    pad_mode="reflect"); None: the rows are full."""
+    _mfcc_args("mfcc", n_mfcc, hop_length)
+    w = _rows(waves, "mfcc", "waves", MFCC_N_FFT, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    L = lib()
+    ptr(w)                                                # a host tensor is refused before the table is asked for a device
+    table = _mel_table(w.device)
+    ws = torch.empty(L.ast_mfcc_ws_floats(B, n, hop_length), dtype=torch.float32, device=w.device)
+    out = torch.empty((B, n_mfcc, 1 + n // hop_length), dtype=torch.float32, device=w.device)
+    check(L.ast_mfcc_len(ptr(w), B, n, ptr(ns), n_mfcc, hop_length, PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(out), stream()),
+          "ast_mfcc_len")
+    return out
+
+
+def mfcc_distance(generated, reference, n_generated=None, n_reference=None, n_mfcc=13, hop_length=256, pad_mode="constant"):
+    """generated (B, n), reference (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the mean over t < min(T_g, T_r) of
+    ||mfcc(generated)[b, :, t] - mfcc(reference)[b, :, t]||_2 (evaluation_style_transfer.py:99-109; the defaults are its call).
+    The clips of a pair keep their own lengths: nothing is truncated, each is clamped by its own maximum.  Equal clips score
+    exactly 0."""
+    _mfcc_args("mfcc_distance", n_mfcc, hop_length)
+    g = _rows(generated, "mfcc_distance", "generated", MFCC_N_FFT, pad_mode)
+    r = _rows(reference, "mfcc_distance", "reference", MFCC_N_FFT, pad_mode)
+    B = g.shape[0]
+    if r.shape[0] != B:
+        raise ValueError(f"mfcc_distance: {B} generated and {r.shape[0]} reference rows")
+    ng = len_tensor(n_generated, B, "n_generated", device=True, contiguous=True)
+    nr = len_tensor(n_reference, B, "n_reference", device=True, contiguous=True)
+    L = lib()
+    ptr(g), ptr(r)
+    table = _mel_table(g.device)
+    ws = torch.empty(L.ast_mfcc_distance_ws_floats(B, g.shape[1], r.shape[1], hop_length), dtype=torch.float32, device=g.device)
+    out = torch.empty(B, dtype=torch.float32, device=g.device)
+    check(L.ast_mfcc_distance_len(ptr(g), g.shape[1], ptr(r), r.shape[1], B, ptr(ng), ptr(nr), n_mfcc, hop_length, PAD_MODES[pad_mode],
+                                  ptr(table), ptr(ws), ws.numel(), ptr(out), stream()), "ast_mfcc_distance_len")
     return out

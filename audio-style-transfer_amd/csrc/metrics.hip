@@ -1,7 +1,9 @@
 // Spectrogram metrics of the reference's evaluation scripts for a padded batch of clips of different lengths:
 //   mse_spectrogram (evaluation_reconstruction.py:105-118, after the truncation to a common length at :193-204): n_fft 1024, hop 256
 //   instrumentation_similarity (evaluation_style_transfer.py:111-119): n_fft 2048, hop 512, band energies + Pearson's r
-// Both are |STFT| (librosa.stft defaults: centred frames, periodic Hann) plus a reduction, so the spectrogram never exists in
+//   mfcc_distance (evaluation_style_transfer.py:99-109) and librosa.feature.mfcc itself: n_fft 2048, hop 256 or 512, Slaney mel
+//     filter bank, power_to_db with top_db 80, orthonormal DCT-II -- the section "MFCC" below
+// The first two are |STFT| (librosa.stft defaults: centred frames, periodic Hann) plus a reduction, so the spectrogram never exists in
 // HBM: a workgroup transforms a frame in LDS with the front end's 1024-point network (fft1024.h), reduces what it needs and stores
 // one partial per frame (MSE) or per run of frames (band energies) into the caller's workspace with ordinary stores.  A second
 // small launch sums a clip's partials in a fixed order in double.  No atomics: every output element has one owner and a fixed
@@ -9,6 +11,8 @@
 //
 // Per-clip sample counts are read from the device and clamped, as in the ragged front end (fft.hip); samples behind a clip's
 // end are never read, and per frame the arithmetic does not depend on the batch around the clip.
+#include <math.h>
+
 #include "ast_common.h"
 #include "fft1024.h"
 #include "../../include/ast_hip.h"
@@ -195,6 +199,185 @@ __global__ __launch_bounds__(256) void pearson_rows_kernel(const float* __restri
   }
 }
 
+// ---- MFCC: librosa.feature.mfcc(y, sr, n_mfcc, hop_length) with every other argument at its default, restated:
+//   S = |STFT|^2 (n_fft 2048), M = W S (Slaney mel filter bank, 128 x 1025), dB = 10 log10(max(1e-10, M)), clamped from below to
+//   the clip's own maximum - 80, mfcc = the first n_mfcc rows of the orthonormal DCT-II along the 128 mel bands.
+// The clamp needs the maximum over the whole clip, hence two passes: the first stores the unclamped dB rows (B, T_max, 128) and
+// one maximum per run of frames, the second takes the clip's maximum, clamps and transforms.
+//
+// The filter bank travels as a sparse table of MEL_WORDS 32-bit words (ast_mel_table, built on the host in double): the first
+// bin of every filter, 129 offsets into the weights, and the weights of the filters one after the other as float bits.  A bin
+// lies inside at most two triangles, so there are never more than 2 x 1025 weights.  What the kernel reads from the table is
+// clamped, so that a wrong table gives wrong numbers, not reads outside the workgroup's arrays.
+constexpr int MEL_N = 128, MEL_W_MAX = 2 * BE_BINS, MEL_WORDS = 2 * MEL_N + 1 + MEL_W_MAX;
+constexpr int MF_RUN = 5;                                // consecutive frames of one clip per workgroup (one maximum per run)
+constexpr int DCT_FRAMES = 32;                           // frames per workgroup of the second pass
+constexpr float TOP_DB = 80.f, AMIN = 1e-10f;            // librosa.power_to_db defaults
+
+// pass 1: run blockIdx.x (frames MF_RUN * run ...) of clip blockIdx.y.  The frame's 2048-point real FFT as in
+// band_energy_runs_kernel; the power of the 1025 bins goes to LDS, then thread j < 128 owns mel band j: it sums its filter's
+// weights x powers over the filter's own bins, ascending, takes the logarithm, stores db[b][t][j] and keeps its maximum.
+// run_max[b][run] = the maximum over the run's frames and the 128 bands (a maximum is exact in any order).
+template <bool REFLECT>
+__global__ __launch_bounds__(256) void mel_db_runs_kernel(const float* __restrict__ waves, int n, const int32_t* __restrict__ n_samples, int hop,
+                                                           const int32_t* __restrict__ mel, int T_max, int n_runs, float* __restrict__ db,
+                                                           float* __restrict__ run_max) {
+  __shared__ float2 buf[2][NFFT];
+  __shared__ float pw[BE_BINS], mw[MEL_W_MAX], red[2];
+  const int run = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int L = clip_count(n_samples, b, REFLECT ? BE_NFFT / 2 + 1 : 1, n);
+  const int T = 1 + L / hop, t0 = run * MF_RUN;
+  if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the first barrier
+  const int t1 = min(t0 + MF_RUN, T);
+  const float* w = waves + (size_t)b * n;
+  int f_lo = 0, f_off = 0, f_n = 0;                      // mel band tid: its first bin, where its weights start, how many
+  if (tid < MEL_N) {
+    f_lo = min(max(mel[tid], 0), BE_BINS);
+    f_off = min(max(mel[MEL_N + tid], 0), MEL_W_MAX);
+    f_n = max(min(min(mel[MEL_N + tid + 1], MEL_W_MAX) - f_off, BE_BINS - f_lo), 0);
+  }
+  for (int i = tid; i < MEL_W_MAX; i += 256) mw[i] = __int_as_float(mel[2 * MEL_N + 1 + i]);   // read behind the loop's first barrier
+  float hann[4][2], tc[4], ts[4], vmax = -INFINITY;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const int j = 2 * (tid + 256 * m);
+    hann[m][0] = 0.5f - 0.5f * cospif(2.f * j / BE_NFFT);
+    hann[m][1] = 0.5f - 0.5f * cospif(2.f * (j + 1) / BE_NFFT);
+    sincospif(-(float)(tid + 256 * m) / NFFT, &ts[m], &tc[m]);
+  }
+  for (int t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int q = tid + 256 * m;
+      const int idx = t * hop + 2 * q - BE_NFFT / 2;
+      buf[0][q] = make_float2(clip_sample<REFLECT>(w, idx, L) * hann[m][0], clip_sample<REFLECT>(w, idx + 1, L) * hann[m][1]);
+    }
+    __syncthreads();
+    const int cur = fft1024_stages(buf, tid);            // = 1; its barriers also stand between the last frame's readers of pw and the writes below
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int k = tid + 256 * m;
+      const float2 z = buf[cur][k], c = buf[cur][(NFFT - k) & (NFFT - 1)];
+      const float er = 0.5f * (z.x + c.x), ei = 0.5f * (z.y - c.y), orr = 0.5f * (z.y + c.y), oi = -0.5f * (z.x - c.x);
+      const float xr = er + (orr * tc[m] - oi * ts[m]), xi = ei + (orr * ts[m] + oi * tc[m]);
+      pw[k] = xr * xr + xi * xi;
+    }
+    if (tid == 0) { const float2 z = buf[cur][0]; pw[NFFT] = (z.x - z.y) * (z.x - z.y); }
+    __syncthreads();
+    if (tid < MEL_N) {
+      float s = 0.f;
+      for (int i = 0; i < f_n; ++i) s += mw[f_off + i] * pw[f_lo + i];
+      const float v = 10.f * log10f(fmaxf(s, AMIN));
+      db[((size_t)b * T_max + t) * MEL_N + tid] = v;
+      vmax = fmaxf(vmax, v);
+    }
+  }
+  vmax = wave_max(vmax);                                  // waves 2 and 3 hold -inf
+  if (tid == 0 || tid == 64) red[tid >> 6] = vmax;
+  __syncthreads();
+  if (tid == 0) run_max[(size_t)b * n_runs + run] = fmaxf(red[0], red[1]);
+}
+
+// the maximum of a clip's `runs` run maxima, to every thread of a 256-thread workgroup (red: 4 floats of LDS of its own)
+__device__ __forceinline__ float clip_max_db(const float* __restrict__ run_max, int runs, float* red) {
+  float m = -INFINITY;
+  for (int r = threadIdx.x; r < runs; r += 256) m = fmaxf(m, run_max[r]);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// cos(pi p / 256), p < 512: every phase of the DCT, k (2 j + 1) reduced mod 512 in integers, so exact to float32 rounding
+__device__ __forceinline__ void dct_cos_table(float* ct) {
+  for (int p = threadIdx.x; p < 512; p += 256) ct[p] = cospif(p / 256.f);
+}
+// coefficient k of the orthonormal DCT-II of one row of 128 values, summed over j ascending
+__device__ __forceinline__ float dct_row(const float* __restrict__ x, const float* __restrict__ ct, int k) {
+  float s = 0.f;
+#pragma unroll 8
+  for (int j = 0; j < MEL_N; ++j) s += x[j] * ct[(k * (2 * j + 1)) & 511];
+  return s * (k ? 0.125f : 0.08838834764831845f);        // sqrt(2 / 128), sqrt(1 / 128)
+}
+
+// pass 2 of mfcc: frames DCT_FRAMES * blockIdx.x ... of clip blockIdx.y -> out[b][k][t], layout (B, n_mfcc, T_max) as librosa's.
+// Thread (tid & 31, tid >> 5) owns frame t0 + (tid & 31) and the coefficients (tid >> 5) + 8 i.  Every element of out is
+// written: frames t >= T_b are exactly 0.
+__global__ __launch_bounds__(256) void mfcc_dct_kernel(const float* __restrict__ db, const float* __restrict__ run_max, int n,
+                                                       const int32_t* __restrict__ n_samples, int lo, int hop, int T_max, int n_runs,
+                                                       int n_mfcc, float* __restrict__ out) {
+  __shared__ float x[DCT_FRAMES][MEL_N + 1], ct[512], red[4];
+  const int t0 = blockIdx.x * DCT_FRAMES, b = blockIdx.y, tid = threadIdx.x;
+  const int T = 1 + clip_count(n_samples, b, lo, n) / hop;
+  const int tl = tid & 31, t = t0 + tl;
+  if (t0 < T) {                                          // uniform over the workgroup
+    const float floor_db = clip_max_db(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
+    dct_cos_table(ct);
+    for (int i = tid; i < DCT_FRAMES * MEL_N; i += 256) {
+      const int r = i >> 7, j = i & (MEL_N - 1);
+      x[r][j] = t0 + r < T ? fmaxf(db[((size_t)b * T_max + t0 + r) * MEL_N + j], floor_db) : 0.f;
+    }
+    __syncthreads();
+  }
+  if (t >= T_max) return;
+  for (int k = tid >> 5; k < n_mfcc; k += 8) out[((size_t)b * n_mfcc + k) * T_max + t] = t < T ? dct_row(x[tl], ct, k) : 0.f;
+}
+
+// pass 2 of mfcc_distance: frames DCT_FRAMES * blockIdx.x ... of pair blockIdx.y, T = min of the two clips' frame counts.
+// The DCT is linear: one transform of the difference of the two clamped rows (each clamped by its OWN clip's maximum over its
+// own full length); both clips pass through the same arithmetic up to there, so equal clips score exactly 0.
+// part[b][t] = the norm over k of frame t's coefficients: thread (tid & 31, tid >> 5) squares its coefficients in turn, thread
+// (tid & 31, 0) adds the eight sums ascending.
+__global__ __launch_bounds__(256) void mfcc_dist_frames_kernel(const float* __restrict__ db_g, const float* __restrict__ max_g, int n_g,
+                                                               const int32_t* __restrict__ len_g, int Tmax_g, int runs_g,
+                                                               const float* __restrict__ db_r, const float* __restrict__ max_r, int n_r,
+                                                               const int32_t* __restrict__ len_r, int Tmax_r, int runs_r, int lo, int hop,
+                                                               int n_mfcc, int P_max, float* __restrict__ part) {
+  __shared__ float x[DCT_FRAMES][MEL_N + 1], ct[512], red[2][4], sq[8][DCT_FRAMES];
+  const int t0 = blockIdx.x * DCT_FRAMES, b = blockIdx.y, tid = threadIdx.x;
+  const int T_g = 1 + clip_count(len_g, b, lo, n_g) / hop, T_r = 1 + clip_count(len_r, b, lo, n_r) / hop;
+  const int T = min(T_g, T_r);
+  if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the first barrier
+  const float floor_g = clip_max_db(max_g + (size_t)b * runs_g, (T_g + MF_RUN - 1) / MF_RUN, red[0]) - TOP_DB;
+  const float floor_r = clip_max_db(max_r + (size_t)b * runs_r, (T_r + MF_RUN - 1) / MF_RUN, red[1]) - TOP_DB;
+  dct_cos_table(ct);
+  for (int i = tid; i < DCT_FRAMES * MEL_N; i += 256) {
+    const int r = i >> 7, j = i & (MEL_N - 1);
+    x[r][j] = t0 + r < T ? fmaxf(db_g[((size_t)b * Tmax_g + t0 + r) * MEL_N + j], floor_g) -
+                               fmaxf(db_r[((size_t)b * Tmax_r + t0 + r) * MEL_N + j], floor_r) : 0.f;
+  }
+  __syncthreads();
+  const int tl = tid & 31;
+  float s = 0.f;
+  for (int k = tid >> 5; k < n_mfcc; k += 8) { const float c = dct_row(x[tl], ct, k); s += c * c; }
+  sq[tid >> 5][tl] = s;
+  __syncthreads();
+  if (tid < DCT_FRAMES && t0 + tid < T) {
+    float tot = sq[0][tid];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) tot += sq[i][tid];
+    part[(size_t)b * P_max + t0 + tid] = sqrtf(tot);
+  }
+}
+
+// out[b] = the mean of the pair's T partials: one wave per pair; lane l sums the partials l, l + 64, ... ascending, lane 0 the
+// 64 lanes ascending, all in double
+__global__ __launch_bounds__(64) void mfcc_dist_finish_kernel(const float* __restrict__ part, int n_g, int n_r, const int32_t* __restrict__ len_g,
+                                                              const int32_t* __restrict__ len_r, int lo, int hop, int P_max,
+                                                              float* __restrict__ out) {
+  __shared__ double lane_sum[64];
+  const int b = blockIdx.x, l = threadIdx.x;
+  const int T = 1 + min(clip_count(len_g, b, lo, n_g), clip_count(len_r, b, lo, n_r)) / hop;
+  double s = 0.0;
+  for (int p = l; p < T; p += 64) s += (double)part[(size_t)b * P_max + p];
+  lane_sum[l] = s;
+  __syncthreads();
+  if (l == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 64; ++i) tot += lane_sum[i];
+    out[b] = (float)(tot / (double)T);
+  }
+}
+
 // host: the row checks both transforms share.  0, or -1 with the message of entry `name` set
 int rows_check(const char* name, int B, int n, int n_fft, int pad_mode) {
   if (B < 1 || B > 65535) AST_FAIL("%s: bad shape (B=%d, 1 .. 65535)", name, B);
@@ -205,6 +388,28 @@ int rows_check(const char* name, int B, int n, int n_fft, int pad_mode) {
     AST_FAIL("%s: reflect padding needs rows of >= %d samples, got %d", name, n_fft / 2 + 1, n);
   return 0;
 }
+// host: what ast_mfcc_len and ast_mfcc_distance_len both refuse
+int mfcc_check(const char* name, int n_mfcc, int hop, const int32_t* mel_table) {
+  if (!mel_table) AST_FAIL("%s: null mel table (ast_mel_table fills one)", name);
+  if (n_mfcc < 1 || n_mfcc > MEL_N) AST_FAIL("%s: bad n_mfcc %d (1 .. %d)", name, n_mfcc, MEL_N);
+  if (hop != 256 && hop != 512) AST_FAIL("%s: bad hop %d (256 or 512)", name, hop);
+  return 0;
+}
+int mfcc_frames(int n, int hop) { return 1 + n / hop; }
+int mfcc_runs(int n, int hop) { return (mfcc_frames(n, hop) + MF_RUN - 1) / MF_RUN; }
+// floats of the dB rows and the run maxima of one batch
+long mfcc_pass1_floats(int B, int n, int hop) { return (long)B * ((long)mfcc_frames(n, hop) * MEL_N + mfcc_runs(n, hop)); }
+void mel_db_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel, float* db,
+                   float* run_max, hipStream_t s) {
+  const int T_max = mfcc_frames(n, hop), n_runs = mfcc_runs(n, hop);
+  if (pad_mode == AST_PAD_REFLECT)
+    hipLaunchKernelGGL(mel_db_runs_kernel<true>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, hop, mel, T_max, n_runs, db, run_max);
+  else
+    hipLaunchKernelGGL(mel_db_runs_kernel<false>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, hop, mel, T_max, n_runs, db, run_max);
+}
+// Slaney's mel scale (librosa.hz_to_mel, htk=False): linear below 1 kHz, logarithmic above
+double hz_to_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + log(f / 1000.0) / (log(6.4) / 27.0); }
+double mel_to_hz(double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
 }  // namespace
 
 extern "C" long ast_spec_mse_ws_floats(int B, int n_orig, int n_gen) {
@@ -260,6 +465,98 @@ extern "C" int ast_pearson_rows(const float* a, const float* b, int B, int n, fl
   if (!a || !b || !out) AST_FAIL("ast_pearson_rows: null pointer");
   if (B < 1 || n < 2 || (long long)B * n > 0x7fffffffll) AST_FAIL("ast_pearson_rows: bad shape (B=%d n=%d)", B, n);
   hipLaunchKernelGGL(pearson_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, b, n, out);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- MFCC entries
+extern "C" int ast_mfcc_run_frames(void) { return MF_RUN; }
+extern "C" int ast_mel_table_words(void) { return MEL_WORDS; }
+
+extern "C" int ast_mel_table(int sample_rate, int32_t* table) {
+  if (!table) AST_FAIL("ast_mel_table: null pointer");
+  if (sample_rate < 1) AST_FAIL("ast_mel_table: bad sample rate %d", sample_rate);
+  const double fmax = 0.5 * sample_rate, mel_max = hz_to_mel(fmax);
+  double mel_f[MEL_N + 2];
+  for (int i = 0; i < MEL_N + 2; ++i) mel_f[i] = mel_to_hz(mel_max * i / (MEL_N + 1));
+  mel_f[MEL_N + 1] = fmax;
+  memset(table, 0, sizeof(int32_t) * MEL_WORDS);
+  int off = 0;
+  for (int i = 0; i < MEL_N; ++i) {
+    int first = -1, count = 0;
+    for (int k = 0; k < BE_BINS; ++k) {
+      const double f = k * fmax / (BE_BINS - 1);
+      const double lower = (f - mel_f[i]) / (mel_f[i + 1] - mel_f[i]), upper = (mel_f[i + 2] - f) / (mel_f[i + 2] - mel_f[i + 1]);
+      const double wgt = std::max(0.0, std::min(lower, upper)) * 2.0 / (mel_f[i + 2] - mel_f[i]);
+      if (!(wgt > 0.0)) {
+        if (first >= 0) break;                           // a triangle: its bins are consecutive
+        continue;
+      }
+      if (first < 0) first = k;
+      if (off + count >= MEL_W_MAX) AST_FAIL("ast_mel_table: more than %d weights at %d Hz", MEL_W_MAX, sample_rate);
+      const float wf = (float)wgt;
+      memcpy(&table[2 * MEL_N + 1 + off + count], &wf, sizeof(float));
+      ++count;
+    }
+    if (count == 0)
+      AST_FAIL("ast_mel_table: mel band %d holds no bin of the 2048-point transform at %d Hz (the bands are narrower than a bin)", i, sample_rate);
+    table[i] = first;
+    table[MEL_N + i] = off;
+    off += count;
+  }
+  table[2 * MEL_N] = off;
+  return 0;
+}
+
+extern "C" long ast_mfcc_ws_floats(int B, int n, int hop) {
+  if (B < 1 || n < 1 || (hop != 256 && hop != 512)) return 0;
+  return mfcc_pass1_floats(B, n, hop);
+}
+
+extern "C" long ast_mfcc_distance_ws_floats(int B, int n_gen, int n_ref, int hop) {
+  if (B < 1 || n_gen < 1 || n_ref < 1 || (hop != 256 && hop != 512)) return 0;
+  return mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * mfcc_frames(std::min(n_gen, n_ref), hop);
+}
+
+extern "C" int ast_mfcc_len(const float* waves, int B, int n, const int32_t* n_samples, int n_mfcc, int hop, int pad_mode,
+                            const int32_t* mel_table, float* ws, long ws_floats, float* out, void* stream) {
+  if (!waves || !out) AST_FAIL("ast_mfcc_len: null pointer");
+  if (mfcc_check("ast_mfcc_len", n_mfcc, hop, mel_table) || rows_check("ast_mfcc_len", B, n, BE_NFFT, pad_mode)) return -1;
+  const long need = mfcc_pass1_floats(B, n, hop);
+  if (!ws || ws_floats < need) AST_FAIL("ast_mfcc_len: workspace of %ld floats needed, got %ld", need, ws ? ws_floats : 0L);
+  hipStream_t s = (hipStream_t)stream;
+  const int T_max = mfcc_frames(n, hop), n_runs = mfcc_runs(n, hop);
+  float* run_max = ws + (size_t)B * T_max * MEL_N;
+  mel_db_launch(waves, B, n, n_samples, hop, pad_mode, mel_table, ws, run_max, s);
+  hipLaunchKernelGGL(mfcc_dct_kernel, dim3((T_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
+                     n_samples, pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1, hop, T_max, n_runs, n_mfcc, out);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_mfcc_distance_len(const float* generated, int n_gen, const float* reference, int n_ref, int B, const int32_t* len_gen,
+                                     const int32_t* len_ref, int n_mfcc, int hop, int pad_mode, const int32_t* mel_table, float* ws,
+                                     long ws_floats, float* out, void* stream) {
+  const char* me = "ast_mfcc_distance_len";
+  if (!generated || !reference || !out) AST_FAIL("%s: null pointer", me);
+  if (mfcc_check(me, n_mfcc, hop, mel_table) || rows_check(me, B, n_gen, BE_NFFT, pad_mode) || rows_check(me, B, n_ref, BE_NFFT, pad_mode)) return -1;
+  const int P_max = mfcc_frames(std::min(n_gen, n_ref), hop);
+  const long need = mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * P_max;
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  hipStream_t s = (hipStream_t)stream;
+  const int Tg = mfcc_frames(n_gen, hop), Tr = mfcc_frames(n_ref, hop), runs_g = mfcc_runs(n_gen, hop), runs_r = mfcc_runs(n_ref, hop);
+  float* db_g = ws;
+  float* max_g = db_g + (size_t)B * Tg * MEL_N;
+  float* db_r = max_g + (size_t)B * runs_g;
+  float* max_r = db_r + (size_t)B * Tr * MEL_N;
+  float* part = max_r + (size_t)B * runs_r;
+  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  mel_db_launch(generated, B, n_gen, len_gen, hop, pad_mode, mel_table, db_g, max_g, s);
+  mel_db_launch(reference, B, n_ref, len_ref, hop, pad_mode, mel_table, db_r, max_r, s);
+  hipLaunchKernelGGL(mfcc_dist_frames_kernel, dim3((P_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)db_g,
+                     (const float*)max_g, n_gen, len_gen, Tg, runs_g, (const float*)db_r, (const float*)max_r, n_ref, len_ref, Tr, runs_r, lo, hop,
+                     n_mfcc, P_max, part);
+  hipLaunchKernelGGL(mfcc_dist_finish_kernel, dim3(B), dim3(64), 0, s, (const float*)part, n_gen, n_ref, len_gen, len_ref, lo, hop, P_max, out);
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -501,6 +501,36 @@ int ast_band_energy_run_frames(void);
 /* Pearson's r of rows a[b], b[b] of n >= 2 values in double (evaluation_style_transfer.py:117-119: pearsonr, nan -> 0.0):
  * out[b] is exactly 0 where r is not finite (a constant row).  a, b (B, n), out (B,) f32. */
 int ast_pearson_rows(const float* a, const float* b, int B, int n, float* out, void* stream);
+/* MFCC: librosa.feature.mfcc(y, sr, n_mfcc, hop_length) with every other argument at its default, restated (csrc/metrics.hip):
+ * S = |STFT|^2 at n_fft 2048, M = W S with the Slaney mel filter bank (128 bands, fmin 0, fmax sr / 2, Slaney normalisation),
+ * dB = 10 log10(max(1e-10, M)) clamped from below to the clip's own maximum - 80, then the first n_mfcc rows of the orthonormal
+ * DCT-II along the bands.  Two passes, because the clamp needs the maximum over the whole clip: the first stores the dB rows
+ * (B, T_max, 128) and one maximum per run of frames into ws, the second clamps and transforms.  The spectrogram is never stored.
+ * hop is 256 or 512 (the reference's two values), n_mfcc 1 .. 128; counts, pad modes, clamps and limits as above, n_fft = 2048.
+ *
+ * The filter bank is a table of `ast_mel_table_words` 32-bit words that the host function below fills for a sample rate (in
+ * double, no device needed); the caller copies it to the device once, outside any capture, and passes the device pointer as
+ * mel_table.  Layout: 128 first bins, 129 offsets into the weights, then the bands' weights in turn as float bits (never more
+ * than 2 x 1025: a bin lies inside at most two triangles).  A rate at which a band holds no bin is refused. */
+int ast_mel_table_words(void);
+int ast_mel_table(int sample_rate, int32_t* table);
+/* frames per run of the first pass (what the workspace counts below are built on) */
+int ast_mfcc_run_frames(void);
+/* librosa.feature.mfcc for a padded batch (evaluation_style_transfer.py:101-102, :122-123): waves (B, n) f32 ->
+ * out (B, n_mfcc, T_max) f32, T_max = 1 + n / hop, librosa's layout; frames t >= T_b = 1 + n_b / hop of clip b are exactly 0.
+ * ws: B * (T_max * 128 + ceil(T_max / run)) floats. */
+long ast_mfcc_ws_floats(int B, int n, int hop);
+int ast_mfcc_len(const float* waves, int B, int n, const int32_t* n_samples, int n_mfcc, int hop, int pad_mode, const int32_t* mel_table,
+                 float* ws, long ws_floats, float* out, void* stream);
+/* mfcc_distance (evaluation_style_transfer.py:99-109): generated (B, n_gen), reference (B, n_ref) f32 -> out (B,) f32, the mean
+ * over t < T = min(T_gen_b, T_ref_b) of the Euclidean norm of the difference of the two clips' coefficient columns.  Each clip
+ * keeps its own length (nothing is truncated) and is clamped by its own maximum.  The DCT is taken of the difference of the
+ * clamped dB rows; both clips pass through the same arithmetic, so equal clips score exactly 0.  One partial per frame, summed in
+ * a fixed order in double.  ws: the two batches' counts above plus B * (1 + min(n_gen, n_ref) / hop) floats. */
+long ast_mfcc_distance_ws_floats(int B, int n_gen, int n_ref, int hop);
+int ast_mfcc_distance_len(const float* generated, int n_gen, const float* reference, int n_ref, int B, const int32_t* len_gen,
+                          const int32_t* len_ref, int n_mfcc, int hop, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats,
+                          float* out, void* stream);
 
 /* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
  * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
