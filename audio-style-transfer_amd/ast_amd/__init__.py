@@ -13,6 +13,7 @@ from .new_decoder import Decoder, compute_comprehensive_loss  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401
 from .losses import infoNCE_loss, margin_loss, adversarial_loss, disentanglement_loss  # noqa: F401
 from .metrics import mse_spectrogram, band_energy, instrumentation_similarity, mfcc, mfcc_distance  # noqa: F401
+from .metrics import estimate_tuning, chroma_stft, chroma_distance, chroma_similarity, pitch_mean, pitch_correlation  # noqa: F401
 
 
 class deterministic:

@@ -174,6 +174,20 @@ _SIGS = {
     "ast_mfcc_len": ([vp, i32, i32, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
     "ast_mfcc_distance_ws_floats": ([i32, i32, i32, i32], C.c_long),
     "ast_mfcc_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
+    # chroma and pitch metrics for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
+    "ast_chroma_run_frames": ([], i32),
+    "ast_pitch_band": ([i32, C.POINTER(i32), C.POINTER(i32)], i32),
+    "ast_tuning_debug_words": ([], i32),
+    "ast_tuning_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_tuning_len": ([vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp], i32),
+    "ast_chroma_len": ([vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp], i32),
+    "ast_chroma_distance_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_chroma_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
+    "ast_chroma_similarity_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_chroma_similarity_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
+    "ast_pitch_mean_len": ([vp, i32, i32, vp, vp, i32, i32, vp, vp], i32),
+    "ast_pitch_correlation_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_pitch_correlation_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

@@ -165,7 +165,7 @@ class StyleTransferSession:
         return self._replay(key, run, inputs)
 
     def transfer_and_score(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, reference: torch.Tensor = None,
-                           n_reference: torch.Tensor = None, mfcc: bool = False, **transfer_kw):
+                           n_reference: torch.Tensor = None, mfcc: bool = False, chroma: bool = False, **transfer_kw):
         """`transfer` and the spectrogram metrics of its output (ast_amd.metrics) as one graph under a key of its own
         -> (waveforms, stft sections, lengths, scores); the first three are what `transfer` returns for the same arguments
         (transfer_kw: stft_stats, cqt_stats, sample_rate).
@@ -179,6 +179,9 @@ class StyleTransferSession:
         mfcc=True (needs a reference): scores["mfcc_distance"] (B,) as well, the output over lengths[b] samples against the
         reference over n_reference[b], at 13 coefficients and hop 256 (evaluation_style_transfer.py:99-109), in the same graph,
         which then has a key of its own; the default leaves the call as it was.
+        chroma=True (needs no reference): scores["chroma_similarity"] (B,) as well, the output over lengths[b] samples against the
+        input at 22 050 Hz over its own count, at n_fft 1024, hop 256 (evaluation_style_transfer.py:80-96), in the same graph,
+        again under a key of its own.
         All with pad_mode="constant".  No length is read on the host."""
         from . import metrics as M
         key, inputs, frames, native, k = self._transfer_plan(waves, class_emb, n_samples, transfer_kw.pop("stft_stats", None),
@@ -210,15 +213,21 @@ class StyleTransferSession:
                 scores += (M.instrumentation_similarity(out_wave, ref[0], lengths, ref[1]),)
                 if mfcc:
                     scores += (M.mfcc_distance(out_wave, ref[0], lengths, ref[1]),)
+            if chroma:
+                scores += (M.chroma_similarity(out_wave, wav, lengths, n),)
             return (out_wave, sections, lengths) + scores
 
         key += ("score", None if reference is None else tuple(reference.shape))
         if mfcc:
             key += ("mfcc",)
+        if chroma:
+            key += ("chroma",)
         res = self._replay(key, run, inputs + extra)
         scores = {"mse_spectrogram": res[3]}
         if reference is not None:
             scores["instrumentation_similarity"] = res[4]
             if mfcc:
                 scores["mfcc_distance"] = res[5]
+        if chroma:
+            scores["chroma_similarity"] = res[-1]
         return res[0], res[1], res[2], scores

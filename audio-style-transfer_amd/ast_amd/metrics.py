@@ -4,6 +4,8 @@
     instrumentation_similarity evaluation_style_transfer.py:111-119 (band energies + Pearson's r)
 
     mfcc, mfcc_distance        evaluation_style_transfer.py:99-109: librosa.feature.mfcc restated as a formula chain (below)
+    chroma_distance, pitch_correlation   evaluation_reconstruction.py:39-52, 83-103 \  librosa's piptrack, estimate_tuning, filters.chroma
+    chroma_similarity                    evaluation_style_transfer.py:80-96         /  and chroma_stft restated (csrc/chroma.hip, below)
 
 All are |STFT| plus a reduction (csrc/metrics.hip); the spectrogram is never stored and no length is read on the host, so the
 calls can be captured in a graph (StyleTransferSession.transfer_and_score).  `librosa.stft`'s documented defaults are restated,
@@ -145,4 +147,135 @@ def mfcc_distance(generated, reference, n_generated=None, n_reference=None, n_mf
     out = torch.empty(B, dtype=torch.float32, device=g.device)
     check(L.ast_mfcc_distance_len(ptr(g), g.shape[1], ptr(r), r.shape[1], B, ptr(ng), ptr(nr), n_mfcc, hop_length, PAD_MODES[pad_mode],
                                   ptr(table), ptr(ws), ws.numel(), ptr(out), stream()), "ast_mfcc_distance_len")
+    return out
+
+
+# ---- chroma and pitch (csrc/chroma.hip): librosa.piptrack, estimate_tuning, filters.chroma and feature.chroma_stft restated as a
+# formula chain ("Chroma and pitch"); parity with librosa's own output is unpinned
+CHROMA_SETTINGS = ((2048, 512), (1024, 256))             # librosa's defaults (chroma_distance, pitch_correlation); chroma_similarity's call
+N_CHROMA = 12
+
+
+def _chroma_setting(name, n_fft, hop_length):
+    if (n_fft, hop_length) not in CHROMA_SETTINGS:
+        raise ValueError(f"{name}: (n_fft, hop_length) must be (2048, 512) or (1024, 256), the evaluation scripts' two settings, "
+                         f"got ({n_fft!r}, {hop_length!r})")
+
+
+def _pair(name, a, what_a, b, what_b, n_a, n_b, n_fft, pad_mode):
+    """the rows and counts of a pair of batches, checked"""
+    a, b = _rows(a, name, what_a, n_fft, pad_mode), _rows(b, name, what_b, n_fft, pad_mode)
+    B = a.shape[0]
+    if b.shape[0] != B:
+        raise ValueError(f"{name}: {B} {what_a} and {b.shape[0]} {what_b} rows")
+    return a, b, B, len_tensor(n_a, B, "n_" + what_a, device=True, contiguous=True), len_tensor(n_b, B, "n_" + what_b, device=True, contiguous=True)
+
+
+def _tuning(w, ns, n_fft, hop_length, pad_mode, debug=None):
+    B, n = w.shape
+    L = lib()
+    ws = torch.empty(L.ast_tuning_ws_floats(B, n, n_fft), dtype=torch.float32, device=w.device)
+    out = torch.empty(B, dtype=torch.float32, device=w.device)
+    check(L.ast_tuning_len(ptr(w), B, n, ptr(ns), None, n, n_fft, hop_length, PAD_MODES[pad_mode], ptr(ws), ws.numel(), ptr(out), ptr(debug),
+                           stream()), "ast_tuning_len")
+    return out
+
+
+def estimate_tuning(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B,) f32: what librosa.estimate_tuning is documented to give as
+    librosa.feature.chroma_stft calls it on clip b's own n_b samples -- piptrack's peaks of |STFT|^2 between 150 and 4000 Hz, those
+    at or above the median magnitude, the fullest 0.01-semitone bin of their deviations from equal temperament; in [-0.5, 0.5),
+    0.0 for a clip without a peak.  (n_fft, hop_length): (2048, 512) or (1024, 256).  n_samples: int32 (B,) device tensor, clamped
+    on the device to [1, n] ([n_fft / 2 + 1, n] with pad_mode="reflect"); None: the rows are full."""
+    _chroma_setting("estimate_tuning", n_fft, hop_length)
+    w = _rows(waves, "estimate_tuning", "waves", n_fft, pad_mode)
+    return _tuning(w, len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True), n_fft, hop_length, pad_mode)
+
+
+def tuning_debug(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode="constant"):
+    """estimate_tuning and what it counted -> (tuning (B,), candidates (B,) int32, kept (B,) int32, thr (B,) f32, histogram (B, 100) int32);
+    for the tests"""
+    _chroma_setting("tuning_debug", n_fft, hop_length)
+    w = _rows(waves, "tuning_debug", "waves", n_fft, pad_mode)
+    ns = len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
+    ptr(w)
+    dbg = torch.zeros((w.shape[0], lib().ast_tuning_debug_words()), dtype=torch.int32, device=w.device)
+    tuning = _tuning(w, ns, n_fft, hop_length, pad_mode, dbg)
+    return tuning, dbg[:, 0], dbg[:, 1], dbg[:, 2].contiguous().view(torch.float32), dbg[:, 3:]
+
+
+def chroma_stft(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode="constant", tuning=None):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, 12, T_max) f32, T_max = 1 + n // hop_length: what
+    librosa.feature.chroma_stft(y, sr=22050, n_fft, hop_length) is documented to compute for clip b over its own n_b samples, in
+    librosa's layout (row 0 = C, row 9 = A); frames t >= T_b are exactly 0.  The chain: |STFT|^2, librosa.filters.chroma's bank
+    (Gaussians a semitone apart around the clip's tuning, unit L2 norm per bin, octave weighting around 5 octaves above 27.5 Hz),
+    each frame divided by its maximum.  tuning: (B,) f32 device tensor in semitones, or None: estimate_tuning's.
+    (n_fft, hop_length): (2048, 512) or (1024, 256).  n_samples as above."""
+    _chroma_setting("chroma_stft", n_fft, hop_length)
+    w = _rows(waves, "chroma_stft", "waves", n_fft, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    if tuning is None:
+        tuning = _tuning(w, ns, n_fft, hop_length, pad_mode)
+    elif not (torch.is_tensor(tuning) and tuning.dtype == torch.float32 and tuple(tuning.shape) == (B,)):
+        raise ValueError(f"chroma_stft: tuning must be a float32 tensor of shape ({B},)")
+    out = torch.empty((B, N_CHROMA, 1 + n // hop_length), dtype=torch.float32, device=w.device)
+    check(lib().ast_chroma_len(ptr(w), B, n, ptr(ns), None, n, n_fft, hop_length, PAD_MODES[pad_mode], ptr(tuning.contiguous()), ptr(out),
+                               stream()), "ast_chroma_len")
+    return out
+
+
+def chroma_distance(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
+    """original (B, n), generated (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the mean over the frames of
+    ||chroma_stft(original)[b, :, t] - chroma_stft(generated)[b, :, t]||_2 at n_fft 2048, hop 512 (evaluation_reconstruction.py:39-52),
+    both clips cut to L_b = min(n_original[b], n_generated[b]) samples first (:193-204), each with its own tuning.  Equal clips score
+    exactly 0."""
+    a, g, B, na, ng = _pair("chroma_distance", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
+    L = lib()
+    ptr(a), ptr(g)
+    ws = torch.empty(L.ast_chroma_distance_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(L.ast_chroma_distance_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
+                                    ptr(out), stream()), "ast_chroma_distance_len")
+    return out
+
+
+def chroma_similarity(generated, original, n_generated=None, n_original=None, pad_mode="constant"):
+    """generated (B, n), original (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the mean over the 12 chroma rows of Pearson's r
+    between chroma_stft(generated)[b, c] and chroma_stft(original)[b, c] at n_fft 1024, hop 256 over the frames t < min(T_g, T_o)
+    (evaluation_style_transfer.py:80-96): the "content kept?" score.  The clips keep their own lengths; rows whose r is not finite
+    are left out, and a pair without a finite row scores exactly 0.0."""
+    g, a, B, ng, na = _pair("chroma_similarity", generated, "generated", original, "original", n_generated, n_original, 1024, pad_mode)
+    L = lib()
+    ptr(g), ptr(a)
+    ws = torch.empty(L.ast_chroma_similarity_ws_floats(B, g.shape[1], a.shape[1]), dtype=torch.float32, device=g.device)
+    out = torch.empty(B, dtype=torch.float32, device=g.device)
+    check(L.ast_chroma_similarity_len(ptr(g), g.shape[1], ptr(a), a.shape[1], B, ptr(ng), ptr(na), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
+                                      ptr(out), stream()), "ast_chroma_similarity_len")
+    return out
+
+
+def pitch_mean(waves, n_samples=None, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, T_max) f32, T_max = 1 + n // 512: np.mean(librosa.piptrack(y, sr)[0], axis=0)
+    as documented, for clip b over its own n_b samples (n_fft 2048, hop 512; the interpolated peaks of |STFT| between 150 and
+    4000 Hz above a tenth of the frame's maximum, averaged over all 1025 bins); frames t >= T_b are exactly 0."""
+    w = _rows(waves, "pitch_mean", "waves", 2048, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    out = torch.empty((B, 1 + n // 512), dtype=torch.float32, device=w.device)
+    check(lib().ast_pitch_mean_len(ptr(w), B, n, ptr(ns), None, n, PAD_MODES[pad_mode], ptr(out), stream()), "ast_pitch_mean_len")
+    return out
+
+
+def pitch_correlation(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
+    """original (B, n), generated (B, m) f32 device rows at 22 050 Hz -> (B,) f32: Pearson's r of the two clips' pitch_mean over
+    the frames (evaluation_reconstruction.py:83-103), both clips cut to L_b = min(n_original[b], n_generated[b]) samples first
+    (:193-204); exactly 0.0 where r is not finite or there are fewer than 2 frames."""
+    a, g, B, na, ng = _pair("pitch_correlation", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
+    L = lib()
+    ptr(a), ptr(g)
+    ws = torch.empty(L.ast_pitch_correlation_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(L.ast_pitch_correlation_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
+                                      ptr(out), stream()), "ast_pitch_correlation_len")
     return out

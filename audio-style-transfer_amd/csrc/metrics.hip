@@ -11,31 +11,12 @@
 //
 // Per-clip sample counts are read from the device and clamped, as in the ragged front end (fft.hip); samples behind a clip's
 // end are never read, and per frame the arithmetic does not depend on the batch around the clip.
-#include <math.h>
-
-#include "ast_common.h"
-#include "fft1024.h"
-#include "../../include/ast_hip.h"
+#include "spec_common.h"
 
 namespace {
 constexpr int MSE_HOP = 256, MSE_BINS = 513;             // N_FFT / HOP_LENGTH of evaluation_reconstruction.py
 constexpr int BE_NFFT = 2048, BE_HOP = 512, BE_BINS = 1025;   // librosa.stft defaults
 constexpr int BE_RUN = 5;                                // consecutive frames of one clip per workgroup (one partial per run)
-
-__device__ __forceinline__ int clip_count(const int32_t* __restrict__ n, int b, int lo, int n_max) {
-  return n ? min(max(n[b], lo), n_max) : n_max;
-}
-// sample `idx` of a clip of L samples under the pad mode; reflect needs -L < idx < 2 L - 1, which L > n_fft / 2 gives
-template <bool REFLECT>
-__device__ __forceinline__ float clip_sample(const float* __restrict__ w, int idx, int L) {
-  if (REFLECT) {
-    if (idx < 0) idx = -idx;
-    if (idx >= L) idx = 2 * (L - 1) - idx;
-    return w[idx];
-  }
-  return (idx >= 0 && idx < L) ? w[idx] : 0.f;
-}
-__device__ __forceinline__ float cabs2(float x, float y) { return sqrtf(x * x + y * y); }
 
 // ---- mse_spectrogram: frames 2 blockIdx.x and 2 blockIdx.x + 1 of pair blockIdx.y.  One FFT per frame pair on average: two
 // consecutive frames of ONE clip ride in the real and the imaginary part of a transform and are split by Hermitian symmetry,
@@ -168,15 +149,6 @@ __global__ __launch_bounds__(256) void band_energy_finish_kernel(const float* __
   energy[(size_t)b * BE_BINS + f] = (float)s;
 }
 
-// block-wide sum in double in a fixed order: thread-strided partial sums, then thread 0 adds the 256 of them ascending
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) { double s = 0.0; for (int i = 0; i < 256; ++i) s += red[i]; red[256] = s; }
-  __syncthreads();
-  return red[256];
-}
 // Pearson's r of rows a[b], b[b] of n values (scipy.stats.pearsonr: means, centred sums, ratio), exactly 0 where it is not
 // finite (the reference's nan -> 0.0)
 __global__ __launch_bounds__(256) void pearson_rows_kernel(const float* __restrict__ a, const float* __restrict__ b, int n,
@@ -378,16 +350,6 @@ __global__ __launch_bounds__(64) void mfcc_dist_finish_kernel(const float* __res
   }
 }
 
-// host: the row checks both transforms share.  0, or -1 with the message of entry `name` set
-int rows_check(const char* name, int B, int n, int n_fft, int pad_mode) {
-  if (B < 1 || B > 65535) AST_FAIL("%s: bad shape (B=%d, 1 .. 65535)", name, B);
-  if (pad_mode != AST_PAD_CONSTANT && pad_mode != AST_PAD_REFLECT) AST_FAIL("%s: bad pad_mode %d (0 constant, 1 reflect)", name, pad_mode);
-  if (n < 1) AST_FAIL("%s: bad shape (n=%d)", name, n);
-  if (n > 0x7fffffff - 2 * n_fft) AST_FAIL("%s: row too long (n=%d: n + 2 n_fft must stay below 2^31)", name, n);
-  if (pad_mode == AST_PAD_REFLECT && n < n_fft / 2 + 1)
-    AST_FAIL("%s: reflect padding needs rows of >= %d samples, got %d", name, n_fft / 2 + 1, n);
-  return 0;
-}
 // host: what ast_mfcc_len and ast_mfcc_distance_len both refuse
 int mfcc_check(const char* name, int n_mfcc, int hop, const int32_t* mel_table) {
   if (!mel_table) AST_FAIL("%s: null mel table (ast_mel_table fills one)", name);

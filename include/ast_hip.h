@@ -532,6 +532,56 @@ int ast_mfcc_distance_len(const float* generated, int n_gen, const float* refere
                           const int32_t* len_ref, int n_mfcc, int hop, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats,
                           float* out, void* stream);
 
+/* ---- chroma and pitch metrics of the evaluation scripts for a padded batch (csrc/chroma.hip).  librosa's documented chain restated
+ * ("Chroma and pitch"; parity with librosa's own output is unpinned), sr = 22 050, frames, windows, pad modes, counts and
+ * clamps as above.  Two settings: (n_fft 2048, hop 512), librosa's defaults, and (1024, 256); anything else is refused.
+ * A clip may be cut to a partner's count first (evaluation_reconstruction.py:193-204): n_cut is the partner's int32 (B,) DEVICE
+ * array or NULL, cut_max its row width, and clip b counts min(clamped n_samples[b], clamped n_cut[b]) samples; without a partner
+ * pass n_cut = NULL and cut_max = n.  No float atomics; the only atomics are integer counters in LDS; results are bit-reproducible
+ * and row b does not depend on the other rows. */
+/* frames per run (one workgroup) of the frame passes; the candidate band of librosa.piptrack's defaults, 150 <= k sr / n_fft < 4000 */
+int ast_chroma_run_frames(void);
+int ast_pitch_band(int n_fft, int* k_lo, int* k_hi);
+/* librosa.estimate_tuning as librosa.feature.chroma_stft calls it (S = |STFT|^2, bins_per_octave 12, resolution 0.01): piptrack's
+ * peaks of the band (pitch and mag, [b][t][band], 0 where there is no peak) go to ws, 2 * B * T_max * band floats; then one
+ * workgroup per clip takes the exact median of the mags by radix selection on their bit patterns (the mean of the two middle
+ * values for an even count), and the 100-bin histogram (np.histogram over linspace(-0.5, 0.5, 101)) of the deviations
+ * frac(12 log2(pitch / 27.5)), wrapped to [-0.5, 0.5), of the peaks with mag >= median.  tuning[b] = -0.5 + 0.01 * argmax, the
+ * lowest index winning ties; 0.0 without a peak.  debug: NULL, or B * ast_tuning_debug_words() int32 on the device, per clip the
+ * count of peaks, the count kept, the median as float bits and the 100 histogram counts (for the tests). */
+int ast_tuning_debug_words(void);
+long ast_tuning_ws_floats(int B, int n, int n_fft);
+int ast_tuning_len(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int n_fft, int hop,
+                   int pad_mode, float* ws, long ws_floats, float* tuning, int32_t* debug, void* stream);
+/* librosa.feature.chroma_stft (evaluation_reconstruction.py:41-42, evaluation_style_transfer.py:82-83): waves (B, n) f32, tuning
+ * (B,) f32 on the device (ast_tuning_len's, or the caller's) -> out (B, 12, T_max) f32, T_max = 1 + n / hop, librosa's layout, row
+ * 0 = C; frames t >= T_b are exactly 0.  raw = W |STFT|^2 with librosa.filters.chroma(sr, n_fft, tuning[b])'s defaults built per
+ * thread in registers, each frame divided by its maximum over the 12 rows unless that is below float32 tiny. */
+int ast_chroma_len(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int n_fft, int hop,
+                   int pad_mode, const float* tuning, float* out, void* stream);
+/* chroma_distance (evaluation_reconstruction.py:39-52, on the audio truncated to a common length at :193-204), n_fft 2048, hop 512:
+ * out[b] = mean over the T(L_b) frames of ||chroma_o[:, t] - chroma_g[:, t]||_2, each clip with its own estimated tuning.  Both
+ * clips pass through the same arithmetic, so equal clips score exactly 0.
+ * ws: the peaks of the wider batch + 2 B tunings + both chromas (ast_chroma_distance_ws_floats). */
+long ast_chroma_distance_ws_floats(int B, int n_orig, int n_gen);
+int ast_chroma_distance_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
+                            const int32_t* len_gen, int pad_mode, float* ws, long ws_floats, float* out, void* stream);
+/* chroma_similarity (evaluation_style_transfer.py:80-96), n_fft 1024, hop 256: each clip keeps its own length; Pearson's r in
+ * double over the frames t < min(T_g, T_o) for each of the 12 rows, out[b] = the mean of the finite ones, exactly 0 if none. */
+long ast_chroma_similarity_ws_floats(int B, int n_gen, int n_orig);
+int ast_chroma_similarity_len(const float* generated, int n_gen, const float* original, int n_orig, int B, const int32_t* len_gen,
+                              const int32_t* len_orig, int pad_mode, float* ws, long ws_floats, float* out, void* stream);
+/* np.mean(librosa.piptrack(y, sr)[0], axis=0) (evaluation_reconstruction.py:85-90), n_fft 2048, hop 512, S = |STFT|:
+ * out[b][t] = (1 / 1025) sum_k pitch[k][t], (B, T_max) f32, summed in a fixed order; frames t >= T_b are exactly 0. */
+int ast_pitch_mean_len(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int pad_mode,
+                       float* out, void* stream);
+/* pitch_correlation (evaluation_reconstruction.py:83-103, on the audio truncated to a common length at :193-204): Pearson's r in
+ * double of the two clips' mean pitches over the T(L_b) frames, exactly 0 where r is not finite or T < 2.
+ * ws: B * (T_max(n_orig) + T_max(n_gen)) floats. */
+long ast_pitch_correlation_ws_floats(int B, int n_orig, int n_gen);
+int ast_pitch_correlation_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
+                              const int32_t* len_gen, int pad_mode, float* ws, long ws_floats, float* out, void* stream);
+
 /* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
  * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
  * workgroup's partial into a slot indexed by its workgroup / tile / row id (plain stores; every slot is written on every call, so
