@@ -174,6 +174,19 @@ _SIGS = {
     "ast_mfcc_len": ([vp, i32, i32, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
     "ast_mfcc_distance_ws_floats": ([i32, i32, i32, i32], C.c_long),
     "ast_mfcc_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
+    # onsets and self-similarity for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
+    "ast_onset_tile_frames": ([], i32),
+    "ast_recurrence_chunk_frames": ([], i32),
+    "ast_onset_strength_ws_floats": ([i32, i32], C.c_long),
+    "ast_onset_strength_len": ([vp, i32, i32, vp, i32, vp, vp, C.c_long, vp, vp], i32),
+    "ast_onset_detect_ws_floats": ([i32, i32], C.c_long),
+    "ast_onset_detect_len": ([vp, i32, i32, vp, i32, vp, vp, C.c_long, vp, vp], i32),
+    "ast_onset_accuracy_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_onset_accuracy_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, C.c_long, vp, vp], i32),
+    "ast_recurrence_ws_floats": ([i32, i32], C.c_long),
+    "ast_recurrence_len": ([vp, i32, i32, vp, i32, vp, vp, C.c_long, vp, vp, vp], i32),
+    "ast_self_similarity_distance_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_self_similarity_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, C.c_long, vp, vp], i32),
     # chroma and pitch metrics for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
     "ast_chroma_run_frames": ([], i32),
     "ast_pitch_band": ([i32, C.POINTER(i32), C.POINTER(i32)], i32),

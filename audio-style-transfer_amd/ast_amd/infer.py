@@ -165,7 +165,8 @@ class StyleTransferSession:
         return self._replay(key, run, inputs)
 
     def transfer_and_score(self, waves: torch.Tensor, class_emb: torch.Tensor, n_samples: torch.Tensor = None, reference: torch.Tensor = None,
-                           n_reference: torch.Tensor = None, mfcc: bool = False, chroma: bool = False, **transfer_kw):
+                           n_reference: torch.Tensor = None, mfcc: bool = False, chroma: bool = False, onsets: bool = False,
+                           self_similarity: bool = False, **transfer_kw):
         """`transfer` and the spectrogram metrics of its output (ast_amd.metrics) as one graph under a key of its own
         -> (waveforms, stft sections, lengths, scores); the first three are what `transfer` returns for the same arguments
         (transfer_kw: stft_stats, cqt_stats, sample_rate).
@@ -182,6 +183,10 @@ class StyleTransferSession:
         chroma=True (needs no reference): scores["chroma_similarity"] (B,) as well, the output over lengths[b] samples against the
         input at 22 050 Hz over its own count, at n_fft 1024, hop 256 (evaluation_style_transfer.py:80-96), in the same graph,
         again under a key of its own.
+        onsets=True (needs no reference): scores["onset_accuracy"] (B,) as well, the output against the input under the length rule of
+        scores["mse_spectrogram"] (evaluation_reconstruction.py:54-81).
+        self_similarity=True (needs a reference): scores["self_similarity_distance"] (B,) as well, the output over lengths[b] samples
+        against the reference over n_reference[b] (evaluation_style_transfer.py:121-133).  Each flag adds its own word to the key.
         All with pad_mode="constant".  No length is read on the host."""
         from . import metrics as M
         key, inputs, frames, native, k = self._transfer_plan(waves, class_emb, n_samples, transfer_kw.pop("stft_stats", None),
@@ -194,6 +199,8 @@ class StyleTransferSession:
                 raise ValueError("transfer_and_score: n_reference without reference")
             if mfcc:
                 raise ValueError("transfer_and_score: mfcc=True scores against a reference, and none was given")
+            if self_similarity:
+                raise ValueError("transfer_and_score: self_similarity=True scores against a reference, and none was given")
             extra = []
         else:
             if not torch.is_tensor(reference) or reference.dim() != 2 or reference.dtype != torch.float32 or reference.shape[0] != B or \
@@ -215,6 +222,10 @@ class StyleTransferSession:
                     scores += (M.mfcc_distance(out_wave, ref[0], lengths, ref[1]),)
             if chroma:
                 scores += (M.chroma_similarity(out_wave, wav, lengths, n),)
+            if onsets:
+                scores += (M.onset_accuracy(wav, out_wave, n, lengths),)
+            if self_similarity:
+                scores += (M.self_similarity_distance(out_wave, ref[0], lengths, ref[1]),)
             return (out_wave, sections, lengths) + scores
 
         key += ("score", None if reference is None else tuple(reference.shape))
@@ -222,12 +233,14 @@ class StyleTransferSession:
             key += ("mfcc",)
         if chroma:
             key += ("chroma",)
+        if onsets:
+            key += ("onsets",)
+        if self_similarity:
+            key += ("self_similarity",)
         res = self._replay(key, run, inputs + extra)
-        scores = {"mse_spectrogram": res[3]}
+        names = ["mse_spectrogram"]                                  # in the order `run` appends them
         if reference is not None:
-            scores["instrumentation_similarity"] = res[4]
-            if mfcc:
-                scores["mfcc_distance"] = res[5]
-        if chroma:
-            scores["chroma_similarity"] = res[-1]
-        return res[0], res[1], res[2], scores
+            names += ["instrumentation_similarity"] + (["mfcc_distance"] if mfcc else [])
+        names += [name for flag, name in ((chroma, "chroma_similarity"), (onsets, "onset_accuracy"),
+                                          (self_similarity, "self_similarity_distance")) if flag]
+        return res[0], res[1], res[2], dict(zip(names, res[3:]))

@@ -6,6 +6,8 @@
     mfcc, mfcc_distance        evaluation_style_transfer.py:99-109: librosa.feature.mfcc restated as a formula chain (below)
     chroma_distance, pitch_correlation   evaluation_reconstruction.py:39-52, 83-103 \  librosa's piptrack, estimate_tuning, filters.chroma
     chroma_similarity                    evaluation_style_transfer.py:80-96         /  and chroma_stft restated (csrc/chroma.hip, below)
+    onset_accuracy             evaluation_reconstruction.py:54-81: librosa.onset.onset_detect restated, then the F1 score (below)
+    self_similarity_distance   evaluation_style_transfer.py:121-133: librosa.segment.recurrence_matrix(mfcc.T) restated (below)
 
 All are |STFT| plus a reduction (csrc/metrics.hip); the spectrogram is never stored and no length is read on the host, so the
 calls can be captured in a graph (StyleTransferSession.transfer_and_score).  `librosa.stft`'s documented defaults are restated,
@@ -278,4 +280,101 @@ def pitch_correlation(original, generated, n_original=None, n_generated=None, pa
     out = torch.empty(B, dtype=torch.float32, device=a.device)
     check(L.ast_pitch_correlation_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
                                       ptr(out), stream()), "ast_pitch_correlation_len")
+    return out
+
+
+# ---- onsets and self-similarity (csrc/metrics.hip): librosa.onset.onset_detect and librosa.segment.recurrence_matrix at their
+# defaults restated as a formula chain ("Onsets and self-similarity"); parity with librosa's own output is unpinned
+ONSET_HOP, SS_N_MFCC = 512, 20                            # librosa's default hop_length and n_mfcc
+
+
+def _onset_one(name, entry, ws_entry, waves, n_samples, pad_mode, out_dtype):
+    w = _rows(waves, name, "waves", MFCC_N_FFT, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    L = lib()
+    ptr(w)
+    table = _mel_table(w.device)
+    ws = torch.empty(getattr(L, ws_entry)(B, n), dtype=torch.float32, device=w.device)
+    out = torch.empty((B, 1 + n // ONSET_HOP), dtype=out_dtype, device=w.device)
+    check(getattr(L, entry)(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(out), stream()), entry)
+    return out
+
+
+def onset_strength(waves, n_samples=None, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, T_max) f32, T_max = 1 + n // 512: the onset strength envelope that
+    librosa.onset.onset_detect(y, sr=22050) is documented to build for clip b over its own n_b samples -- with dB the clamped mel rows
+    of `mfcc` at hop 512, e[t] = the mean over the 128 bands of max(0, dB[m, t-2] - dB[m, t-3]) for 3 <= t < T_b; exactly 0 for t < 3
+    and for t >= T_b = 1 + n_b // 512.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
+    pad_mode="reflect"); None: the rows are full."""
+    return _onset_one("onset_strength", "ast_onset_strength_len", "ast_onset_strength_ws_floats", waves, n_samples, pad_mode, torch.float32)
+
+
+def onset_detect(waves, n_samples=None, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, T_max) int32 mask: 1 where librosa.onset.onset_detect(y, sr=22050) at its
+    defaults is documented to report frame t of clip b as an onset, 0 elsewhere and for t >= T_b.  A mask, not an index list: the
+    shape does not depend on the data, so the call can be captured; `mask[b].nonzero()` gives librosa's frames.  No onsets where
+    the envelope is all zero or not all finite; else the normalised envelope's peak picking with pre_max 1, post_max 1, pre_avg 4,
+    post_avg 5, delta 0.07, wait 1 (0.03 sr // hop and so on at 22 050 Hz and hop 512).  n_samples as for onset_strength."""
+    return _onset_one("onset_detect", "ast_onset_detect_len", "ast_onset_detect_ws_floats", waves, n_samples, pad_mode, torch.int32)
+
+
+def onset_accuracy(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
+    """original (B, n), generated (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the F1 score of the two clips' onset frames
+    (evaluation_reconstruction.py:54-81), both clips cut to L_b = min(n_original[b], n_generated[b]) samples first (:193-204):
+    1.0 if neither has an onset, 0.0 if exactly one has none, else 2 |O and G| / (|O| + |G|).  Equal clips score exactly 1."""
+    a, g, B, na, ng = _pair("onset_accuracy", original, "original", generated, "generated", n_original, n_generated, MFCC_N_FFT, pad_mode)
+    L = lib()
+    ptr(a), ptr(g)
+    table = _mel_table(a.device)
+    ws = torch.empty(L.ast_onset_accuracy_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(L.ast_onset_accuracy_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(table), ptr(ws),
+                                   ws.numel(), ptr(out), stream()), "ast_onset_accuracy_len")
+    return out
+
+
+def _recurrence(name, waves, n_samples, pad_mode, debug):
+    w = _rows(waves, name, "waves", MFCC_N_FFT, pad_mode)
+    B, n = w.shape
+    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
+    L = lib()
+    ptr(w)
+    table = _mel_table(w.device)
+    ws = torch.empty(L.ast_recurrence_ws_floats(B, n), dtype=torch.float32, device=w.device)
+    R = torch.empty((B, SS_N_MFCC, SS_N_MFCC), dtype=torch.int32, device=w.device)
+    d2 = torch.empty((B, SS_N_MFCC, SS_N_MFCC), dtype=torch.float32, device=w.device) if debug else None
+    check(L.ast_recurrence_len(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(R), ptr(d2), stream()),
+          "ast_recurrence_len")
+    return R, d2
+
+
+def recurrence_matrix(waves, n_samples=None, pad_mode="constant"):
+    """waves (B, n) f32 device rows at 22 050 Hz -> (B, 20, 20) int32: what librosa.segment.recurrence_matrix(mfcc.T) at its defaults
+    is documented to give for mfcc = librosa.feature.mfcc(y, sr=22050) of clip b over its own n_b samples
+    (evaluation_style_transfer.py:122-126).  The reference hands over the transpose, so the matrix's points are the 20 coefficient
+    rows, each a vector over the clip's T_b frames, and the result is 20 x 20 whatever the clip's length.  Orientation: R[b, i, j] = 1
+    iff coefficient row i is one of the kept neighbours of row j -- of the 12 nearest other rows of j (ties to the lower index)
+    those at distance exactly 0 are dropped and of the rest the 10 nearest are kept.  Column j holds at most 10 ones, the diagonal
+    is 0, the matrix is not symmetrised.  A T x T matrix over time frames is not offered.  n_samples as for onset_strength."""
+    return _recurrence("recurrence_matrix", waves, n_samples, pad_mode, False)[0]
+
+
+def recurrence_debug(waves, n_samples=None, pad_mode="constant"):
+    """recurrence_matrix and the squared distances it ranked -> (R (B, 20, 20) int32, dist2 (B, 20, 20) f32); for the tests"""
+    return _recurrence("recurrence_debug", waves, n_samples, pad_mode, True)
+
+
+def self_similarity_distance(a, b, n_a=None, n_b=None, pad_mode="constant"):
+    """a (B, n), b (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the mean over the 400 cells of
+    |recurrence_matrix(a)[i] - recurrence_matrix(b)[i]| (evaluation_style_transfer.py:121-133), a multiple of 1 / 400.  Each clip is
+    taken at its own length.  Equal clips score exactly 0."""
+    a, b, B, na, nb = _pair("self_similarity_distance", a, "a", b, "b", n_a, n_b, MFCC_N_FFT, pad_mode)
+    L = lib()
+    ptr(a), ptr(b)
+    table = _mel_table(a.device)
+    ws = torch.empty(L.ast_self_similarity_distance_ws_floats(B, a.shape[1], b.shape[1]), dtype=torch.float32, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(L.ast_self_similarity_distance_len(ptr(a), a.shape[1], ptr(b), b.shape[1], B, ptr(na), ptr(nb), PAD_MODES[pad_mode], ptr(table),
+                                             ptr(ws), ws.numel(), ptr(out), stream()), "ast_self_similarity_distance_len")
     return out

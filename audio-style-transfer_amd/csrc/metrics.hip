@@ -522,3 +522,386 @@ extern "C" int ast_mfcc_distance_len(const float* generated, int n_gen, const fl
   AST_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- onsets and self-similarity: the last two of the evaluation scripts' eight metrics.
+//   onset_accuracy (evaluation_reconstruction.py:54-81): librosa.onset.onset_detect(y, sr) with every other argument at its default,
+//     restated: the mel dB rows of the MFCC's first pass at hop 512, clamped; onset strength e[t] = mean over the 128 bands of
+//     max(0, dB[m][t-2] - dB[m][t-3]) for 3 <= t < T_b (lag 1, max_size 1, centred: shifted by 1 + n_fft / (2 hop) = 3 frames and
+//     cut to T_b), 0 before; x = (e - min e) / (max e - min e + float32 tiny); frame n is a detection if x[n] is the maximum of its
+//     pre_max / post_max window and x[n] >= the mean of its pre_avg / post_avg window + 0.07, windows cut at the clip's ends; of the
+//     detections those further than `wait` behind the last kept one are kept.  Then the F1 score of the two clips' onset sets.
+//   self_similarity_distance (evaluation_style_transfer.py:121-133): librosa.segment.recurrence_matrix(mfcc.T) at its defaults.  The
+//     reference hands over the transpose, so the matrix's "frames" are the 20 coefficient rows, each a vector over the clip's T_b
+//     time frames: 20 x 20 whatever the length.  D[i][j] = ||c_i - c_j||; per column j the 12 nearest other rows, those at
+//     distance exactly 0 dropped, of the rest the 10 nearest kept: R[i][j] = 1.  The score is the mean of |R_a - R_b|.
+// The rules of the kernels above hold: no atomics, one owner and a fixed order per output, counts clamped on the device.
+namespace {
+constexpr int ON_SR = 22050, ON_HOP = BE_HOP;            // librosa's defaults: sr, hop_length
+constexpr int ON_SHIFT = 1 + BE_NFFT / (2 * ON_HOP);     // 3: lag + the frames `center=True` pads on the left
+constexpr int ON_PRE_MAX = (3 * ON_SR / 100) / ON_HOP;   // 0.03 sr // hop = 1   \  librosa.onset.onset_detect's peak_pick arguments
+constexpr int ON_POST_MAX = (0 * ON_SR) / ON_HOP + 1;    // 0.00 sr // hop + 1 = 1 |  at 22 050 Hz and hop 512; the window of frame n is
+constexpr int ON_PRE_AVG = (ON_SR / 10) / ON_HOP;        // 0.10 sr // hop = 4     |  n - pre .. n + post - 1
+constexpr int ON_POST_AVG = (ON_SR / 10) / ON_HOP + 1;   // 0.10 sr // hop + 1 = 5 |
+constexpr int ON_WAIT = (3 * ON_SR / 100) / ON_HOP;      // 0.03 sr // hop = 1    /
+constexpr float ON_DELTA = 0.07f, F32_TINY = 1.17549435e-38f;
+static_assert(ON_WAIT == 1, "the pick kernel's greedy pass keeps every second frame of a run of detections: wait = 1");
+constexpr int ENV_TILE = 8;                              // frames of one clip per workgroup of the envelope kernel
+constexpr int SS_MFCC = 20;                              // librosa.feature.mfcc's default n_mfcc: the rows of the recurrence matrix
+constexpr int SS_WIDTH = 1;                              // recurrence_matrix's default width
+constexpr int ceil_sqrt(int v) { int r = 0; while (r * r < v) ++r; return r; }
+constexpr int SS_K = 2 * ceil_sqrt(SS_MFCC - 2 * SS_WIDTH + 1);                                           // 10 links kept per column
+constexpr int SS_NN = SS_MFCC - 1 < SS_K + 2 * SS_WIDTH ? SS_MFCC - 1 : SS_K + 2 * SS_WIDTH;           // 12 neighbours asked for
+constexpr int SS_PAIRS = SS_MFCC * (SS_MFCC - 1) / 2, SS_CELLS = SS_MFCC * SS_MFCC;                      // 190, 400
+constexpr int CD_CHUNK = 16;                             // frames per workgroup of the coefficient-distance kernel
+
+// L[b] = the common length of pair b (evaluation_reconstruction.py:193-204): the minimum of the two clamped counts.  Both clips of
+// the pair then take L as their count; it lies inside both clamps already.
+__global__ __launch_bounds__(64) void pair_counts_kernel(const int32_t* __restrict__ len_a, int n_a, const int32_t* __restrict__ len_g, int n_g,
+                                                         int lo, int B, int32_t* __restrict__ L) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b < B) L[b] = min(clip_count(len_a, b, lo, n_a), clip_count(len_g, b, lo, n_g));
+}
+
+// onset strength: frames ENV_TILE * blockIdx.x ... of clip blockIdx.y.  The tile's dB rows and one halo row go to LDS, clamped by the
+// clip's own maximum; thread (tid >> 5, tid & 31) sums frame tid >> 5's rectified differences of the bands l, l + 32, l + 64, l + 96
+// in turn, thread (f, 0) the 32 sums ascending.  Every element of env is written: 0 for t < 3 and for t >= T_b.  tile_min / tile_max:
+// over the tile's frames t < T_b; the maximum is +inf if one of them is not finite.
+__global__ __launch_bounds__(256) void onset_env_kernel(const float* __restrict__ db, const float* __restrict__ run_max, int n,
+                                                        const int32_t* __restrict__ n_samples, int lo, int T_max, int n_runs, int n_tiles,
+                                                        float* __restrict__ env, float* __restrict__ tile_min, float* __restrict__ tile_max) {
+  __shared__ float x[ENV_TILE + 1][MEL_N], ps[ENV_TILE][32], ev[ENV_TILE], red[4];
+  const int t0 = blockIdx.x * ENV_TILE, b = blockIdx.y, tid = threadIdx.x;
+  const int T = 1 + clip_count(n_samples, b, lo, n) / ON_HOP;
+  if (t0 >= T) {                                         // uniform over the workgroup: nothing of the clip is read
+    if (tid < ENV_TILE && t0 + tid < T_max) env[(size_t)b * T_max + t0 + tid] = 0.f;
+    return;
+  }
+  const float floor_db = clip_max_db(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
+  for (int i = tid; i < (ENV_TILE + 1) * MEL_N; i += 256) {
+    const int r = i >> 7, j = i & (MEL_N - 1), u = t0 - ON_SHIFT + r;          // row r holds dB frame u
+    x[r][j] = (u >= 0 && u < T) ? fmaxf(db[((size_t)b * T_max + u) * MEL_N + j], floor_db) : 0.f;
+  }
+  __syncthreads();
+  const int f = tid >> 5, l = tid & 31;
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < MEL_N / 32; ++q) s += fmaxf(x[f + 1][l + 32 * q] - x[f][l + 32 * q], 0.f);
+  ps[f][l] = s;
+  __syncthreads();
+  if (tid < ENV_TILE) {
+    float tot = ps[tid][0];
+    for (int i = 1; i < 32; ++i) tot += ps[tid][i];
+    const int t = t0 + tid;
+    const float e = (t >= ON_SHIFT && t < T) ? tot * (1.f / MEL_N) : 0.f;
+    ev[tid] = e;
+    if (t < T_max) env[(size_t)b * T_max + t] = e;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = 0; i < ENV_TILE && t0 + i < T; ++i) {
+      mn = fminf(mn, ev[i]);
+      mx = ev[i] < INFINITY ? fmaxf(mx, ev[i]) : INFINITY;                      // not finite (NaN as well): +inf
+    }
+    tile_min[(size_t)b * n_tiles + blockIdx.x] = mn;
+    tile_max[(size_t)b * n_tiles + blockIdx.x] = mx;
+  }
+}
+
+// the first frame of the run of consecutive detections that holds frame c0 + pos; bits: the detections of the 256 frames from
+// c0 on; carry: the first frame of the run that reaches frame c0 - 1, or -1
+__device__ __forceinline__ int run_start(const unsigned long long* bits, int pos, int c0, int carry) {
+  int w = pos >> 6;
+  unsigned long long z = ~bits[w] & ((1ull << (pos & 63)) - 1ull);
+  for (;;) {
+    if (z) return c0 + 64 * w + 64 - __clzll((long long)z);
+    if (--w < 0) return carry >= 0 ? carry : c0;
+    z = ~bits[w];
+  }
+}
+
+// peak picking: clip blockIdx.x, one workgroup.  Minimum and maximum over the clip's tiles, then 256 consecutive frames at a time:
+// every thread tests its frame's two conditions on the normalised envelope (window sums in ascending order), a ballot turns the
+// detections into bit masks, and the greedy pass with wait = 1 needs no walk: inside a run of consecutive detections the frames at
+// even distance from the run's first are kept.  Every element of mask is written, 0 for t >= T_b.
+__global__ __launch_bounds__(256) void onset_pick_kernel(const float* __restrict__ env, const float* __restrict__ tile_min,
+                                                         const float* __restrict__ tile_max, int n, const int32_t* __restrict__ n_samples,
+                                                         int lo, int T_max, int n_tiles, int32_t* __restrict__ mask) {
+  __shared__ float red[2][4];
+  __shared__ unsigned long long bits[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int T = 1 + clip_count(n_samples, b, lo, n) / ON_HOP;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = tid; i < (T + ENV_TILE - 1) / ENV_TILE; i += 256) {
+    mn = fminf(mn, tile_min[(size_t)b * n_tiles + i]);
+    mx = fmaxf(mx, tile_max[(size_t)b * n_tiles + i]);
+  }
+  mn = -wave_max(-mn);
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+  __syncthreads();
+  mn = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+  mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  const bool any = mx > 0.f && mx < INFINITY;            // e >= 0: all zero means max e = 0; not all finite means max e = +inf
+  const float den = (mx - mn) + F32_TINY;
+  const float* e = env + (size_t)b * T_max;
+  int carry = -1;
+  for (int c0 = 0; c0 < T_max; c0 += 256) {
+    const int t = c0 + tid;
+    bool det = false;
+    if (any && t < T) {
+      const float xt = (e[t] - mn) / den;
+      bool top = true;
+      for (int k = max(t - ON_PRE_MAX, 0); k < min(t + ON_POST_MAX, T); ++k) top = top && xt >= (e[k] - mn) / den;
+      const int k0 = max(t - ON_PRE_AVG, 0), k1 = min(t + ON_POST_AVG, T);
+      float s = 0.f;
+      for (int k = k0; k < k1; ++k) s += (e[k] - mn) / den;
+      det = top && xt >= s / (float)(k1 - k0) + ON_DELTA;
+    }
+    const unsigned long long m = __ballot(det);
+    if ((tid & 63) == 0) bits[tid >> 6] = m;
+    __syncthreads();
+    if (t < T_max) mask[(size_t)b * T_max + t] = det && ((t - run_start(bits, tid, c0, carry)) & 1) == 0;
+    carry = (bits[3] >> 63) ? run_start(bits, 255, c0, carry) : -1;
+    __syncthreads();
+  }
+}
+
+// onset_accuracy's F1: pair blockIdx.x over its T(L_b) frames; integer counts, thread 0 adds the 256 partial counts
+__global__ __launch_bounds__(256) void onset_f1_kernel(const int32_t* __restrict__ mask_o, int To_max, const int32_t* __restrict__ mask_g, int Tg_max,
+                                                       const int32_t* __restrict__ L, float* __restrict__ out) {
+  __shared__ int cnt[3][256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int T = min(1 + L[b] / ON_HOP, min(To_max, Tg_max));
+  int o = 0, g = 0, both = 0;
+  for (int t = tid; t < T; t += 256) {
+    const int mo = mask_o[(size_t)b * To_max + t] != 0, mg = mask_g[(size_t)b * Tg_max + t] != 0;
+    o += mo; g += mg; both += mo & mg;
+  }
+  cnt[0][tid] = o; cnt[1][tid] = g; cnt[2][tid] = both;
+  __syncthreads();
+  if (tid == 0) {
+    int O = 0, G = 0, I = 0;
+    for (int i = 0; i < 256; ++i) { O += cnt[0][i]; G += cnt[1][i]; I += cnt[2][i]; }
+    out[b] = (O == 0 && G == 0) ? 1.f : (O == 0 || G == 0) ? 0.f : (float)((double)(2 * I) / (double)(O + G));
+  }
+}
+
+// pair p < 190 of coefficient rows -> (i, j), i < j, counted row by row
+__device__ __forceinline__ void ss_pair(int p, int& i, int& j) {
+  i = 0;
+  while (p >= SS_MFCC - 1 - i) { p -= SS_MFCC - 1 - i; ++i; }
+  j = i + 1 + p;
+}
+
+// squared distances between the 20 coefficient rows: frames CD_CHUNK * blockIdx.x ... of clip blockIdx.y through an LDS tile;
+// thread p < 190 owns pair p and sums (c_i[t] - c_j[t])^2 over the chunk's frames t < T_b ascending -- the differences themselves,
+// no Gram matrix: c_0 is near -1000 and the other rows are small.  part[b][chunk][p]
+__global__ __launch_bounds__(256) void coef_dist_chunks_kernel(const float* __restrict__ c, int n, const int32_t* __restrict__ n_samples, int lo,
+                                                               int T_max, int n_chunks, float* __restrict__ part) {
+  __shared__ float x[SS_MFCC][CD_CHUNK + 1];
+  const int t0 = blockIdx.x * CD_CHUNK, b = blockIdx.y, tid = threadIdx.x;
+  const int T = 1 + clip_count(n_samples, b, lo, n) / ON_HOP;
+  if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the barrier
+  const int len = min(CD_CHUNK, T - t0);
+  for (int i = tid; i < SS_MFCC * CD_CHUNK; i += 256) {
+    const int r = i / CD_CHUNK, j = i % CD_CHUNK;
+    x[r][j] = j < len ? c[((size_t)b * SS_MFCC + r) * T_max + t0 + j] : 0.f;
+  }
+  __syncthreads();
+  if (tid < SS_PAIRS) {
+    int i, j;
+    ss_pair(tid, i, j);
+    float s = 0.f;
+    for (int t = 0; t < len; ++t) { const float d = x[i][t] - x[j][t]; s += d * d; }
+    part[((size_t)b * n_chunks + blockIdx.x) * SS_PAIRS + tid] = s;
+  }
+}
+
+// recurrence matrix of clip blockIdx.x: thread p < 190 sums pair p's chunks ascending in double and rounds the sum to float once (what
+// d2_out shows is what is ranked); then thread (i, j) ranks row i among the 19 candidates of column j by squared distance, ties
+// to the lower index: i is kept if it is among the SS_NN nearest,
+// its distance is not exactly 0, and fewer than SS_K nonzero candidates come before it.  R[b][i][j], diagonal 0, not symmetrised.
+// d2_out: NULL, or (B, 20, 20) f32 squared distances (for the tests)
+__global__ __launch_bounds__(256) void recurrence_kernel(const float* __restrict__ part, int n, const int32_t* __restrict__ n_samples, int lo,
+                                                         int n_chunks, int32_t* __restrict__ R, float* __restrict__ d2_out) {
+  __shared__ float d2[SS_MFCC][SS_MFCC];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int T = 1 + clip_count(n_samples, b, lo, n) / ON_HOP;
+  if (tid < SS_PAIRS) {
+    int i, j;
+    ss_pair(tid, i, j);
+    double s = 0.0;
+    for (int ch = 0; ch < (T + CD_CHUNK - 1) / CD_CHUNK; ++ch) s += (double)part[((size_t)b * n_chunks + ch) * SS_PAIRS + tid];
+    d2[i][j] = (float)s;
+    d2[j][i] = (float)s;
+  }
+  if (tid < SS_MFCC) d2[tid][tid] = 0.f;
+  __syncthreads();
+  for (int cell = tid; cell < SS_CELLS; cell += 256) {
+    const int i = cell / SS_MFCC, j = cell % SS_MFCC;
+    const float d = d2[i][j];
+    int rank = 0, nonzero_before = 0;
+    for (int k = 0; k < SS_MFCC; ++k) {
+      if (k == i || k == j) continue;
+      const float dk = d2[k][j];
+      const bool before = dk < d || (dk == d && k < i);
+      rank += before;
+      nonzero_before += before && dk != 0.f;
+    }
+    R[(size_t)b * SS_CELLS + cell] = i != j && rank < SS_NN && d != 0.f && nonzero_before < SS_K;
+    if (d2_out) d2_out[(size_t)b * SS_CELLS + cell] = d;
+  }
+}
+
+// out[b] = the mean over the 400 cells of |R_a - R_b|: one wave per pair, integer counts, lane 0 adds the 64 lanes
+__global__ __launch_bounds__(64) void self_sim_finish_kernel(const int32_t* __restrict__ Ra, const int32_t* __restrict__ Rb, float* __restrict__ out) {
+  __shared__ int cnt[64];
+  const int b = blockIdx.x, l = threadIdx.x;
+  int s = 0;
+  for (int i = l; i < SS_CELLS; i += 64) s += abs(Ra[(size_t)b * SS_CELLS + i] - Rb[(size_t)b * SS_CELLS + i]);
+  cnt[l] = s;
+  __syncthreads();
+  if (l == 0) {
+    int tot = 0;
+    for (int i = 0; i < 64; ++i) tot += cnt[i];
+    out[b] = (float)((double)tot / (double)SS_CELLS);
+  }
+}
+
+// host: sizes and launches the onset and recurrence entries share
+int on_tiles(int n) { return (mfcc_frames(n, ON_HOP) + ENV_TILE - 1) / ENV_TILE; }
+int ss_chunks(int n) { return (mfcc_frames(n, ON_HOP) + CD_CHUNK - 1) / CD_CHUNK; }
+long on_strength_floats(int B, int n) { return mfcc_pass1_floats(B, n, ON_HOP) + 2L * B * on_tiles(n); }
+long on_detect_floats(int B, int n) { return on_strength_floats(B, n) + (long)B * mfcc_frames(n, ON_HOP); }
+long ss_rec_floats(int B, int n) {
+  return mfcc_pass1_floats(B, n, ON_HOP) + (long)B * SS_MFCC * mfcc_frames(n, ON_HOP) + (long)B * ss_chunks(n) * SS_PAIRS;
+}
+// mel dB rows -> envelope (-> mask, unless it is null) of one batch; ws: on_strength_floats(B, n)
+void onset_launch(const float* waves, int B, int n, const int32_t* counts, int pad_mode, const int32_t* mel, float* ws, float* env,
+                  int32_t* mask, hipStream_t s) {
+  const int T_max = mfcc_frames(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_tiles = on_tiles(n);
+  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  float* run_max = ws + (size_t)B * T_max * MEL_N;
+  float* tile_min = run_max + (size_t)B * n_runs;
+  float* tile_max = tile_min + (size_t)B * n_tiles;
+  mel_db_launch(waves, B, n, counts, ON_HOP, pad_mode, mel, ws, run_max, s);
+  hipLaunchKernelGGL(onset_env_kernel, dim3(n_tiles, B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n, counts, lo, T_max, n_runs,
+                     n_tiles, env, tile_min, tile_max);
+  if (mask)
+    hipLaunchKernelGGL(onset_pick_kernel, dim3(B), dim3(256), 0, s, (const float*)env, (const float*)tile_min, (const float*)tile_max, n, counts,
+                       lo, T_max, n_tiles, mask);
+}
+// mel dB rows -> 20 coefficients -> squared distances -> R of one batch; ws: ss_rec_floats(B, n)
+void recurrence_launch(const float* waves, int B, int n, const int32_t* counts, int pad_mode, const int32_t* mel, float* ws, int32_t* R,
+                       float* d2, hipStream_t s) {
+  const int T_max = mfcc_frames(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_chunks = ss_chunks(n);
+  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  float* run_max = ws + (size_t)B * T_max * MEL_N;
+  float* coef = run_max + (size_t)B * n_runs;
+  float* part = coef + (size_t)B * SS_MFCC * T_max;
+  mel_db_launch(waves, B, n, counts, ON_HOP, pad_mode, mel, ws, run_max, s);
+  hipLaunchKernelGGL(mfcc_dct_kernel, dim3((T_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
+                     counts, lo, ON_HOP, T_max, n_runs, SS_MFCC, coef);
+  hipLaunchKernelGGL(coef_dist_chunks_kernel, dim3(n_chunks, B), dim3(256), 0, s, (const float*)coef, n, counts, lo, T_max, n_chunks, part);
+  hipLaunchKernelGGL(recurrence_kernel, dim3(B), dim3(256), 0, s, (const float*)part, n, counts, lo, n_chunks, R, d2);
+}
+int onset_check(const char* name, const void* a, const void* b, const void* out, const int32_t* mel) {
+  if (!a || !b || !out) AST_FAIL("%s: null pointer", name);
+  if (!mel) AST_FAIL("%s: null mel table (ast_mel_table fills one)", name);
+  return 0;
+}
+}  // namespace
+
+extern "C" int ast_onset_tile_frames(void) { return ENV_TILE; }
+extern "C" int ast_recurrence_chunk_frames(void) { return CD_CHUNK; }
+
+extern "C" long ast_onset_strength_ws_floats(int B, int n) { return (B < 1 || n < 1) ? 0 : on_strength_floats(B, n); }
+extern "C" long ast_onset_detect_ws_floats(int B, int n) { return (B < 1 || n < 1) ? 0 : on_detect_floats(B, n); }
+extern "C" long ast_onset_accuracy_ws_floats(int B, int n_orig, int n_gen) {
+  if (B < 1 || n_orig < 1 || n_gen < 1) return 0;
+  return B + on_detect_floats(B, n_orig) + on_detect_floats(B, n_gen) + (long)B * (mfcc_frames(n_orig, ON_HOP) + mfcc_frames(n_gen, ON_HOP));
+}
+extern "C" long ast_recurrence_ws_floats(int B, int n) { return (B < 1 || n < 1) ? 0 : ss_rec_floats(B, n); }
+extern "C" long ast_self_similarity_distance_ws_floats(int B, int n_a, int n_b) {
+  if (B < 1 || n_a < 1 || n_b < 1) return 0;
+  return ss_rec_floats(B, n_a) + ss_rec_floats(B, n_b) + 2L * B * SS_CELLS;
+}
+
+extern "C" int ast_onset_strength_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table,
+                                      float* ws, long ws_floats, float* out, void* stream) {
+  const char* me = "ast_onset_strength_len";
+  if (onset_check(me, waves, waves, out, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
+  const long need = on_strength_floats(B, n);
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  onset_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, out, nullptr, (hipStream_t)stream);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_onset_detect_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table,
+                                    float* ws, long ws_floats, int32_t* mask, void* stream) {
+  const char* me = "ast_onset_detect_len";
+  if (onset_check(me, waves, waves, mask, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
+  const long need = on_detect_floats(B, n);
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  onset_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, ws + on_strength_floats(B, n), mask, (hipStream_t)stream);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_onset_accuracy_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
+                                      const int32_t* len_gen, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats, float* out,
+                                      void* stream) {
+  const char* me = "ast_onset_accuracy_len";
+  if (onset_check(me, original, generated, out, mel_table) || rows_check(me, B, n_orig, BE_NFFT, pad_mode) ||
+      rows_check(me, B, n_gen, BE_NFFT, pad_mode))
+    return -1;
+  const long need = ast_onset_accuracy_ws_floats(B, n_orig, n_gen);
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  hipStream_t s = (hipStream_t)stream;
+  const int To = mfcc_frames(n_orig, ON_HOP), Tg = mfcc_frames(n_gen, ON_HOP);
+  int32_t* L = (int32_t*)ws;                             // the pair's common counts, then the two clips' chains and masks
+  float* ws_o = ws + B;
+  float* env_o = ws_o + on_strength_floats(B, n_orig);
+  float* ws_g = env_o + (size_t)B * To;
+  float* env_g = ws_g + on_strength_floats(B, n_gen);
+  int32_t* mask_o = (int32_t*)(env_g + (size_t)B * Tg);
+  int32_t* mask_g = mask_o + (size_t)B * To;
+  hipLaunchKernelGGL(pair_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, len_orig, n_orig, len_gen, n_gen,
+                     pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1, B, L);
+  onset_launch(original, B, n_orig, L, pad_mode, mel_table, ws_o, env_o, mask_o, s);
+  onset_launch(generated, B, n_gen, L, pad_mode, mel_table, ws_g, env_g, mask_g, s);
+  hipLaunchKernelGGL(onset_f1_kernel, dim3(B), dim3(256), 0, s, (const int32_t*)mask_o, To, (const int32_t*)mask_g, Tg, (const int32_t*)L, out);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_recurrence_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table, float* ws,
+                                  long ws_floats, int32_t* R, float* dist2, void* stream) {
+  const char* me = "ast_recurrence_len";
+  if (onset_check(me, waves, waves, R, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
+  const long need = ss_rec_floats(B, n);
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  recurrence_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, R, dist2, (hipStream_t)stream);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_self_similarity_distance_len(const float* a, int n_a, const float* b, int n_b, int B, const int32_t* len_a,
+                                                const int32_t* len_b, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats,
+                                                float* out, void* stream) {
+  const char* me = "ast_self_similarity_distance_len";
+  if (onset_check(me, a, b, out, mel_table) || rows_check(me, B, n_a, BE_NFFT, pad_mode) || rows_check(me, B, n_b, BE_NFFT, pad_mode)) return -1;
+  const long need = ast_self_similarity_distance_ws_floats(B, n_a, n_b);
+  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws_b = ws + ss_rec_floats(B, n_a);
+  int32_t* Ra = (int32_t*)(ws_b + ss_rec_floats(B, n_b));
+  int32_t* Rb = Ra + (size_t)B * SS_CELLS;
+  recurrence_launch(a, B, n_a, len_a, pad_mode, mel_table, ws, Ra, nullptr, s);
+  recurrence_launch(b, B, n_b, len_b, pad_mode, mel_table, ws_b, Rb, nullptr, s);
+  hipLaunchKernelGGL(self_sim_finish_kernel, dim3(B), dim3(64), 0, s, (const int32_t*)Ra, (const int32_t*)Rb, out);
+  AST_CHECK_LAUNCH();
+  return 0;
+}

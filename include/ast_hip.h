@@ -582,6 +582,53 @@ long ast_pitch_correlation_ws_floats(int B, int n_orig, int n_gen);
 int ast_pitch_correlation_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
                               const int32_t* len_gen, int pad_mode, float* ws, long ws_floats, float* out, void* stream);
 
+/* ---- onsets and self-similarity: the last two of the evaluation scripts' eight metrics (csrc/metrics.hip; DESIGN 7, "Onsets and
+ * self-similarity"; parity with librosa's own output is unpinned).  sr 22 050, n_fft 2048, hop 512; frames, windows, pad modes,
+ * counts, clamps and limits as for the MFCC above, mel_table as there (at 22 050 Hz).  No atomics; results are bit-reproducible and
+ * row b does not depend on the other rows.  Every workspace slot that is read is written first. */
+/* frames per workgroup of the envelope pass and of the coefficient-distance pass (what the workspace counts are built on) */
+int ast_onset_tile_frames(void);
+int ast_recurrence_chunk_frames(void);
+/* librosa.onset.onset_strength as onset_detect calls it (evaluation_reconstruction.py:57-58): waves (B, n) f32 -> out (B, T_max) f32,
+ * T_max = 1 + n / 512.  e[t] = the mean over the 128 mel bands of max(0, dB[m][t-2] - dB[m][t-3]) for 3 <= t < T_b, with dB the
+ * MFCC's clamped mel rows; exactly 0 for t < 3 and for t >= T_b.
+ * ws: the MFCC's first pass at hop 512 + 2 B ceil(T_max / tile) floats (one minimum and one maximum per tile). */
+long ast_onset_strength_ws_floats(int B, int n);
+int ast_onset_strength_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table, float* ws,
+                           long ws_floats, float* out, void* stream);
+/* librosa.onset.onset_detect(y, sr=22050) at its defaults (evaluation_reconstruction.py:57-58), as a mask: mask (B, T_max) int32, 1
+ * where frame t of clip b is an onset, 0 elsewhere and for t >= T_b.  No onsets if the envelope is all zero or not all finite;
+ * else x = (e - min e) / (max e - min e + float32 tiny), frame n is a detection if x[n] >= x[n-1] and
+ * x[n] >= mean(x[n-4 .. n+4]) + 0.07 (the windows cut at the clip's ends; the sizes are 0.03 sr / hop and so on), and walking up a
+ * detection is kept if it lies more than 1 frame behind the last kept one.  ws: ast_onset_strength's + B T_max floats. */
+long ast_onset_detect_ws_floats(int B, int n);
+int ast_onset_detect_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table, float* ws,
+                         long ws_floats, int32_t* mask, void* stream);
+/* onset_accuracy (evaluation_reconstruction.py:54-81, on the audio truncated to a common length at :193-204): both clips cut to
+ * L_b = min of the two clamped counts; O, G their onset sets; out[b] = 1 if both are empty, 0 if exactly one is, else
+ * 2 |O and G| / (|O| + |G|), the F1 score that sklearn.metrics.f1_score gives at :78 (total_frames there only sizes the arrays).
+ * Both clips pass through the same arithmetic.  ws: B + both clips' ast_onset_detect counts + B (T_max_orig + T_max_gen) floats. */
+long ast_onset_accuracy_ws_floats(int B, int n_orig, int n_gen);
+int ast_onset_accuracy_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
+                           const int32_t* len_gen, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats, float* out,
+                           void* stream);
+/* librosa.segment.recurrence_matrix(mfcc.T) at its defaults (evaluation_style_transfer.py:122-126): the reference hands over the
+ * transpose, so the matrix's points are the 20 coefficient rows c_i of librosa.feature.mfcc(y, sr) (hop 512), each a vector over
+ * the clip's own T_b frames.  D[i][j] = ||c_i - c_j||_2, summed as squared differences (no Gram matrix), per chunk of frames in
+ * f32 and over the chunks ascending in double, rounded to f32 once: dist2 shows exactly what is ranked.  Per column j: the min(19, k + 2) = 12 nearest other rows, ties to the lower index;
+ * those at distance exactly 0 dropped; of the rest the k = 2 ceil(sqrt(19)) = 10 nearest kept.  R (B, 20, 20) int32: R[b][i][j] = 1
+ * iff row i is kept for column j; the diagonal is 0, the matrix is not symmetrised.  dist2: NULL, or (B, 20, 20) f32, the squared
+ * distances (for the tests).  A T x T matrix over time frames is not built.
+ * ws: the MFCC's first pass at hop 512 + B 20 T_max + B ceil(T_max / chunk) 190 floats. */
+long ast_recurrence_ws_floats(int B, int n);
+int ast_recurrence_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table, float* ws,
+                       long ws_floats, int32_t* R, float* dist2, void* stream);
+/* self_similarity_distance (evaluation_style_transfer.py:121-133): each clip at its own length; out[b] = the mean over the 400 cells
+ * of |R_a - R_b|, a multiple of 1 / 400.  Equal clips score exactly 0.  ws: both clips' ast_recurrence counts + 2 B 400 floats. */
+long ast_self_similarity_distance_ws_floats(int B, int n_a, int n_b);
+int ast_self_similarity_distance_len(const float* a, int n_a, const float* b, int n_b, int B, const int32_t* len_a, const int32_t* len_b,
+                                     int pad_mode, const int32_t* mel_table, float* ws, long ws_floats, float* out, void* stream);
+
 /* ---- deterministic forms (ast_amd.set_deterministic / AST_DETERMINISTIC) ---------------------------------------------------
  * The default entry points sum partials that cross workgroups with f32 atomics, in arrival order.  The forms below STORE every
  * workgroup's partial into a slot indexed by its workgroup / tile / row id (plain stores; every slot is written on every call, so
