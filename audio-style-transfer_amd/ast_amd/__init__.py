@@ -15,6 +15,7 @@ from .losses import infoNCE_loss, margin_loss, adversarial_loss, disentanglement
 from .metrics import mse_spectrogram, band_energy, instrumentation_similarity, mfcc, mfcc_distance  # noqa: F401
 from .metrics import estimate_tuning, chroma_stft, chroma_distance, chroma_similarity, pitch_mean, pitch_correlation  # noqa: F401
 from .metrics import onset_strength, onset_detect, onset_accuracy, recurrence_matrix, self_similarity_distance  # noqa: F401
+from .curation import frame_rms, silence_ratio, clip_rms, sound_windows, sound_ratio, mfcc_mean, rms_normalize, screen, DatasetReport  # noqa: F401
 
 
 class deterministic:

@@ -187,6 +187,15 @@ _SIGS = {
     "ast_recurrence_len": ([vp, i32, i32, vp, i32, vp, vp, C.c_long, vp, vp, vp], i32),
     "ast_self_similarity_distance_ws_floats": ([i32, i32, i32], C.c_long),
     "ast_self_similarity_distance_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, C.c_long, vp, vp], i32),
+    # dataset screening for a padded batch (include/ast_hip.h, ast_amd/curation.py)
+    "ast_frame_rms_tile_frames": ([], i32),
+    "ast_mfcc_mean_chunk_frames": ([], i32),
+    "ast_frame_rms_ws_floats": ([i32, i32], C.c_long),
+    "ast_frame_rms_len": ([vp, i32, i32, vp, f32, i32, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp], i32),
+    "ast_window_sound_len": ([vp, i32, i32, vp, i32, f32, vp, vp, vp], i32),
+    "ast_mfcc_mean_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_mfcc_mean_len": ([vp, i32, i32, vp, i32, i32, i32, vp, vp, C.c_long, vp, vp], i32),
+    "ast_gain_rows_len": ([vp, i32, i32, vp, vp, C.c_double, vp, vp], i32),
     # chroma and pitch metrics for a padded batch (include/ast_hip.h, ast_amd/metrics.py)
     "ast_chroma_run_frames": ([], i32),
     "ast_pitch_band": ([i32, C.POINTER(i32), C.POINTER(i32)], i32),

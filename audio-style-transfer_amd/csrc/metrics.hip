@@ -374,6 +374,14 @@ double hz_to_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + log(f 
 double mel_to_hz(double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
 }  // namespace
 
+// the first pass as curation.hip reaches it (spec_common.h)
+long mel_db_pass1_floats(int B, int n, int hop) { return mfcc_pass1_floats(B, n, hop); }
+int mel_db_pass1_runs(int n, int hop) { return mfcc_runs(n, hop); }
+void mel_db_pass1_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel, float* db,
+                         float* run_max, hipStream_t s) {
+  mel_db_launch(waves, B, n, n_samples, hop, pad_mode, mel, db, run_max, s);
+}
+
 extern "C" long ast_spec_mse_ws_floats(int B, int n_orig, int n_gen) {
   if (B < 1 || n_orig < 1 || n_gen < 1) return 0;
   return (long)B * ((2 + std::min(n_orig, n_gen) / MSE_HOP) / 2);

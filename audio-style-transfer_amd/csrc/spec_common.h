@@ -1,5 +1,5 @@
-// What the spectrogram metrics (metrics.hip) and the chroma / pitch metrics (chroma.hip) share: the clamped per-clip count, a
-// clip's sample under the pad mode, the fixed-order block sum in double and the host's row checks.  Everything on the device is
+// What the spectrogram metrics (metrics.hip), the chroma / pitch metrics (chroma.hip) and the dataset screening (curation.hip)
+// share: the clamped per-clip count, a clip's sample under the pad mode, the fixed-order block sum in double and the host's row checks.  Everything on the device is
 // force-inlined, so moving it here changes no kernel's code (tools/kernel_diff.py).
 #pragma once
 #include <math.h>
@@ -45,3 +45,10 @@ inline int rows_check(const char* name, int B, int n, int n_fft, int pad_mode) {
   return 0;
 }
 }  // namespace
+
+// ---- the MFCC's first pass (metrics.hip) for the dataset screening (curation.hip): the unclamped mel dB rows db (B, T_max, 128) and
+// one maximum per run of frames, T_max = 1 + n / hop.  Host code only, not exported.
+AST_HIDDEN long mel_db_pass1_floats(int B, int n, int hop);                    // floats of db + run_max, run_max behind db
+AST_HIDDEN int mel_db_pass1_runs(int n, int hop);                             // run maxima per clip
+AST_HIDDEN void mel_db_pass1_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel,
+                                    float* db, float* run_max, hipStream_t s);

@@ -757,6 +757,46 @@ int ast_tok_max_ops(void);
 int ast_tok_program(const ast_tok_op_t* ops, int nops, int G, int xcd, void* sync, int* status, const int64_t* d_offset,
                     void* stream);
 
+/* ---- dataset screening: the reference's Preprocessing_Dataset scripts for a padded batch (csrc/curation.hip; DESIGN 7, "Dataset
+ * screening"; parity with librosa's and pydub's own output is unpinned).  Rows, counts, clamps, pad modes and limits as for the
+ * spectrogram metrics above; at any sample rate -- a rate enters only through `win` and the mel table.  No atomics; results are
+ * bit-reproducible and row b does not depend on the other rows.  Every workspace slot that is read is written first. */
+/* frames per workgroup of the frame-RMS pass and frames per partial of the mel-mean pass (what the workspace counts are built on) */
+int ast_frame_rms_tile_frames(void);
+int ast_mfcc_mean_chunk_frames(void);
+/* librosa.feature.rms(y)[0] at its defaults, the silent-frame share of silent_tracks_dataset.py:20-27 and the clip level
+ * sqrt(mean(y^2)) of dataset_tracks_analysis.py:27, in one pass over the samples: frame_length 2048, hop 512, centred,
+ * T_b = 1 + L_b / 512.  rms (B, T_max) f32, T_max = 1 + n / 512: rms[b][t] = sqrt(mean of the padded clip's samples
+ * [512 t - 1024, 512 t + 1024) squared), 0 for t >= T_b.  A frame is four hop blocks of 512 samples: a workgroup forms each
+ * block's sum of squares once (a fixed tree) and adds four of them per frame in ascending block order.
+ * n_frames[b] = T_b; silent[b] = the frames with rms < threshold (int32); silence_ratio[b] = silent / T_b;
+ * level[b] = sqrt(S_b / L_b) with S_b the sum of squares of the clip's own L_b samples in double, rounded once; sumsq[b] = S_b
+ * (double (B,), may be NULL: what ast_gain_rows_len takes).  With AST_PAD_REFLECT L_b is clamped to [1025, n] for the level too.
+ * ws: 3 B ceil(T_max / tile) floats, 8-byte aligned (a double and an int32 per tile). */
+long ast_frame_rms_ws_floats(int B, int n);
+int ast_frame_rms_len(const float* waves, int B, int n, const int32_t* n_samples, float threshold, int pad_mode, float* ws,
+                      long ws_floats, float* rms, int32_t* n_frames, int32_t* silent, float* silence_ratio, float* level,
+                      double* sumsq, void* stream);
+/* is_mostly_sound (split_BachViolinDataset.py:24-30) on float samples at full scale 1.0: non-overlapping windows of `win` samples
+ * (the caller's sample_rate / 10 for the script's 100 ms), W_b = L_b / win of them; mask (B, W_max) int32, W_max = n / win:
+ * mask[b][w] = 1 when 20 log10(rms_w) > threshold_db (an rms_w of 0 is never sound), 0 for w >= W_b; sound_ratio[b] = the clip's
+ * ones / W_b, exactly 0 when W_b = 0.  One wave per window.  mask may be NULL when W_max = 0.  No workspace. */
+int ast_window_sound_len(const float* waves, int B, int n, const int32_t* n_samples, int win, float threshold_db, int32_t* mask,
+                         float* sound_ratio, void* stream);
+/* np.mean(librosa.feature.mfcc(y, sr, n_mfcc), axis=1) (dataset_tracks_analysis.py:28-29, dataset_variety.py:13-16) without the
+ * per-frame DCT: out (B, n_mfcc) f32 = the first n_mfcc <= 20 coefficients of the orthonormal DCT-II, in double, of the time-mean
+ * over the clip's T_b = 1 + L_b / hop frames of its clamped mel dB rows (the DCT is linear).  The rows are ast_mfcc_len's first
+ * pass, unchanged; mel_table as there, built by ast_mel_table for the clip's own sample rate.  hop 256 or 512.
+ * ws: ast_mfcc_ws_floats(B, n, hop) + 128 B ceil(T_max / chunk) floats. */
+long ast_mfcc_mean_ws_floats(int B, int n, int hop);
+int ast_mfcc_mean_len(const float* waves, int B, int n, const int32_t* n_samples, int n_mfcc, int hop, int pad_mode,
+                      const int32_t* mel_table, float* ws, long ws_floats, float* out, void* stream);
+/* rms_normalize (unifies_violin_datasets.py:25-30): out[b][i] = waves[b][i] * g_b for i < L_b, 0 behind;
+ * g_b = target_rms / sqrt(sumsq[b] / L_b) in double, rounded once, and 1 where the level is 0.  sumsq: ast_frame_rms_len's, taken
+ * with AST_PAD_CONSTANT (the same clamp of L_b).  out may be waves.  No workspace. */
+int ast_gain_rows_len(const float* waves, int B, int n, const int32_t* n_samples, const double* sumsq, double target_rms, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
