@@ -14,12 +14,10 @@ table and the window length.  No length is read on the host, so every call can b
 (device, sample_rate) is built on first use, which has to happen outside a capture."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from ._lib import check, len_tensor, lib, ptr, stream
-from .metrics import MFCC_HOPS, MFCC_N_FFT, PAD_MODES, _rows
+from ._lib import check, lib, ptr, stream
+from .metrics import MFCC_HOPS, MFCC_N_FFT, PAD_MODES, _one, _run
 
 RMS_FRAME, RMS_HOP = 2048, 512                           # librosa.feature.rms defaults: frame_length, hop_length
 SILENCE_RMS, SILENCE_RATIO = 0.005, 0.3                  # rms_threshold, silence_ratio_threshold of silent_tracks_dataset.py
@@ -30,9 +28,8 @@ MAX_N_MFCC = 20
 
 def _frame_rms(name, waves, n_samples, threshold, pad_mode):
     """-> dict(rms (B, T_max), n_frames, silent (B,) int32, silence_ratio, level (B,) f32, sumsq (B,) f64, w, ns)"""
-    w = _rows(waves, name, "waves", RMS_FRAME, pad_mode)
+    w, ns = _one(name, waves, n_samples, RMS_FRAME, pad_mode)
     B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
     L = lib()
     ptr(w)
     dev = w.device
@@ -94,33 +91,14 @@ def sound_windows(waves, n_samples=None, sample_rate=22050, frame_ms=SOUND_MS, t
     """waves (B, n) f32 device rows -> (B, W_max) int32 mask, W_max = n // win, win = sample_rate * frame_ms // 1000: 1 where window w
     of clip b (its samples [w win, (w + 1) win)) has 20 log10(rms) > threshold_db at full scale 1.0, 0 elsewhere and for
     w >= W_b = n_b // win.  A window whose rms is 0 is never sound."""
-    w = _rows(waves, "sound_windows", "waves", RMS_FRAME, "constant")
-    ns = len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
-    return _sound("sound_windows", w, ns, sample_rate, frame_ms, threshold_db)[0]
+    return _sound("sound_windows", *_one("sound_windows", waves, n_samples, RMS_FRAME, "constant"), sample_rate, frame_ms, threshold_db)[0]
 
 
 def sound_ratio(waves, n_samples=None, sample_rate=22050, frame_ms=SOUND_MS, threshold_db=SOUND_DB):
     """waves (B, n) f32 device rows -> (B,) f32: the share of clip b's W_b windows that sound_windows marks, exactly 0.0 when the clip
     is shorter than a window (is_mostly_sound, split_BachViolinDataset.py:24-30; the script keeps a clip at >= 0.6).  pydub computes
     the level on int16 samples with an integer RMS; this is the same rule on float samples."""
-    w = _rows(waves, "sound_ratio", "waves", RMS_FRAME, "constant")
-    ns = len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
-    return _sound("sound_ratio", w, ns, sample_rate, frame_ms, threshold_db)[1]
-
-
-_mel_tables = {}
-
-
-def _mel_table(device, sample_rate):
-    """The Slaney mel filter bank at `sample_rate` as the sparse table the kernels read (ast_mel_table), on `device`; one per
-    (device, sample_rate), filled on first use, outside any graph capture."""
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), sample_rate)
-    if key not in _mel_tables:
-        L = lib()
-        words = (ctypes.c_int32 * L.ast_mel_table_words())()
-        check(L.ast_mel_table(sample_rate, ctypes.addressof(words)), "ast_mel_table")
-        _mel_tables[key] = torch.tensor(list(words), dtype=torch.int32).to(device)
-    return _mel_tables[key]
+    return _sound("sound_ratio", *_one("sound_ratio", waves, n_samples, RMS_FRAME, "constant"), sample_rate, frame_ms, threshold_db)[1]
 
 
 def _mfcc_mean_args(name, sample_rate, n_mfcc, hop_length):
@@ -133,15 +111,7 @@ def _mfcc_mean_args(name, sample_rate, n_mfcc, hop_length):
 
 
 def _mfcc_mean(w, ns, sample_rate, n_mfcc, hop_length, pad_mode):
-    B, n = w.shape
-    L = lib()
-    ptr(w)
-    table = _mel_table(w.device, sample_rate)
-    ws = torch.empty(L.ast_mfcc_mean_ws_floats(B, n, hop_length), dtype=torch.float32, device=w.device)
-    out = torch.empty((B, n_mfcc), dtype=torch.float32, device=w.device)
-    check(L.ast_mfcc_mean_len(ptr(w), B, n, ptr(ns), n_mfcc, hop_length, PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(out),
-                              stream()), "ast_mfcc_mean_len")
-    return out
+    return _run("mfcc_mean", (w,), (ns,), [((w.shape[0], n_mfcc), torch.float32)], pad_mode, (n_mfcc, hop_length), (hop_length,), sample_rate)[0]
 
 
 def mfcc_mean(waves, n_samples=None, sample_rate=22050, n_mfcc=13, hop_length=512, pad_mode="constant"):
@@ -150,9 +120,7 @@ def mfcc_mean(waves, n_samples=None, sample_rate=22050, n_mfcc=13, hop_length=51
     so this is the DCT (in double) of the time-mean of the clip's clamped mel dB rows; the per-frame coefficients never exist.
     n_mfcc <= 20.  n_samples as for frame_rms."""
     _mfcc_mean_args("mfcc_mean", sample_rate, n_mfcc, hop_length)
-    w = _rows(waves, "mfcc_mean", "waves", MFCC_N_FFT, pad_mode)
-    ns = len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
-    return _mfcc_mean(w, ns, sample_rate, n_mfcc, hop_length, pad_mode)
+    return _mfcc_mean(*_one("mfcc_mean", waves, n_samples, MFCC_N_FFT, pad_mode), sample_rate, n_mfcc, hop_length, pad_mode)
 
 
 def _target(name, target_rms):

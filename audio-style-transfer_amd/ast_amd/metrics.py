@@ -38,38 +38,69 @@ def _rows(t, name, what, n_fft, pad_mode):
     return t.contiguous()
 
 
+def _one(name, waves, n_samples, n_fft, pad_mode):
+    """the rows and counts of one batch, checked"""
+    w = _rows(waves, name, "waves", n_fft, pad_mode)
+    return w, len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
+
+
+def _pair(name, a, what_a, b, what_b, n_a, n_b, n_fft, pad_mode):
+    """the rows and counts of a pair of batches, checked"""
+    a, b = _rows(a, name, what_a, n_fft, pad_mode), _rows(b, name, what_b, n_fft, pad_mode)
+    B = a.shape[0]
+    if b.shape[0] != B:
+        raise ValueError(f"{name}: {B} {what_a} and {b.shape[0]} {what_b} rows")
+    return a, b, len_tensor(n_a, B, "n_" + what_a, device=True, contiguous=True), len_tensor(n_b, B, "n_" + what_b, device=True, contiguous=True)
+
+
+_mel_tables = {}
+
+
+def _mel_table(device, sample_rate):
+    """The Slaney mel filter bank at `sample_rate` as the sparse table the kernels read (ast_mel_table: built on the host in double),
+    on `device`; one per (device, sample_rate).  Filled on first use, which has to happen outside a graph capture: a session's
+    warm-up runs do that."""
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), sample_rate)
+    if key not in _mel_tables:
+        L = lib()
+        words = (ctypes.c_int32 * L.ast_mel_table_words())()
+        check(L.ast_mel_table(sample_rate, ctypes.addressof(words)), "ast_mel_table")
+        _mel_tables[key] = torch.tensor(list(words), dtype=torch.int32).to(device)
+    return _mel_tables[key]
+
+
+def _run(entry, rows, counts, outs, pad_mode, extra=(), ws_extra=(), sample_rate=None):
+    """The call of ast_<entry>_len on one batch or on the two of a pair (rows, counts: one or two checked tensors each), in the order
+    of its refusals: a host tensor first, then the mel table at `sample_rate` (None: the entry takes none), then the workspace of
+    ast_<entry>_ws_floats(B, row widths, *ws_extra) and the outputs -- outs: (shape, dtype) each, or None for a null pointer.
+    extra: the entry's arguments between the counts and the pad mode.  -> the list of outputs"""
+    L = lib()
+    B, dev, widths = rows[0].shape[0], rows[0].device, [t.shape[1] for t in rows]
+    p = [ptr(t) for t in rows]
+    table = () if sample_rate is None else (ptr(_mel_table(dev, sample_rate)),)
+    ws = torch.empty(getattr(L, f"ast_{entry}_ws_floats")(B, *widths, *ws_extra), dtype=torch.float32, device=dev)
+    outs = [o and torch.empty(o[0], dtype=o[1], device=dev) for o in outs]
+    front = (p[0], B, widths[0], ptr(counts[0])) if len(rows) == 1 else (p[0], widths[0], p[1], widths[1], B, ptr(counts[0]), ptr(counts[1]))
+    check(getattr(L, f"ast_{entry}_len")(*front, *extra, PAD_MODES[pad_mode], *table, ptr(ws), ws.numel(), *map(ptr, outs), stream()),
+          f"ast_{entry}_len")
+    return outs
+
+
 def mse_spectrogram(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
     """original (B, n), generated (B, m) f32 device rows -> (B,) f32: mean over 513 x T_b of (|A| - |G|)^2 at n_fft 1024, hop 256,
     both clips cut to L_b = min(n_original[b], n_generated[b]) samples first, T_b = 1 + L_b // 256.
     n_original, n_generated: int32 (B,) device tensors, clamped on the device to [1, row width] ([513, row width] with
     pad_mode="reflect"); None: the rows are full."""
-    a = _rows(original, "mse_spectrogram", "original", MSE_N_FFT, pad_mode)
-    g = _rows(generated, "mse_spectrogram", "generated", MSE_N_FFT, pad_mode)
-    B = a.shape[0]
-    if g.shape[0] != B:
-        raise ValueError(f"mse_spectrogram: {B} original and {g.shape[0]} generated rows")
-    na = len_tensor(n_original, B, "n_original", device=True, contiguous=True)
-    ng = len_tensor(n_generated, B, "n_generated", device=True, contiguous=True)
-    L = lib()
-    ws = torch.empty(L.ast_spec_mse_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
-    out = torch.empty(B, dtype=torch.float32, device=a.device)
-    check(L.ast_spec_mse_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(), ptr(out),
-                             stream()), "ast_spec_mse_len")
-    return out
+    a, g, na, ng = _pair("mse_spectrogram", original, "original", generated, "generated", n_original, n_generated, MSE_N_FFT, pad_mode)
+    return _run("spec_mse", (a, g), (na, ng), [((a.shape[0],), torch.float32)], pad_mode)[0]
 
 
 def band_energy(waves, n_samples=None, pad_mode="constant"):
     """waves (B, n) f32 device rows -> (B, 1025) f32: E[b, f] = sum over the clip's own T(n_b) = 1 + n_b // 512 frames of |S_b[f, t]|
     at n_fft 2048, hop 512.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
     pad_mode="reflect"); None: the rows are full."""
-    w = _rows(waves, "band_energy", "waves", BAND_N_FFT, pad_mode)
-    B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
-    L = lib()
-    ws = torch.empty(L.ast_band_energy_ws_floats(B, n), dtype=torch.float32, device=w.device)
-    out = torch.empty((B, BAND_BINS), dtype=torch.float32, device=w.device)
-    check(L.ast_band_energy_len(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(ws), ws.numel(), ptr(out), stream()), "ast_band_energy_len")
-    return out
+    w, ns = _one("band_energy", waves, n_samples, BAND_N_FFT, pad_mode)
+    return _run("band_energy", (w,), (ns,), [((w.shape[0], BAND_BINS), torch.float32)], pad_mode)[0]
 
 
 def instrumentation_similarity(a, b, n_a=None, n_b=None, pad_mode="constant"):
@@ -84,21 +115,6 @@ def instrumentation_similarity(a, b, n_a=None, n_b=None, pad_mode="constant"):
     out = torch.empty(a.shape[0], dtype=torch.float32, device=ea.device)
     check(lib().ast_pearson_rows(ptr(ea), ptr(eb), a.shape[0], BAND_BINS, ptr(out), stream()), "ast_pearson_rows")
     return out
-
-
-_mel_tables = {}
-
-
-def _mel_table(device):
-    """The Slaney mel filter bank at 22 050 Hz as the sparse table the kernels read (ast_mel_table: built on the host in double),
-    on `device`.  Filled on first use per device, which has to happen outside a graph capture: a session's warm-up runs do that."""
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    if key not in _mel_tables:
-        L = lib()
-        words = (ctypes.c_int32 * L.ast_mel_table_words())()
-        check(L.ast_mel_table(MFCC_SR, ctypes.addressof(words)), "ast_mel_table")
-        _mel_tables[key] = torch.tensor(list(words), dtype=torch.int32).to(device)
-    return _mel_tables[key]
 
 
 def _mfcc_args(name, n_mfcc, hop_length):
@@ -116,17 +132,9 @@ def mfcc(waves, n_samples=None, n_mfcc=20, hop_length=512, pad_mode="constant"):
     orthonormal DCT-II along the bands.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
     pad_mode="reflect"); None: the rows are full."""
     _mfcc_args("mfcc", n_mfcc, hop_length)
-    w = _rows(waves, "mfcc", "waves", MFCC_N_FFT, pad_mode)
+    w, ns = _one("mfcc", waves, n_samples, MFCC_N_FFT, pad_mode)
     B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
-    L = lib()
-    ptr(w)                                                # a host tensor is refused before the table is asked for a device
-    table = _mel_table(w.device)
-    ws = torch.empty(L.ast_mfcc_ws_floats(B, n, hop_length), dtype=torch.float32, device=w.device)
-    out = torch.empty((B, n_mfcc, 1 + n // hop_length), dtype=torch.float32, device=w.device)
-    check(L.ast_mfcc_len(ptr(w), B, n, ptr(ns), n_mfcc, hop_length, PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(out), stream()),
-          "ast_mfcc_len")
-    return out
+    return _run("mfcc", (w,), (ns,), [((B, n_mfcc, 1 + n // hop_length), torch.float32)], pad_mode, (n_mfcc, hop_length), (hop_length,), MFCC_SR)[0]
 
 
 def mfcc_distance(generated, reference, n_generated=None, n_reference=None, n_mfcc=13, hop_length=256, pad_mode="constant"):
@@ -135,21 +143,8 @@ def mfcc_distance(generated, reference, n_generated=None, n_reference=None, n_mf
     The clips of a pair keep their own lengths: nothing is truncated, each is clamped by its own maximum.  Equal clips score
     exactly 0."""
     _mfcc_args("mfcc_distance", n_mfcc, hop_length)
-    g = _rows(generated, "mfcc_distance", "generated", MFCC_N_FFT, pad_mode)
-    r = _rows(reference, "mfcc_distance", "reference", MFCC_N_FFT, pad_mode)
-    B = g.shape[0]
-    if r.shape[0] != B:
-        raise ValueError(f"mfcc_distance: {B} generated and {r.shape[0]} reference rows")
-    ng = len_tensor(n_generated, B, "n_generated", device=True, contiguous=True)
-    nr = len_tensor(n_reference, B, "n_reference", device=True, contiguous=True)
-    L = lib()
-    ptr(g), ptr(r)
-    table = _mel_table(g.device)
-    ws = torch.empty(L.ast_mfcc_distance_ws_floats(B, g.shape[1], r.shape[1], hop_length), dtype=torch.float32, device=g.device)
-    out = torch.empty(B, dtype=torch.float32, device=g.device)
-    check(L.ast_mfcc_distance_len(ptr(g), g.shape[1], ptr(r), r.shape[1], B, ptr(ng), ptr(nr), n_mfcc, hop_length, PAD_MODES[pad_mode],
-                                  ptr(table), ptr(ws), ws.numel(), ptr(out), stream()), "ast_mfcc_distance_len")
-    return out
+    g, r, ng, nr = _pair("mfcc_distance", generated, "generated", reference, "reference", n_generated, n_reference, MFCC_N_FFT, pad_mode)
+    return _run("mfcc_distance", (g, r), (ng, nr), [((g.shape[0],), torch.float32)], pad_mode, (n_mfcc, hop_length), (hop_length,), MFCC_SR)[0]
 
 
 # ---- chroma and pitch (csrc/chroma.hip): librosa.piptrack, estimate_tuning, filters.chroma and feature.chroma_stft restated as a
@@ -162,15 +157,6 @@ def _chroma_setting(name, n_fft, hop_length):
     if (n_fft, hop_length) not in CHROMA_SETTINGS:
         raise ValueError(f"{name}: (n_fft, hop_length) must be (2048, 512) or (1024, 256), the evaluation scripts' two settings, "
                          f"got ({n_fft!r}, {hop_length!r})")
-
-
-def _pair(name, a, what_a, b, what_b, n_a, n_b, n_fft, pad_mode):
-    """the rows and counts of a pair of batches, checked"""
-    a, b = _rows(a, name, what_a, n_fft, pad_mode), _rows(b, name, what_b, n_fft, pad_mode)
-    B = a.shape[0]
-    if b.shape[0] != B:
-        raise ValueError(f"{name}: {B} {what_a} and {b.shape[0]} {what_b} rows")
-    return a, b, B, len_tensor(n_a, B, "n_" + what_a, device=True, contiguous=True), len_tensor(n_b, B, "n_" + what_b, device=True, contiguous=True)
 
 
 def _tuning(w, ns, n_fft, hop_length, pad_mode, debug=None):
@@ -190,16 +176,14 @@ def estimate_tuning(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode=
     0.0 for a clip without a peak.  (n_fft, hop_length): (2048, 512) or (1024, 256).  n_samples: int32 (B,) device tensor, clamped
     on the device to [1, n] ([n_fft / 2 + 1, n] with pad_mode="reflect"); None: the rows are full."""
     _chroma_setting("estimate_tuning", n_fft, hop_length)
-    w = _rows(waves, "estimate_tuning", "waves", n_fft, pad_mode)
-    return _tuning(w, len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True), n_fft, hop_length, pad_mode)
+    return _tuning(*_one("estimate_tuning", waves, n_samples, n_fft, pad_mode), n_fft, hop_length, pad_mode)
 
 
 def tuning_debug(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode="constant"):
     """estimate_tuning and what it counted -> (tuning (B,), candidates (B,) int32, kept (B,) int32, thr (B,) f32, histogram (B, 100) int32);
     for the tests"""
     _chroma_setting("tuning_debug", n_fft, hop_length)
-    w = _rows(waves, "tuning_debug", "waves", n_fft, pad_mode)
-    ns = len_tensor(n_samples, w.shape[0], "n_samples", device=True, contiguous=True)
+    w, ns = _one("tuning_debug", waves, n_samples, n_fft, pad_mode)
     ptr(w)
     dbg = torch.zeros((w.shape[0], lib().ast_tuning_debug_words()), dtype=torch.int32, device=w.device)
     tuning = _tuning(w, ns, n_fft, hop_length, pad_mode, dbg)
@@ -214,9 +198,8 @@ def chroma_stft(waves, n_samples=None, n_fft=2048, hop_length=512, pad_mode="con
     each frame divided by its maximum.  tuning: (B,) f32 device tensor in semitones, or None: estimate_tuning's.
     (n_fft, hop_length): (2048, 512) or (1024, 256).  n_samples as above."""
     _chroma_setting("chroma_stft", n_fft, hop_length)
-    w = _rows(waves, "chroma_stft", "waves", n_fft, pad_mode)
+    w, ns = _one("chroma_stft", waves, n_samples, n_fft, pad_mode)
     B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
     if tuning is None:
         tuning = _tuning(w, ns, n_fft, hop_length, pad_mode)
     elif not (torch.is_tensor(tuning) and tuning.dtype == torch.float32 and tuple(tuning.shape) == (B,)):
@@ -232,14 +215,8 @@ def chroma_distance(original, generated, n_original=None, n_generated=None, pad_
     ||chroma_stft(original)[b, :, t] - chroma_stft(generated)[b, :, t]||_2 at n_fft 2048, hop 512 (evaluation_reconstruction.py:39-52),
     both clips cut to L_b = min(n_original[b], n_generated[b]) samples first (:193-204), each with its own tuning.  Equal clips score
     exactly 0."""
-    a, g, B, na, ng = _pair("chroma_distance", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
-    L = lib()
-    ptr(a), ptr(g)
-    ws = torch.empty(L.ast_chroma_distance_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
-    out = torch.empty(B, dtype=torch.float32, device=a.device)
-    check(L.ast_chroma_distance_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
-                                    ptr(out), stream()), "ast_chroma_distance_len")
-    return out
+    a, g, na, ng = _pair("chroma_distance", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
+    return _run("chroma_distance", (a, g), (na, ng), [((a.shape[0],), torch.float32)], pad_mode)[0]
 
 
 def chroma_similarity(generated, original, n_generated=None, n_original=None, pad_mode="constant"):
@@ -247,23 +224,16 @@ def chroma_similarity(generated, original, n_generated=None, n_original=None, pa
     between chroma_stft(generated)[b, c] and chroma_stft(original)[b, c] at n_fft 1024, hop 256 over the frames t < min(T_g, T_o)
     (evaluation_style_transfer.py:80-96): the "content kept?" score.  The clips keep their own lengths; rows whose r is not finite
     are left out, and a pair without a finite row scores exactly 0.0."""
-    g, a, B, ng, na = _pair("chroma_similarity", generated, "generated", original, "original", n_generated, n_original, 1024, pad_mode)
-    L = lib()
-    ptr(g), ptr(a)
-    ws = torch.empty(L.ast_chroma_similarity_ws_floats(B, g.shape[1], a.shape[1]), dtype=torch.float32, device=g.device)
-    out = torch.empty(B, dtype=torch.float32, device=g.device)
-    check(L.ast_chroma_similarity_len(ptr(g), g.shape[1], ptr(a), a.shape[1], B, ptr(ng), ptr(na), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
-                                      ptr(out), stream()), "ast_chroma_similarity_len")
-    return out
+    g, a, ng, na = _pair("chroma_similarity", generated, "generated", original, "original", n_generated, n_original, 1024, pad_mode)
+    return _run("chroma_similarity", (g, a), (ng, na), [((g.shape[0],), torch.float32)], pad_mode)[0]
 
 
 def pitch_mean(waves, n_samples=None, pad_mode="constant"):
     """waves (B, n) f32 device rows at 22 050 Hz -> (B, T_max) f32, T_max = 1 + n // 512: np.mean(librosa.piptrack(y, sr)[0], axis=0)
     as documented, for clip b over its own n_b samples (n_fft 2048, hop 512; the interpolated peaks of |STFT| between 150 and
     4000 Hz above a tenth of the frame's maximum, averaged over all 1025 bins); frames t >= T_b are exactly 0."""
-    w = _rows(waves, "pitch_mean", "waves", 2048, pad_mode)
+    w, ns = _one("pitch_mean", waves, n_samples, 2048, pad_mode)
     B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
     out = torch.empty((B, 1 + n // 512), dtype=torch.float32, device=w.device)
     check(lib().ast_pitch_mean_len(ptr(w), B, n, ptr(ns), None, n, PAD_MODES[pad_mode], ptr(out), stream()), "ast_pitch_mean_len")
     return out
@@ -273,14 +243,8 @@ def pitch_correlation(original, generated, n_original=None, n_generated=None, pa
     """original (B, n), generated (B, m) f32 device rows at 22 050 Hz -> (B,) f32: Pearson's r of the two clips' pitch_mean over
     the frames (evaluation_reconstruction.py:83-103), both clips cut to L_b = min(n_original[b], n_generated[b]) samples first
     (:193-204); exactly 0.0 where r is not finite or there are fewer than 2 frames."""
-    a, g, B, na, ng = _pair("pitch_correlation", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
-    L = lib()
-    ptr(a), ptr(g)
-    ws = torch.empty(L.ast_pitch_correlation_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
-    out = torch.empty(B, dtype=torch.float32, device=a.device)
-    check(L.ast_pitch_correlation_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(ws), ws.numel(),
-                                      ptr(out), stream()), "ast_pitch_correlation_len")
-    return out
+    a, g, na, ng = _pair("pitch_correlation", original, "original", generated, "generated", n_original, n_generated, 2048, pad_mode)
+    return _run("pitch_correlation", (a, g), (na, ng), [((a.shape[0],), torch.float32)], pad_mode)[0]
 
 
 # ---- onsets and self-similarity (csrc/metrics.hip): librosa.onset.onset_detect and librosa.segment.recurrence_matrix at their
@@ -288,17 +252,9 @@ def pitch_correlation(original, generated, n_original=None, n_generated=None, pa
 ONSET_HOP, SS_N_MFCC = 512, 20                            # librosa's default hop_length and n_mfcc
 
 
-def _onset_one(name, entry, ws_entry, waves, n_samples, pad_mode, out_dtype):
-    w = _rows(waves, name, "waves", MFCC_N_FFT, pad_mode)
-    B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
-    L = lib()
-    ptr(w)
-    table = _mel_table(w.device)
-    ws = torch.empty(getattr(L, ws_entry)(B, n), dtype=torch.float32, device=w.device)
-    out = torch.empty((B, 1 + n // ONSET_HOP), dtype=out_dtype, device=w.device)
-    check(getattr(L, entry)(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(out), stream()), entry)
-    return out
+def _onset_one(name, waves, n_samples, pad_mode, out_dtype):
+    w, ns = _one(name, waves, n_samples, MFCC_N_FFT, pad_mode)
+    return _run(name, (w,), (ns,), [((w.shape[0], 1 + w.shape[1] // ONSET_HOP), out_dtype)], pad_mode, sample_rate=MFCC_SR)[0]
 
 
 def onset_strength(waves, n_samples=None, pad_mode="constant"):
@@ -307,7 +263,7 @@ def onset_strength(waves, n_samples=None, pad_mode="constant"):
     of `mfcc` at hop 512, e[t] = the mean over the 128 bands of max(0, dB[m, t-2] - dB[m, t-3]) for 3 <= t < T_b; exactly 0 for t < 3
     and for t >= T_b = 1 + n_b // 512.  n_samples: int32 (B,) device tensor, clamped on the device to [1, n] ([1025, n] with
     pad_mode="reflect"); None: the rows are full."""
-    return _onset_one("onset_strength", "ast_onset_strength_len", "ast_onset_strength_ws_floats", waves, n_samples, pad_mode, torch.float32)
+    return _onset_one("onset_strength", waves, n_samples, pad_mode, torch.float32)
 
 
 def onset_detect(waves, n_samples=None, pad_mode="constant"):
@@ -316,37 +272,21 @@ def onset_detect(waves, n_samples=None, pad_mode="constant"):
     shape does not depend on the data, so the call can be captured; `mask[b].nonzero()` gives librosa's frames.  No onsets where
     the envelope is all zero or not all finite; else the normalised envelope's peak picking with pre_max 1, post_max 1, pre_avg 4,
     post_avg 5, delta 0.07, wait 1 (0.03 sr // hop and so on at 22 050 Hz and hop 512).  n_samples as for onset_strength."""
-    return _onset_one("onset_detect", "ast_onset_detect_len", "ast_onset_detect_ws_floats", waves, n_samples, pad_mode, torch.int32)
+    return _onset_one("onset_detect", waves, n_samples, pad_mode, torch.int32)
 
 
 def onset_accuracy(original, generated, n_original=None, n_generated=None, pad_mode="constant"):
     """original (B, n), generated (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the F1 score of the two clips' onset frames
     (evaluation_reconstruction.py:54-81), both clips cut to L_b = min(n_original[b], n_generated[b]) samples first (:193-204):
     1.0 if neither has an onset, 0.0 if exactly one has none, else 2 |O and G| / (|O| + |G|).  Equal clips score exactly 1."""
-    a, g, B, na, ng = _pair("onset_accuracy", original, "original", generated, "generated", n_original, n_generated, MFCC_N_FFT, pad_mode)
-    L = lib()
-    ptr(a), ptr(g)
-    table = _mel_table(a.device)
-    ws = torch.empty(L.ast_onset_accuracy_ws_floats(B, a.shape[1], g.shape[1]), dtype=torch.float32, device=a.device)
-    out = torch.empty(B, dtype=torch.float32, device=a.device)
-    check(L.ast_onset_accuracy_len(ptr(a), a.shape[1], ptr(g), g.shape[1], B, ptr(na), ptr(ng), PAD_MODES[pad_mode], ptr(table), ptr(ws),
-                                   ws.numel(), ptr(out), stream()), "ast_onset_accuracy_len")
-    return out
+    a, g, na, ng = _pair("onset_accuracy", original, "original", generated, "generated", n_original, n_generated, MFCC_N_FFT, pad_mode)
+    return _run("onset_accuracy", (a, g), (na, ng), [((a.shape[0],), torch.float32)], pad_mode, sample_rate=MFCC_SR)[0]
 
 
 def _recurrence(name, waves, n_samples, pad_mode, debug):
-    w = _rows(waves, name, "waves", MFCC_N_FFT, pad_mode)
-    B, n = w.shape
-    ns = len_tensor(n_samples, B, "n_samples", device=True, contiguous=True)
-    L = lib()
-    ptr(w)
-    table = _mel_table(w.device)
-    ws = torch.empty(L.ast_recurrence_ws_floats(B, n), dtype=torch.float32, device=w.device)
-    R = torch.empty((B, SS_N_MFCC, SS_N_MFCC), dtype=torch.int32, device=w.device)
-    d2 = torch.empty((B, SS_N_MFCC, SS_N_MFCC), dtype=torch.float32, device=w.device) if debug else None
-    check(L.ast_recurrence_len(ptr(w), B, n, ptr(ns), PAD_MODES[pad_mode], ptr(table), ptr(ws), ws.numel(), ptr(R), ptr(d2), stream()),
-          "ast_recurrence_len")
-    return R, d2
+    w, ns = _one(name, waves, n_samples, MFCC_N_FFT, pad_mode)
+    shape = (w.shape[0], SS_N_MFCC, SS_N_MFCC)
+    return tuple(_run("recurrence", (w,), (ns,), [(shape, torch.int32), (shape, torch.float32) if debug else None], pad_mode, sample_rate=MFCC_SR))
 
 
 def recurrence_matrix(waves, n_samples=None, pad_mode="constant"):
@@ -369,12 +309,5 @@ def self_similarity_distance(a, b, n_a=None, n_b=None, pad_mode="constant"):
     """a (B, n), b (B, m) f32 device rows at 22 050 Hz -> (B,) f32: the mean over the 400 cells of
     |recurrence_matrix(a)[i] - recurrence_matrix(b)[i]| (evaluation_style_transfer.py:121-133), a multiple of 1 / 400.  Each clip is
     taken at its own length.  Equal clips score exactly 0."""
-    a, b, B, na, nb = _pair("self_similarity_distance", a, "a", b, "b", n_a, n_b, MFCC_N_FFT, pad_mode)
-    L = lib()
-    ptr(a), ptr(b)
-    table = _mel_table(a.device)
-    ws = torch.empty(L.ast_self_similarity_distance_ws_floats(B, a.shape[1], b.shape[1]), dtype=torch.float32, device=a.device)
-    out = torch.empty(B, dtype=torch.float32, device=a.device)
-    check(L.ast_self_similarity_distance_len(ptr(a), a.shape[1], ptr(b), b.shape[1], B, ptr(na), ptr(nb), PAD_MODES[pad_mode], ptr(table),
-                                             ptr(ws), ws.numel(), ptr(out), stream()), "ast_self_similarity_distance_len")
-    return out
+    a, b, na, nb = _pair("self_similarity_distance", a, "a", b, "b", n_a, n_b, MFCC_N_FFT, pad_mode)
+    return _run("self_similarity_distance", (a, b), (na, nb), [((a.shape[0],), torch.float32)], pad_mode, sample_rate=MFCC_SR)[0]

@@ -21,7 +21,6 @@ constexpr int SR = 22050, N_CHROMA = 12;
 constexpr int CH_RUN = 16;                               // consecutive frames of one clip per workgroup
 constexpr int TN_THREADS = 1024;                         // threads of the tuning pass, one workgroup per clip
 constexpr int DBG_WORDS = 103;                           // candidates, kept, thr (float bits), 100 histogram counts
-constexpr float F32_TINY = 1.1754944e-38f;
 
 // librosa.piptrack's defaults fmin = 150, fmax = 4000: the bins with 150 <= k sr / n_fft < 4000
 __host__ __device__ constexpr int band_lo(int n_fft) { return (150 * n_fft + SR - 1) / SR; }
@@ -34,64 +33,6 @@ static_assert(band_width(2048) <= 512 && band_width(1024) <= 512, "two candidate
 __device__ __forceinline__ int cut_count(const int32_t* __restrict__ n_samples, int n, const int32_t* __restrict__ n_cut, int cut_max,
                                          int b, int lo) {
   return min(clip_count(n_samples, b, lo, n), clip_count(n_cut, b, lo, cut_max));
-}
-
-// Per-thread constants of a frame's transform.  WIDE: n_fft 2048 through the 1024-point network as in band_energy_runs_kernel
-// (thread tid owns the bins tid + 256 m, m < 4, thread 0 bin 1024 as well); otherwise n_fft 1024, one real frame per transform
-// (bins tid + 256 m, m < 2, thread 0 bin 512 as well).
-template <bool WIDE>
-struct FrameConsts {
-  float hann[4][2], tc[4], ts[4];
-  __device__ __forceinline__ void init(int tid) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int q = tid + 256 * m;
-      if (WIDE) {
-        hann[m][0] = 0.5f - 0.5f * cospif(2.f * (2 * q) / 2048);
-        hann[m][1] = 0.5f - 0.5f * cospif(2.f * (2 * q + 1) / 2048);
-        sincospif(-(float)q / NFFT, &ts[m], &tc[m]);
-      } else {
-        hann[m][0] = 0.5f - 0.5f * cospif(2.f * q / NFFT);
-      }
-    }
-  }
-};
-template <bool WIDE> struct Bins { static constexpr int N_FFT = WIDE ? 2048 : 1024, HOP = WIDE ? 512 : 256, K = N_FFT / 2 + 1, OWN = WIDE ? 4 : 2; };
-
-// frame t of a clip of L samples into buf[0], transformed; returns the half of buf that holds Z (= 1: the next frame's loads
-// into buf[0] disturb no reader of buf[1])
-template <bool WIDE, bool REFLECT>
-__device__ __forceinline__ int frame_fft(float2 (&buf)[2][NFFT], const float* __restrict__ w, int t, int L, int tid, const FrameConsts<WIDE>& fc) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int q = tid + 256 * m;
-    if (WIDE) {
-      const int idx = t * 512 + 2 * q - 1024;
-      buf[0][q] = make_float2(clip_sample<REFLECT>(w, idx, L) * fc.hann[m][0], clip_sample<REFLECT>(w, idx + 1, L) * fc.hann[m][1]);
-    } else {
-      buf[0][q] = make_float2(clip_sample<REFLECT>(w, t * 256 + q - 512, L) * fc.hann[m][0], 0.f);
-    }
-  }
-  __syncthreads();
-  return fft1024_stages(buf, tid);
-}
-// |X[k]|^2 of the thread's own bin tid + 256 m (WIDE: the Hermitian split and the twiddle of band_energy_runs_kernel)
-template <bool WIDE>
-__device__ __forceinline__ float own_power(const float2 (&z_)[NFFT], int tid, int m, const FrameConsts<WIDE>& fc) {
-  const int k = tid + 256 * m;
-  const float2 z = z_[k];
-  if (!WIDE) return z.x * z.x + z.y * z.y;
-  const float2 c = z_[(NFFT - k) & (NFFT - 1)];
-  const float er = 0.5f * (z.x + c.x), ei = 0.5f * (z.y - c.y), orr = 0.5f * (z.y + c.y), oi = -0.5f * (z.x - c.x);
-  const float xr = er + (orr * fc.tc[m] - oi * fc.ts[m]), xi = ei + (orr * fc.ts[m] + oi * fc.tc[m]);
-  return xr * xr + xi * xi;
-}
-// the last bin, K - 1 (thread 0 only)
-template <bool WIDE>
-__device__ __forceinline__ float last_power(const float2 (&z_)[NFFT]) {
-  if (WIDE) { const float2 z = z_[0]; return (z.x - z.y) * (z.x - z.y); }
-  const float2 z = z_[NFFT / 2];
-  return z.x * z.x + z.y * z.y;
 }
 
 // ---- pass 1, librosa.piptrack with its defaults: run blockIdx.x (frames CH_RUN * run ...) of clip blockIdx.y.  S (the power
@@ -123,7 +64,7 @@ __global__ __launch_bounds__(256) void pitch_runs_kernel(const float* __restrict
       if (!TUNE && tid == 0) pitch_out[(size_t)b * T_max + t] = 0.f;
       continue;
     }
-    const int cur = frame_fft<WIDE, REFLECT>(buf, w, t, L, tid, fc);   // its barriers also stand between the last frame's readers of sp and red and the writes below
+    const int cur = frame_fft<WIDE, REFLECT>(buf, w, t, G::HOP, L, tid, fc);   // its barriers also stand between the last frame's readers of sp and red and the writes below
     float mx = 0.f;
 #pragma unroll
     for (int m = 0; m < G::OWN; ++m) {
@@ -309,7 +250,7 @@ __global__ __launch_bounds__(256) void chroma_runs_kernel(const float* __restric
     for (int m = 0; m < G::OWN; ++m) chroma_column(tid + 256 * m, G::N_FFT, tune, wt[m]);
     if (tid == 0) chroma_column(G::K - 1, G::N_FFT, tune, wl);   // the last bin is thread 0's
     for (int t = t0; t < min(t0 + CH_RUN, T); ++t) {
-      const int cur = frame_fft<WIDE, REFLECT>(buf, w, t, L, tid, fc);   // its barriers also stand between the last frame's readers of red and the writes below
+      const int cur = frame_fft<WIDE, REFLECT>(buf, w, t, G::HOP, L, tid, fc);   // its barriers also stand between the last frame's readers of red and the writes below
       float acc[N_CHROMA];
 #pragma unroll
       for (int c = 0; c < N_CHROMA; ++c) acc[c] = 0.f;
@@ -378,7 +319,7 @@ __global__ __launch_bounds__(256) void chroma_dist_kernel(const float* __restric
   if (threadIdx.x == 0) out[b] = (float)(s / (double)T);
 }
 
-// chroma_similarity (R = 12) and pitch_correlation (R = 1): Pearson's r (pearson_rows_kernel's arithmetic, in double) of rows
+// chroma_similarity (R = 12) and pitch_correlation (R = 1): Pearson's r (pearson_r, spec_common.h) of rows
 // a[b][r][:T] and g[b][r][:T] for every r < R; out[b] = the mean of the finite ones, exactly 0 if there is none (a constant
 // row, T < 2).  a (B, R, Ta), g (B, R, Tg).
 __global__ __launch_bounds__(256) void pearson_frames_kernel(const float* __restrict__ a, int n_a, const int32_t* __restrict__ len_a, int Ta,
@@ -390,26 +331,15 @@ __global__ __launch_bounds__(256) void pearson_frames_kernel(const float* __rest
   double tot = 0.0;
   int kept = 0;
   for (int r = 0; r < R; ++r) {
-    const float* x = a + ((size_t)b * R + r) * Ta;
-    const float* y = g + ((size_t)b * R + r) * Tg;
-    double sx = 0.0, sy = 0.0;
-    for (int i = threadIdx.x; i < T; i += 256) { sx += (double)x[i]; sy += (double)y[i]; }
-    const double mx = block_sum_f64(sx, red) / T, my = block_sum_f64(sy, red) / T;
-    double sxy = 0.0, sxx = 0.0, syy = 0.0;
-    for (int i = threadIdx.x; i < T; i += 256) {
-      const double dx = (double)x[i] - mx, dy = (double)y[i] - my;
-      sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
-    }
-    sxy = block_sum_f64(sxy, red); sxx = block_sum_f64(sxx, red); syy = block_sum_f64(syy, red);
-    const double rr = sxy / (sqrt(sxx) * sqrt(syy));
-    if (rr == rr && fabs(rr) <= 1.7976931348623157e308) { tot += fmin(fmax(rr, -1.0), 1.0); ++kept; }
+    bool counts;
+    const double rr = pearson_r(a + ((size_t)b * R + r) * Ta, g + ((size_t)b * R + r) * Tg, T, red, counts);
+    if (counts) { tot += rr; ++kept; }
   }
   if (threadIdx.x == 0) out[b] = kept ? (float)(tot / kept) : 0.f;
 }
 
 // ---- host
-int frames_of(int n, int hop) { return 1 + n / hop; }
-int runs_of(int n, int hop) { return (frames_of(n, hop) + CH_RUN - 1) / CH_RUN; }
+int ch_runs(int n, int hop) { return runs_of(frames_of(n, hop), CH_RUN); }
 // the two settings of the evaluation scripts: 0, or -1 with the message of entry `name` set
 int setting_check(const char* name, int n_fft, int hop) {
   if (!((n_fft == 2048 && hop == 512) || (n_fft == 1024 && hop == 256)))
@@ -422,47 +352,30 @@ int cut_check(const char* name, int B, int n, int cut_max, int n_fft, int pad_mo
 }
 long tuning_floats(int B, int n, int n_fft) { return 2l * B * frames_of(n, n_fft / 4) * band_width(n_fft); }
 
-#define CH_LAUNCH(KERNEL, wide, reflect, grid, s, ...)                                                                     \
-  do {                                                                                                                      \
-    if (wide) { if (reflect) hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, s, __VA_ARGS__);                  \
-                else hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, s, __VA_ARGS__); }                       \
-    else { if (reflect) hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, s, __VA_ARGS__);                      \
-           else hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, s, __VA_ARGS__); }                           \
-  } while (0)
-
 // passes 1 and 2 (checked arguments): ws holds tuning_floats(B, n, n_fft) floats
 void tuning_launch(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int n_fft, int pad_mode,
                    float* ws, float* tuning, int32_t* debug, hipStream_t s) {
   const int hop = n_fft / 4, T_max = frames_of(n, hop), band = band_width(n_fft);
-  const bool reflect = pad_mode == AST_PAD_REFLECT;
   float* pitch = ws;
   float* mag = ws + (size_t)B * T_max * band;
-  const dim3 grid(runs_of(n, hop), B);
-  if (n_fft == 2048) {
-    if (reflect) hipLaunchKernelGGL((pitch_runs_kernel<true, true, true>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
-    else hipLaunchKernelGGL((pitch_runs_kernel<true, true, false>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
-  } else {
-    if (reflect) hipLaunchKernelGGL((pitch_runs_kernel<false, true, true>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
-    else hipLaunchKernelGGL((pitch_runs_kernel<false, true, false>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
-  }
+  const dim3 grid(ch_runs(n, hop), B);
+  if (n_fft == 2048) PAD_LAUNCH(pad_mode, (pitch_runs_kernel<true, true, R>), grid, dim3(256), s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
+  else PAD_LAUNCH(pad_mode, (pitch_runs_kernel<false, true, R>), grid, dim3(256), s, waves, n, n_samples, n_cut, cut_max, T_max, pitch, mag);
   hipLaunchKernelGGL(tuning_kernel, dim3(B), dim3(TN_THREADS), 0, s, (const float*)pitch, (const float*)mag, n, n_samples, n_cut, cut_max,
-                     reflect ? n_fft / 2 + 1 : 1, hop, T_max, band, tuning, debug);
+                     min_count(pad_mode, n_fft), hop, T_max, band, tuning, debug);
 }
 // pass 3 (checked arguments)
 void chroma_launch(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int n_fft, int pad_mode,
                    const float* tuning, float* out, hipStream_t s) {
   const int hop = n_fft / 4, T_max = frames_of(n, hop);
-  CH_LAUNCH(chroma_runs_kernel, n_fft == 2048, pad_mode == AST_PAD_REFLECT, dim3(runs_of(n, hop), B), s, waves, n, n_samples, n_cut, cut_max,
-            tuning, T_max, out);
+  const dim3 grid(ch_runs(n, hop), B);
+  if (n_fft == 2048) PAD_LAUNCH(pad_mode, (chroma_runs_kernel<true, R>), grid, dim3(256), s, waves, n, n_samples, n_cut, cut_max, tuning, T_max, out);
+  else PAD_LAUNCH(pad_mode, (chroma_runs_kernel<false, R>), grid, dim3(256), s, waves, n, n_samples, n_cut, cut_max, tuning, T_max, out);
 }
 void pitch_mean_launch(const float* waves, int B, int n, const int32_t* n_samples, const int32_t* n_cut, int cut_max, int pad_mode, float* out,
                        hipStream_t s) {
-  const int T_max = frames_of(n, 512);
-  const dim3 grid(runs_of(n, 512), B);
-  if (pad_mode == AST_PAD_REFLECT)
-    hipLaunchKernelGGL((pitch_runs_kernel<true, false, true>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, out, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((pitch_runs_kernel<true, false, false>), grid, dim3(256), 0, s, waves, n, n_samples, n_cut, cut_max, T_max, out, (float*)nullptr);
+  PAD_LAUNCH(pad_mode, (pitch_runs_kernel<true, false, R>), dim3(ch_runs(n, 512), B), dim3(256), s, waves, n, n_samples, n_cut, cut_max,
+             frames_of(n, 512), out, (float*)nullptr);
 }
 // floats of a pair's chroma scores: the peaks of the wider batch (the two batches use them in turn), 2 B tunings, both chromas
 long chroma_pair_floats(int B, int n_a, int n_g, int n_fft) {
@@ -504,8 +417,7 @@ extern "C" int ast_tuning_len(const float* waves, int B, int n, const int32_t* n
   const char* me = "ast_tuning_len";
   if (!waves || !tuning) AST_FAIL("%s: null pointer", me);
   if (setting_check(me, n_fft, hop) || cut_check(me, B, n, cut_max, n_fft, pad_mode)) return -1;
-  const long need = tuning_floats(B, n, n_fft);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, tuning_floats(B, n, n_fft))) return -1;
   tuning_launch(waves, B, n, n_samples, n_cut, cut_max, n_fft, pad_mode, ws, tuning, debug, (hipStream_t)stream);
   AST_CHECK_LAUNCH();
   return 0;
@@ -531,13 +443,12 @@ extern "C" int ast_chroma_distance_len(const float* original, int n_orig, const 
   const char* me = "ast_chroma_distance_len";
   if (!original || !generated || !out) AST_FAIL("%s: null pointer", me);
   if (cut_check(me, B, n_orig, n_gen, 2048, pad_mode)) return -1;
-  const long need = chroma_pair_floats(B, n_orig, n_gen, 2048);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, chroma_pair_floats(B, n_orig, n_gen, 2048))) return -1;
   hipStream_t s = (hipStream_t)stream;
   float *ca, *cg;
   chroma_pair_launch(original, n_orig, len_orig, generated, n_gen, len_gen, B, 2048, true, pad_mode, ws, &ca, &cg, s);
   hipLaunchKernelGGL(chroma_dist_kernel, dim3(B), dim3(256), 0, s, (const float*)ca, n_orig, len_orig, frames_of(n_orig, 512), (const float*)cg,
-                     n_gen, len_gen, frames_of(n_gen, 512), pad_mode == AST_PAD_REFLECT ? 1025 : 1, 512, out);
+                     n_gen, len_gen, frames_of(n_gen, 512), min_count(pad_mode, 2048), 512, out);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -552,13 +463,12 @@ extern "C" int ast_chroma_similarity_len(const float* generated, int n_gen, cons
   const char* me = "ast_chroma_similarity_len";
   if (!original || !generated || !out) AST_FAIL("%s: null pointer", me);
   if (cut_check(me, B, n_gen, n_orig, 1024, pad_mode)) return -1;
-  const long need = chroma_pair_floats(B, n_gen, n_orig, 1024);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, chroma_pair_floats(B, n_gen, n_orig, 1024))) return -1;
   hipStream_t s = (hipStream_t)stream;
   float *cg, *co;
   chroma_pair_launch(generated, n_gen, len_gen, original, n_orig, len_orig, B, 1024, false, pad_mode, ws, &cg, &co, s);
   hipLaunchKernelGGL(pearson_frames_kernel, dim3(B), dim3(256), 0, s, (const float*)cg, n_gen, len_gen, frames_of(n_gen, 256), (const float*)co,
-                     n_orig, len_orig, frames_of(n_orig, 256), pad_mode == AST_PAD_REFLECT ? 513 : 1, 256, N_CHROMA, out);
+                     n_orig, len_orig, frames_of(n_orig, 256), min_count(pad_mode, 1024), 256, N_CHROMA, out);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -584,15 +494,14 @@ extern "C" int ast_pitch_correlation_len(const float* original, int n_orig, cons
   if (!original || !generated || !out) AST_FAIL("%s: null pointer", me);
   if (cut_check(me, B, n_orig, n_gen, 2048, pad_mode)) return -1;
   const int To = frames_of(n_orig, 512), Tg = frames_of(n_gen, 512);
-  const long need = (long)B * (To + Tg);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, (long)B * (To + Tg))) return -1;
   hipStream_t s = (hipStream_t)stream;
   float* po = ws;
   float* pg = ws + (size_t)B * To;
   pitch_mean_launch(original, B, n_orig, len_orig, len_gen, n_gen, pad_mode, po, s);
   pitch_mean_launch(generated, B, n_gen, len_gen, len_orig, n_orig, pad_mode, pg, s);
   hipLaunchKernelGGL(pearson_frames_kernel, dim3(B), dim3(256), 0, s, (const float*)po, n_orig, len_orig, To, (const float*)pg, n_gen, len_gen, Tg,
-                     pad_mode == AST_PAD_REFLECT ? 1025 : 1, 512, 1, out);
+                     min_count(pad_mode, 2048), 512, 1, out);
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -17,10 +17,8 @@
 namespace {
 constexpr int RMS_FRAME = 2048, RMS_HOP = 512;           // librosa.feature.rms defaults: frame_length, hop_length
 constexpr int RMS_TILE = 32;                             // consecutive frames of one clip per workgroup
-constexpr int MEL_BANDS = 128, MFCC_NFFT = 2048;         // librosa.feature.mfcc defaults: n_mels, n_fft
 constexpr int MM_CHUNK = 32;                             // frames per partial of the mel-mean pass
 constexpr int MM_MAX_MFCC = 20;                          // librosa's default n_mfcc; the scripts ask for 13
-constexpr float MM_TOP_DB = 80.f;                        // librosa.power_to_db's default
 
 // ---- 1. frame RMS, silent frames, clip level
 // The sum of squares of hop block j, wave-wide: lane l owns the samples 4 l .. 4 l + 3 and 256 + 4 l .. 256 + 4 l + 3 of the block,
@@ -162,39 +160,34 @@ __global__ __launch_bounds__(256) void window_ratio_kernel(const int32_t* __rest
 // ---- 3. MFCC time-mean.  Chunk blockIdx.x (frames MM_CHUNK * chunk ...) of clip blockIdx.y: thread j owns mel band j and adds
 // max(dB[t][j], clip maximum - 80) over the chunk's frames t < T_b ascending.  part[b][chunk][128]
 __global__ __launch_bounds__(128) void mel_mean_chunks_kernel(const float* __restrict__ db, const float* __restrict__ run_max, int n,
-                                                              const int32_t* __restrict__ n_samples, int lo, int hop, int run_frames, int T_max,
-                                                              int n_runs, int n_chunks, float* __restrict__ part) {
+                                                              const int32_t* __restrict__ n_samples, int lo, int hop, int T_max, int n_runs,
+                                                              int n_chunks, float* __restrict__ part) {
   __shared__ float red[2];
   const int t0 = blockIdx.x * MM_CHUNK, b = blockIdx.y, tid = threadIdx.x;
   const int T = 1 + clip_count(n_samples, b, lo, n) / hop;
   if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the barrier
-  float m = -INFINITY;                                   // the clip's maximum (exact in any order)
-  for (int r = tid; r < (T + run_frames - 1) / run_frames; r += 128) m = fmaxf(m, run_max[(size_t)b * n_runs + r]);
-  m = wave_max(m);
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  const float floor_db = fmaxf(red[0], red[1]) - MM_TOP_DB;
-  const float* row = db + ((size_t)b * T_max + t0) * MEL_BANDS + tid;
+  const float floor_db = clip_max_db<128>(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
+  const float* row = db + ((size_t)b * T_max + t0) * MEL_N + tid;
   float s = 0.f;
-  for (int t = 0; t < min(MM_CHUNK, T - t0); ++t) s += fmaxf(row[(size_t)t * MEL_BANDS], floor_db);
-  part[((size_t)b * n_chunks + blockIdx.x) * MEL_BANDS + tid] = s;
+  for (int t = 0; t < min(MM_CHUNK, T - t0); ++t) s += fmaxf(row[(size_t)t * MEL_N], floor_db);
+  part[((size_t)b * n_chunks + blockIdx.x) * MEL_N + tid] = s;
 }
 
 // clip blockIdx.x: thread j adds band j's chunks ascending in double and divides by T_b; thread k < n_mfcc then takes coefficient k
-// of the orthonormal DCT-II of the 128 means in double, summed over j ascending, the phase k (2 j + 1) reduced mod 512 in integers
+// of the orthonormal DCT-II of the 128 means in double, summed over j ascending (dct_phase, dct_scale: spec_common.h)
 __global__ __launch_bounds__(128) void mfcc_mean_finish_kernel(const float* __restrict__ part, int n, const int32_t* __restrict__ n_samples, int lo,
                                                                int hop, int n_chunks, int n_mfcc, float* __restrict__ out) {
-  __shared__ double mean[MEL_BANDS];
+  __shared__ double mean[MEL_N];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int T = 1 + clip_count(n_samples, b, lo, n) / hop;
   double s = 0.0;
-  for (int c = 0; c < (T + MM_CHUNK - 1) / MM_CHUNK; ++c) s += (double)part[((size_t)b * n_chunks + c) * MEL_BANDS + tid];
+  for (int c = 0; c < (T + MM_CHUNK - 1) / MM_CHUNK; ++c) s += (double)part[((size_t)b * n_chunks + c) * MEL_N + tid];
   mean[tid] = s / (double)T;
   __syncthreads();
   if (tid < n_mfcc) {
     double a = 0.0;
-    for (int j = 0; j < MEL_BANDS; ++j) a += mean[j] * cospi((double)((tid * (2 * j + 1)) & 511) / 256.0);
-    out[(size_t)b * n_mfcc + tid] = (float)(a * (tid ? 0.125 : 0.08838834764831845));   // sqrt(2 / 128), sqrt(1 / 128)
+    for (int j = 0; j < MEL_N; ++j) a += mean[j] * cospi((double)dct_phase(tid, j) / 256.0);
+    out[(size_t)b * n_mfcc + tid] = (float)(a * dct_scale<double>(tid));
   }
 }
 
@@ -215,12 +208,10 @@ __global__ __launch_bounds__(256) void gain_rows_kernel(const float* waves, int 
 }
 
 // host
-int rms_frames(int n) { return 1 + n / RMS_HOP; }
-int rms_tiles(int n) { return (rms_frames(n) + RMS_TILE - 1) / RMS_TILE; }
+int rms_tiles(int n) { return runs_of(frames_of(n, RMS_HOP), RMS_TILE); }
 long rms_ws_floats(int B, int n) { return 3L * B * rms_tiles(n); }            // a double and an int32 per tile
-int mm_frames(int n, int hop) { return 1 + n / hop; }
-int mm_chunks(int n, int hop) { return (mm_frames(n, hop) + MM_CHUNK - 1) / MM_CHUNK; }
-long mm_ws_floats(int B, int n, int hop) { return mel_db_pass1_floats(B, n, hop) + (long)B * mm_chunks(n, hop) * MEL_BANDS; }
+int mm_chunks(int n, int hop) { return runs_of(frames_of(n, hop), MM_CHUNK); }
+long mm_ws_floats(int B, int n, int hop) { return mfcc_pass1_floats(B, n, hop) + (long)B * mm_chunks(n, hop) * MEL_N; }
 }  // namespace
 
 extern "C" int ast_frame_rms_tile_frames(void) { return RMS_TILE; }
@@ -234,22 +225,16 @@ extern "C" int ast_frame_rms_len(const float* waves, int B, int n, const int32_t
   const char* me = "ast_frame_rms_len";
   if (!waves || !rms || !n_frames || !silent || !silence_ratio || !level) AST_FAIL("%s: null pointer", me);
   if (rows_check(me, B, n, RMS_FRAME, pad_mode)) return -1;
-  const long need = rms_ws_floats(B, n);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, rms_ws_floats(B, n))) return -1;
   if (reinterpret_cast<uintptr_t>(ws) & 7) AST_FAIL("%s: the workspace must be 8-byte aligned (it holds doubles)", me);
   hipStream_t s = (hipStream_t)stream;
-  const int T_max = rms_frames(n), n_tiles = rms_tiles(n);
+  const int T_max = frames_of(n, RMS_HOP), n_tiles = rms_tiles(n);
   double* tile_sum = reinterpret_cast<double*>(ws);
   int32_t* tile_silent = reinterpret_cast<int32_t*>(tile_sum + (size_t)B * n_tiles);
-  const bool reflect = pad_mode == AST_PAD_REFLECT;
-  if (reflect)
-    hipLaunchKernelGGL(frame_rms_tiles_kernel<true>, dim3(n_tiles, B), dim3(256), 0, s, waves, n, n_samples, threshold, T_max, n_tiles, rms,
-                       tile_silent, tile_sum);
-  else
-    hipLaunchKernelGGL(frame_rms_tiles_kernel<false>, dim3(n_tiles, B), dim3(256), 0, s, waves, n, n_samples, threshold, T_max, n_tiles, rms,
-                       tile_silent, tile_sum);
+  PAD_LAUNCH(pad_mode, (frame_rms_tiles_kernel<R>), dim3(n_tiles, B), dim3(256), s, waves, n, n_samples, threshold, T_max, n_tiles, rms, tile_silent,
+             tile_sum);
   hipLaunchKernelGGL(frame_rms_finish_kernel, dim3(B), dim3(64), 0, s, (const int32_t*)tile_silent, (const double*)tile_sum, n, n_samples,
-                     reflect ? RMS_FRAME / 2 + 1 : 1, n_tiles, n_frames, silent, silence_ratio, level, sumsq);
+                     min_count(pad_mode, RMS_FRAME), n_tiles, n_frames, silent, silence_ratio, level, sumsq);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -279,20 +264,16 @@ extern "C" int ast_mfcc_mean_len(const float* waves, int B, int n, const int32_t
                                  const int32_t* mel_table, float* ws, long ws_floats, float* out, void* stream) {
   const char* me = "ast_mfcc_mean_len";
   if (!waves || !out) AST_FAIL("%s: null pointer", me);
-  if (!mel_table) AST_FAIL("%s: null mel table (ast_mel_table fills one)", me);
-  if (n_mfcc < 1 || n_mfcc > MM_MAX_MFCC) AST_FAIL("%s: bad n_mfcc %d (1 .. %d)", me, n_mfcc, MM_MAX_MFCC);
-  if (hop != 256 && hop != 512) AST_FAIL("%s: bad hop %d (256 or 512)", me, hop);
-  if (rows_check(me, B, n, MFCC_NFFT, pad_mode)) return -1;
-  const long need = mm_ws_floats(B, n, hop);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (mfcc_check(me, n_mfcc, MM_MAX_MFCC, hop, mel_table) || rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, mm_ws_floats(B, n, hop))) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int T_max = mm_frames(n, hop), n_runs = mel_db_pass1_runs(n, hop), n_chunks = mm_chunks(n, hop);
-  const int lo = pad_mode == AST_PAD_REFLECT ? MFCC_NFFT / 2 + 1 : 1;
-  float* run_max = ws + (size_t)B * T_max * MEL_BANDS;
-  float* part = ws + mel_db_pass1_floats(B, n, hop);
-  mel_db_pass1_launch(waves, B, n, n_samples, hop, pad_mode, mel_table, ws, run_max, s);
+  const int T_max = frames_of(n, hop), n_runs = mfcc_runs(n, hop), n_chunks = mm_chunks(n, hop);
+  const int lo = min_count(pad_mode, WIDE_NFFT);
+  float* run_max = ws + (size_t)B * T_max * MEL_N;
+  float* part = ws + mfcc_pass1_floats(B, n, hop);
+  mel_db_launch(waves, B, n, n_samples, hop, pad_mode, mel_table, ws, run_max, s);
   hipLaunchKernelGGL(mel_mean_chunks_kernel, dim3(n_chunks, B), dim3(128), 0, s, (const float*)ws, (const float*)run_max, n, n_samples, lo, hop,
-                     ast_mfcc_run_frames(), T_max, n_runs, n_chunks, part);
+                     T_max, n_runs, n_chunks, part);
   hipLaunchKernelGGL(mfcc_mean_finish_kernel, dim3(B), dim3(128), 0, s, (const float*)part, n, n_samples, lo, hop, n_chunks, n_mfcc, out);
   AST_CHECK_LAUNCH();
   return 0;

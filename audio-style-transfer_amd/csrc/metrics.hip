@@ -15,7 +15,7 @@
 
 namespace {
 constexpr int MSE_HOP = 256, MSE_BINS = 513;             // N_FFT / HOP_LENGTH of evaluation_reconstruction.py
-constexpr int BE_NFFT = 2048, BE_HOP = 512, BE_BINS = 1025;   // librosa.stft defaults
+constexpr int BE_HOP = 512;                              // librosa.stft's default at n_fft 2048
 constexpr int BE_RUN = 5;                                // consecutive frames of one clip per workgroup (one partial per run)
 
 // ---- mse_spectrogram: frames 2 blockIdx.x and 2 blockIdx.x + 1 of pair blockIdx.y.  One FFT per frame pair on average: two
@@ -71,67 +71,41 @@ __global__ __launch_bounds__(256) void spec_mse_frames_kernel(const float* __res
   if (tid == 0) part[(size_t)b * P_max + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// out[b] = sum of the clip's ceil(T_b / 2) partials / (513 T_b): one wave per pair; lane l sums the partials l, l + 64, ...
-// ascending, lane 0 the 64 lanes ascending, all in double
+// out[b] = sum of the clip's ceil(T_b / 2) partials / (513 T_b): one wave per pair (wave_partials_sum)
 __global__ __launch_bounds__(64) void spec_mse_finish_kernel(const float* __restrict__ part, int n_orig, int n_gen,
                                                              const int32_t* __restrict__ len_orig, const int32_t* __restrict__ len_gen,
                                                              int P_max, int lo, float* __restrict__ out) {
   __shared__ double lane_sum[64];
-  const int b = blockIdx.x, l = threadIdx.x;
+  const int b = blockIdx.x;
   const int L = min(clip_count(len_orig, b, lo, n_orig), clip_count(len_gen, b, lo, n_gen));
   const int T = 1 + L / MSE_HOP;
-  double s = 0.0;
-  for (int p = l; p < (T + 1) / 2; p += 64) s += (double)part[(size_t)b * P_max + p];
-  lane_sum[l] = s;
-  __syncthreads();
-  if (l == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 64; ++i) tot += lane_sum[i];
-    out[b] = (float)(tot / ((double)MSE_BINS * (double)T));
-  }
+  const double tot = wave_partials_sum(part + (size_t)b * P_max, (T + 1) / 2, lane_sum);
+  if (threadIdx.x == 0) out[b] = (float)(tot / ((double)MSE_BINS * (double)T));
 }
 
-// ---- band energies: run blockIdx.x (frames BE_RUN * run ...) of clip blockIdx.y.  The 2048-point real FFT of a frame through
-// the 1024-point network: z[n] = x[2n] + i x[2n+1], then X[k] = E[k] + e^(-i pi k / 1024) O[k] with E, O the Hermitian split of
-// Z as above (Z[1024] = Z[0]).  Thread tid owns the bins tid + 256 m, m < 4 (thread 0 bin 1024 as well), keeps their window
-// values, twiddles and running sums of |X| in registers and stores them once: part[b][run][1025].
+// ---- band energies: run blockIdx.x (frames BE_RUN * run ...) of clip blockIdx.y.  The 2048-point real FFT of a frame
+// (frame_fft, spec_common.h); thread tid keeps the window values, the twiddles and the running sums of |X| of its bins
+// tid + 256 m, m < 4 (thread 0 of bin 1024 as well) in registers and stores the sums once: part[b][run][1025].
 template <bool REFLECT>
 __global__ __launch_bounds__(256) void band_energy_runs_kernel(const float* __restrict__ waves, int n, const int32_t* __restrict__ n_samples,
                                                                 int n_runs, float* __restrict__ part) {
   __shared__ float2 buf[2][NFFT];
   const int run = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int L = clip_count(n_samples, b, REFLECT ? BE_NFFT / 2 + 1 : 1, n);
+  const int L = clip_count(n_samples, b, REFLECT ? WIDE_NFFT / 2 + 1 : 1, n);
   const int T = 1 + L / BE_HOP, t0 = run * BE_RUN;
   if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the first barrier
   const int t1 = min(t0 + BE_RUN, T);
   const float* w = waves + (size_t)b * n;
-  float hann[4][2], tc[4], ts[4], acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int j = 2 * (tid + 256 * m);
-    hann[m][0] = 0.5f - 0.5f * cospif(2.f * j / BE_NFFT);
-    hann[m][1] = 0.5f - 0.5f * cospif(2.f * (j + 1) / BE_NFFT);
-    sincospif(-(float)(tid + 256 * m) / NFFT, &ts[m], &tc[m]);
-  }
+  FrameConsts<true> fc;
+  fc.init(tid);
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (int t = t0; t < t1; ++t) {
+    const int cur = frame_fft<true, REFLECT>(buf, w, t, BE_HOP, L, tid, fc);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int q = tid + 256 * m;
-      const int idx = t * BE_HOP + 2 * q - BE_NFFT / 2;
-      buf[0][q] = make_float2(clip_sample<REFLECT>(w, idx, L) * hann[m][0], clip_sample<REFLECT>(w, idx + 1, L) * hann[m][1]);
-    }
-    __syncthreads();
-    const int cur = fft1024_stages(buf, tid);            // = 1: the next frame's loads into buf[0] disturb no reader of buf[1]
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int k = tid + 256 * m;
-      const float2 z = buf[cur][k], c = buf[cur][(NFFT - k) & (NFFT - 1)];
-      const float er = 0.5f * (z.x + c.x), ei = 0.5f * (z.y - c.y), orr = 0.5f * (z.y + c.y), oi = -0.5f * (z.x - c.x);
-      acc[m] += cabs2(er + (orr * tc[m] - oi * ts[m]), ei + (orr * ts[m] + oi * tc[m]));
-    }
-    if (tid == 0) { const float2 z = buf[cur][0]; acc[4] += fabsf(z.x - z.y); }
+    for (int m = 0; m < 4; ++m) { const float2 x = own_bin<true>(buf[cur], tid, m, fc); acc[m] += cabs2(x.x, x.y); }
+    if (tid == 0) acc[4] += fabsf(last_real(buf[cur]));
   }
-  float* p = part + ((size_t)b * n_runs + run) * BE_BINS;
+  float* p = part + ((size_t)b * n_runs + run) * WIDE_BINS;
 #pragma unroll
   for (int m = 0; m < 4; ++m) p[tid + 256 * m] = acc[m];
   if (tid == 0) p[NFFT] = acc[4];
@@ -141,34 +115,21 @@ __global__ __launch_bounds__(256) void band_energy_runs_kernel(const float* __re
 __global__ __launch_bounds__(256) void band_energy_finish_kernel(const float* __restrict__ part, int n, const int32_t* __restrict__ n_samples,
                                                                  int lo, int n_runs, float* __restrict__ energy) {
   const int f = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-  if (f >= BE_BINS) return;
+  if (f >= WIDE_BINS) return;
   const int T = 1 + clip_count(n_samples, b, lo, n) / BE_HOP;
   const int runs = (T + BE_RUN - 1) / BE_RUN;
   double s = 0.0;
-  for (int r = 0; r < runs; ++r) s += (double)part[((size_t)b * n_runs + r) * BE_BINS + f];
-  energy[(size_t)b * BE_BINS + f] = (float)s;
+  for (int r = 0; r < runs; ++r) s += (double)part[((size_t)b * n_runs + r) * WIDE_BINS + f];
+  energy[(size_t)b * WIDE_BINS + f] = (float)s;
 }
 
-// Pearson's r of rows a[b], b[b] of n values (scipy.stats.pearsonr: means, centred sums, ratio), exactly 0 where it is not
-// finite (the reference's nan -> 0.0)
+// Pearson's r (pearson_r) of rows a[b], b[b] of n values, exactly 0 where it is not finite
 __global__ __launch_bounds__(256) void pearson_rows_kernel(const float* __restrict__ a, const float* __restrict__ b, int n,
                                                            float* __restrict__ out) {
   __shared__ double red[257];
-  const float* x = a + (size_t)blockIdx.x * n;
-  const float* y = b + (size_t)blockIdx.x * n;
-  double sx = 0.0, sy = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) { sx += (double)x[i]; sy += (double)y[i]; }
-  const double mx = block_sum_f64(sx, red) / n, my = block_sum_f64(sy, red) / n;
-  double sxy = 0.0, sxx = 0.0, syy = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const double dx = (double)x[i] - mx, dy = (double)y[i] - my;
-    sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
-  }
-  sxy = block_sum_f64(sxy, red); sxx = block_sum_f64(sxx, red); syy = block_sum_f64(syy, red);
-  if (threadIdx.x == 0) {
-    const double r = sxy / (sqrt(sxx) * sqrt(syy));
-    out[blockIdx.x] = (r == r && fabs(r) <= 1.7976931348623157e308) ? (float)fmin(fmax(r, -1.0), 1.0) : 0.f;
-  }
+  bool counts;
+  const double r = pearson_r(a + (size_t)blockIdx.x * n, b + (size_t)blockIdx.x * n, n, red, counts);
+  if (threadIdx.x == 0) out[blockIdx.x] = counts ? (float)r : 0.f;
 }
 
 // ---- MFCC: librosa.feature.mfcc(y, sr, n_mfcc, hop_length) with every other argument at its default, restated:
@@ -181,13 +142,11 @@ __global__ __launch_bounds__(256) void pearson_rows_kernel(const float* __restri
 // bin of every filter, 129 offsets into the weights, and the weights of the filters one after the other as float bits.  A bin
 // lies inside at most two triangles, so there are never more than 2 x 1025 weights.  What the kernel reads from the table is
 // clamped, so that a wrong table gives wrong numbers, not reads outside the workgroup's arrays.
-constexpr int MEL_N = 128, MEL_W_MAX = 2 * BE_BINS, MEL_WORDS = 2 * MEL_N + 1 + MEL_W_MAX;
-constexpr int MF_RUN = 5;                                // consecutive frames of one clip per workgroup (one maximum per run)
+constexpr int MEL_W_MAX = 2 * WIDE_BINS, MEL_WORDS = 2 * MEL_N + 1 + MEL_W_MAX;
 constexpr int DCT_FRAMES = 32;                           // frames per workgroup of the second pass
-constexpr float TOP_DB = 80.f, AMIN = 1e-10f;            // librosa.power_to_db defaults
 
-// pass 1: run blockIdx.x (frames MF_RUN * run ...) of clip blockIdx.y.  The frame's 2048-point real FFT as in
-// band_energy_runs_kernel; the power of the 1025 bins goes to LDS, then thread j < 128 owns mel band j: it sums its filter's
+// pass 1: run blockIdx.x (frames MF_RUN * run ...) of clip blockIdx.y.  The frame's 2048-point real FFT (frame_fft,
+// spec_common.h); the power of the 1025 bins goes to LDS, then thread j < 128 owns mel band j: it sums its filter's
 // weights x powers over the filter's own bins, ascending, takes the logarithm, stores db[b][t][j] and keeps its maximum.
 // run_max[b][run] = the maximum over the run's frames and the 128 bands (a maximum is exact in any order).
 template <bool REFLECT>
@@ -195,46 +154,28 @@ __global__ __launch_bounds__(256) void mel_db_runs_kernel(const float* __restric
                                                            const int32_t* __restrict__ mel, int T_max, int n_runs, float* __restrict__ db,
                                                            float* __restrict__ run_max) {
   __shared__ float2 buf[2][NFFT];
-  __shared__ float pw[BE_BINS], mw[MEL_W_MAX], red[2];
+  __shared__ float pw[WIDE_BINS], mw[MEL_W_MAX], red[2];
   const int run = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int L = clip_count(n_samples, b, REFLECT ? BE_NFFT / 2 + 1 : 1, n);
+  const int L = clip_count(n_samples, b, REFLECT ? WIDE_NFFT / 2 + 1 : 1, n);
   const int T = 1 + L / hop, t0 = run * MF_RUN;
   if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the first barrier
   const int t1 = min(t0 + MF_RUN, T);
   const float* w = waves + (size_t)b * n;
   int f_lo = 0, f_off = 0, f_n = 0;                      // mel band tid: its first bin, where its weights start, how many
   if (tid < MEL_N) {
-    f_lo = min(max(mel[tid], 0), BE_BINS);
+    f_lo = min(max(mel[tid], 0), WIDE_BINS);
     f_off = min(max(mel[MEL_N + tid], 0), MEL_W_MAX);
-    f_n = max(min(min(mel[MEL_N + tid + 1], MEL_W_MAX) - f_off, BE_BINS - f_lo), 0);
+    f_n = max(min(min(mel[MEL_N + tid + 1], MEL_W_MAX) - f_off, WIDE_BINS - f_lo), 0);
   }
   for (int i = tid; i < MEL_W_MAX; i += 256) mw[i] = __int_as_float(mel[2 * MEL_N + 1 + i]);   // read behind the loop's first barrier
-  float hann[4][2], tc[4], ts[4], vmax = -INFINITY;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int j = 2 * (tid + 256 * m);
-    hann[m][0] = 0.5f - 0.5f * cospif(2.f * j / BE_NFFT);
-    hann[m][1] = 0.5f - 0.5f * cospif(2.f * (j + 1) / BE_NFFT);
-    sincospif(-(float)(tid + 256 * m) / NFFT, &ts[m], &tc[m]);
-  }
+  FrameConsts<true> fc;
+  fc.init(tid);
+  float vmax = -INFINITY;
   for (int t = t0; t < t1; ++t) {
+    const int cur = frame_fft<true, REFLECT>(buf, w, t, hop, L, tid, fc);   // its barriers also stand between the last frame's readers of pw and the writes below
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int q = tid + 256 * m;
-      const int idx = t * hop + 2 * q - BE_NFFT / 2;
-      buf[0][q] = make_float2(clip_sample<REFLECT>(w, idx, L) * hann[m][0], clip_sample<REFLECT>(w, idx + 1, L) * hann[m][1]);
-    }
-    __syncthreads();
-    const int cur = fft1024_stages(buf, tid);            // = 1; its barriers also stand between the last frame's readers of pw and the writes below
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int k = tid + 256 * m;
-      const float2 z = buf[cur][k], c = buf[cur][(NFFT - k) & (NFFT - 1)];
-      const float er = 0.5f * (z.x + c.x), ei = 0.5f * (z.y - c.y), orr = 0.5f * (z.y + c.y), oi = -0.5f * (z.x - c.x);
-      const float xr = er + (orr * tc[m] - oi * ts[m]), xi = ei + (orr * ts[m] + oi * tc[m]);
-      pw[k] = xr * xr + xi * xi;
-    }
-    if (tid == 0) { const float2 z = buf[cur][0]; pw[NFFT] = (z.x - z.y) * (z.x - z.y); }
+    for (int m = 0; m < 4; ++m) pw[tid + 256 * m] = own_power<true>(buf[cur], tid, m, fc);
+    if (tid == 0) pw[NFFT] = last_power<true>(buf[cur]);
     __syncthreads();
     if (tid < MEL_N) {
       float s = 0.f;
@@ -250,16 +191,7 @@ __global__ __launch_bounds__(256) void mel_db_runs_kernel(const float* __restric
   if (tid == 0) run_max[(size_t)b * n_runs + run] = fmaxf(red[0], red[1]);
 }
 
-// the maximum of a clip's `runs` run maxima, to every thread of a 256-thread workgroup (red: 4 floats of LDS of its own)
-__device__ __forceinline__ float clip_max_db(const float* __restrict__ run_max, int runs, float* red) {
-  float m = -INFINITY;
-  for (int r = threadIdx.x; r < runs; r += 256) m = fmaxf(m, run_max[r]);
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-// cos(pi p / 256), p < 512: every phase of the DCT, k (2 j + 1) reduced mod 512 in integers, so exact to float32 rounding
+// cos(pi p / 256), p < 512: every phase of the DCT (dct_phase), so exact to float32 rounding
 __device__ __forceinline__ void dct_cos_table(float* ct) {
   for (int p = threadIdx.x; p < 512; p += 256) ct[p] = cospif(p / 256.f);
 }
@@ -267,8 +199,8 @@ __device__ __forceinline__ void dct_cos_table(float* ct) {
 __device__ __forceinline__ float dct_row(const float* __restrict__ x, const float* __restrict__ ct, int k) {
   float s = 0.f;
 #pragma unroll 8
-  for (int j = 0; j < MEL_N; ++j) s += x[j] * ct[(k * (2 * j + 1)) & 511];
-  return s * (k ? 0.125f : 0.08838834764831845f);        // sqrt(2 / 128), sqrt(1 / 128)
+  for (int j = 0; j < MEL_N; ++j) s += x[j] * ct[dct_phase(k, j)];
+  return s * dct_scale<float>(k);
 }
 
 // pass 2 of mfcc: frames DCT_FRAMES * blockIdx.x ... of clip blockIdx.y -> out[b][k][t], layout (B, n_mfcc, T_max) as librosa's.
@@ -282,7 +214,7 @@ __global__ __launch_bounds__(256) void mfcc_dct_kernel(const float* __restrict__
   const int T = 1 + clip_count(n_samples, b, lo, n) / hop;
   const int tl = tid & 31, t = t0 + tl;
   if (t0 < T) {                                          // uniform over the workgroup
-    const float floor_db = clip_max_db(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
+    const float floor_db = clip_max_db<256>(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
     dct_cos_table(ct);
     for (int i = tid; i < DCT_FRAMES * MEL_N; i += 256) {
       const int r = i >> 7, j = i & (MEL_N - 1);
@@ -309,8 +241,8 @@ __global__ __launch_bounds__(256) void mfcc_dist_frames_kernel(const float* __re
   const int T_g = 1 + clip_count(len_g, b, lo, n_g) / hop, T_r = 1 + clip_count(len_r, b, lo, n_r) / hop;
   const int T = min(T_g, T_r);
   if (t0 >= T) return;                                   // uniform over the workgroup, ahead of the first barrier
-  const float floor_g = clip_max_db(max_g + (size_t)b * runs_g, (T_g + MF_RUN - 1) / MF_RUN, red[0]) - TOP_DB;
-  const float floor_r = clip_max_db(max_r + (size_t)b * runs_r, (T_r + MF_RUN - 1) / MF_RUN, red[1]) - TOP_DB;
+  const float floor_g = clip_max_db<256>(max_g + (size_t)b * runs_g, (T_g + MF_RUN - 1) / MF_RUN, red[0]) - TOP_DB;
+  const float floor_r = clip_max_db<256>(max_r + (size_t)b * runs_r, (T_r + MF_RUN - 1) / MF_RUN, red[1]) - TOP_DB;
   dct_cos_table(ct);
   for (int i = tid; i < DCT_FRAMES * MEL_N; i += 256) {
     const int r = i >> 7, j = i & (MEL_N - 1);
@@ -331,55 +263,29 @@ __global__ __launch_bounds__(256) void mfcc_dist_frames_kernel(const float* __re
   }
 }
 
-// out[b] = the mean of the pair's T partials: one wave per pair; lane l sums the partials l, l + 64, ... ascending, lane 0 the
-// 64 lanes ascending, all in double
+// out[b] = the mean of the pair's T partials: one wave per pair (wave_partials_sum)
 __global__ __launch_bounds__(64) void mfcc_dist_finish_kernel(const float* __restrict__ part, int n_g, int n_r, const int32_t* __restrict__ len_g,
                                                               const int32_t* __restrict__ len_r, int lo, int hop, int P_max,
                                                               float* __restrict__ out) {
   __shared__ double lane_sum[64];
-  const int b = blockIdx.x, l = threadIdx.x;
+  const int b = blockIdx.x;
   const int T = 1 + min(clip_count(len_g, b, lo, n_g), clip_count(len_r, b, lo, n_r)) / hop;
-  double s = 0.0;
-  for (int p = l; p < T; p += 64) s += (double)part[(size_t)b * P_max + p];
-  lane_sum[l] = s;
-  __syncthreads();
-  if (l == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 64; ++i) tot += lane_sum[i];
-    out[b] = (float)(tot / (double)T);
-  }
+  const double tot = wave_partials_sum(part + (size_t)b * P_max, T, lane_sum);
+  if (threadIdx.x == 0) out[b] = (float)(tot / (double)T);
 }
 
-// host: what ast_mfcc_len and ast_mfcc_distance_len both refuse
-int mfcc_check(const char* name, int n_mfcc, int hop, const int32_t* mel_table) {
-  if (!mel_table) AST_FAIL("%s: null mel table (ast_mel_table fills one)", name);
-  if (n_mfcc < 1 || n_mfcc > MEL_N) AST_FAIL("%s: bad n_mfcc %d (1 .. %d)", name, n_mfcc, MEL_N);
-  if (hop != 256 && hop != 512) AST_FAIL("%s: bad hop %d (256 or 512)", name, hop);
-  return 0;
-}
-int mfcc_frames(int n, int hop) { return 1 + n / hop; }
-int mfcc_runs(int n, int hop) { return (mfcc_frames(n, hop) + MF_RUN - 1) / MF_RUN; }
-// floats of the dB rows and the run maxima of one batch
-long mfcc_pass1_floats(int B, int n, int hop) { return (long)B * ((long)mfcc_frames(n, hop) * MEL_N + mfcc_runs(n, hop)); }
-void mel_db_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel, float* db,
-                   float* run_max, hipStream_t s) {
-  const int T_max = mfcc_frames(n, hop), n_runs = mfcc_runs(n, hop);
-  if (pad_mode == AST_PAD_REFLECT)
-    hipLaunchKernelGGL(mel_db_runs_kernel<true>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, hop, mel, T_max, n_runs, db, run_max);
-  else
-    hipLaunchKernelGGL(mel_db_runs_kernel<false>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, hop, mel, T_max, n_runs, db, run_max);
-}
 // Slaney's mel scale (librosa.hz_to_mel, htk=False): linear below 1 kHz, logarithmic above
 double hz_to_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + log(f / 1000.0) / (log(6.4) / 27.0); }
 double mel_to_hz(double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
 }  // namespace
 
-// the first pass as curation.hip reaches it (spec_common.h)
-long mel_db_pass1_floats(int B, int n, int hop) { return mfcc_pass1_floats(B, n, hop); }
-int mel_db_pass1_runs(int n, int hop) { return mfcc_runs(n, hop); }
-void mel_db_pass1_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel, float* db,
-                         float* run_max, hipStream_t s) {
-  mel_db_launch(waves, B, n, n_samples, hop, pad_mode, mel, db, run_max, s);
+// the first pass and its sizes, for curation.hip as well (spec_common.h)
+int mfcc_runs(int n, int hop) { return runs_of(frames_of(n, hop), MF_RUN); }
+long mfcc_pass1_floats(int B, int n, int hop) { return (long)B * ((long)frames_of(n, hop) * MEL_N + mfcc_runs(n, hop)); }
+void mel_db_launch(const float* waves, int B, int n, const int32_t* n_samples, int hop, int pad_mode, const int32_t* mel, float* db,
+                   float* run_max, hipStream_t s) {
+  const int T_max = frames_of(n, hop), n_runs = mfcc_runs(n, hop);
+  PAD_LAUNCH(pad_mode, (mel_db_runs_kernel<R>), dim3(n_runs, B), dim3(256), s, waves, n, n_samples, hop, mel, T_max, n_runs, db, run_max);
 }
 
 extern "C" long ast_spec_mse_ws_floats(int B, int n_orig, int n_gen) {
@@ -389,42 +295,35 @@ extern "C" long ast_spec_mse_ws_floats(int B, int n_orig, int n_gen) {
 
 extern "C" int ast_spec_mse_len(const float* original, int n_orig, const float* generated, int n_gen, int B, const int32_t* len_orig,
                                 const int32_t* len_gen, int pad_mode, float* ws, long ws_floats, float* out, void* stream) {
-  if (!original || !generated || !out) AST_FAIL("ast_spec_mse_len: null pointer");
-  if (rows_check("ast_spec_mse_len", B, n_orig, NFFT, pad_mode) || rows_check("ast_spec_mse_len", B, n_gen, NFFT, pad_mode)) return -1;
+  const char* me = "ast_spec_mse_len";
+  if (!original || !generated || !out) AST_FAIL("%s: null pointer", me);
+  if (rows_check(me, B, n_orig, NFFT, pad_mode) || rows_check(me, B, n_gen, NFFT, pad_mode)) return -1;
   const int P_max = (2 + std::min(n_orig, n_gen) / MSE_HOP) / 2;        // frame pairs of the longest clip: ceil(T / 2)
-  if (!ws || ws_floats < (long)B * P_max) AST_FAIL("ast_spec_mse_len: workspace of %ld floats needed, got %ld", (long)B * P_max, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, (long)B * P_max)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const bool reflect = pad_mode == AST_PAD_REFLECT;
-  if (reflect)
-    hipLaunchKernelGGL(spec_mse_frames_kernel<true>, dim3(P_max, B), dim3(256), 0, s, original, n_orig, generated, n_gen, len_orig, len_gen, P_max, ws);
-  else
-    hipLaunchKernelGGL(spec_mse_frames_kernel<false>, dim3(P_max, B), dim3(256), 0, s, original, n_orig, generated, n_gen, len_orig, len_gen, P_max, ws);
+  PAD_LAUNCH(pad_mode, (spec_mse_frames_kernel<R>), dim3(P_max, B), dim3(256), s, original, n_orig, generated, n_gen, len_orig, len_gen, P_max, ws);
   hipLaunchKernelGGL(spec_mse_finish_kernel, dim3(B), dim3(64), 0, s, (const float*)ws, n_orig, n_gen, len_orig, len_gen, P_max,
-                     reflect ? NFFT / 2 + 1 : 1, out);
+                     min_count(pad_mode, NFFT), out);
   AST_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" long ast_band_energy_ws_floats(int B, int n) {
   if (B < 1 || n < 1) return 0;
-  return (long)B * ((1 + n / BE_HOP + BE_RUN - 1) / BE_RUN) * BE_BINS;
+  return (long)B * runs_of(frames_of(n, BE_HOP), BE_RUN) * WIDE_BINS;
 }
 
 extern "C" int ast_band_energy_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, float* ws, long ws_floats,
                                    float* energy, void* stream) {
-  if (!waves || !energy) AST_FAIL("ast_band_energy_len: null pointer");
-  if (rows_check("ast_band_energy_len", B, n, BE_NFFT, pad_mode)) return -1;
-  const int n_runs = (1 + n / BE_HOP + BE_RUN - 1) / BE_RUN;
-  const long need = (long)B * n_runs * BE_BINS;
-  if (!ws || ws_floats < need) AST_FAIL("ast_band_energy_len: workspace of %ld floats needed, got %ld", need, ws ? ws_floats : 0L);
+  const char* me = "ast_band_energy_len";
+  if (!waves || !energy) AST_FAIL("%s: null pointer", me);
+  if (rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  const int n_runs = runs_of(frames_of(n, BE_HOP), BE_RUN);
+  if (ws_check(me, ws, ws_floats, (long)B * n_runs * WIDE_BINS)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const bool reflect = pad_mode == AST_PAD_REFLECT;
-  if (reflect)
-    hipLaunchKernelGGL(band_energy_runs_kernel<true>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, n_runs, ws);
-  else
-    hipLaunchKernelGGL(band_energy_runs_kernel<false>, dim3(n_runs, B), dim3(256), 0, s, waves, n, n_samples, n_runs, ws);
-  hipLaunchKernelGGL(band_energy_finish_kernel, dim3((BE_BINS + 255) / 256, B), dim3(256), 0, s, (const float*)ws, n, n_samples,
-                     reflect ? BE_NFFT / 2 + 1 : 1, n_runs, energy);
+  PAD_LAUNCH(pad_mode, (band_energy_runs_kernel<R>), dim3(n_runs, B), dim3(256), s, waves, n, n_samples, n_runs, ws);
+  hipLaunchKernelGGL(band_energy_finish_kernel, dim3((WIDE_BINS + 255) / 256, B), dim3(256), 0, s, (const float*)ws, n, n_samples,
+                     min_count(pad_mode, WIDE_NFFT), n_runs, energy);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -454,8 +353,8 @@ extern "C" int ast_mel_table(int sample_rate, int32_t* table) {
   int off = 0;
   for (int i = 0; i < MEL_N; ++i) {
     int first = -1, count = 0;
-    for (int k = 0; k < BE_BINS; ++k) {
-      const double f = k * fmax / (BE_BINS - 1);
+    for (int k = 0; k < WIDE_BINS; ++k) {
+      const double f = k * fmax / (WIDE_BINS - 1);
       const double lower = (f - mel_f[i]) / (mel_f[i + 1] - mel_f[i]), upper = (mel_f[i + 2] - f) / (mel_f[i + 2] - mel_f[i + 1]);
       const double wgt = std::max(0.0, std::min(lower, upper)) * 2.0 / (mel_f[i + 2] - mel_f[i]);
       if (!(wgt > 0.0)) {
@@ -485,21 +384,21 @@ extern "C" long ast_mfcc_ws_floats(int B, int n, int hop) {
 
 extern "C" long ast_mfcc_distance_ws_floats(int B, int n_gen, int n_ref, int hop) {
   if (B < 1 || n_gen < 1 || n_ref < 1 || (hop != 256 && hop != 512)) return 0;
-  return mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * mfcc_frames(std::min(n_gen, n_ref), hop);
+  return mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * frames_of(std::min(n_gen, n_ref), hop);
 }
 
 extern "C" int ast_mfcc_len(const float* waves, int B, int n, const int32_t* n_samples, int n_mfcc, int hop, int pad_mode,
                             const int32_t* mel_table, float* ws, long ws_floats, float* out, void* stream) {
-  if (!waves || !out) AST_FAIL("ast_mfcc_len: null pointer");
-  if (mfcc_check("ast_mfcc_len", n_mfcc, hop, mel_table) || rows_check("ast_mfcc_len", B, n, BE_NFFT, pad_mode)) return -1;
-  const long need = mfcc_pass1_floats(B, n, hop);
-  if (!ws || ws_floats < need) AST_FAIL("ast_mfcc_len: workspace of %ld floats needed, got %ld", need, ws ? ws_floats : 0L);
+  const char* me = "ast_mfcc_len";
+  if (!waves || !out) AST_FAIL("%s: null pointer", me);
+  if (mfcc_check(me, n_mfcc, MEL_N, hop, mel_table) || rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, mfcc_pass1_floats(B, n, hop))) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int T_max = mfcc_frames(n, hop), n_runs = mfcc_runs(n, hop);
+  const int T_max = frames_of(n, hop), n_runs = mfcc_runs(n, hop);
   float* run_max = ws + (size_t)B * T_max * MEL_N;
   mel_db_launch(waves, B, n, n_samples, hop, pad_mode, mel_table, ws, run_max, s);
-  hipLaunchKernelGGL(mfcc_dct_kernel, dim3((T_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
-                     n_samples, pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1, hop, T_max, n_runs, n_mfcc, out);
+  hipLaunchKernelGGL(mfcc_dct_kernel, dim3(runs_of(T_max, DCT_FRAMES), B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
+                     n_samples, min_count(pad_mode, WIDE_NFFT), hop, T_max, n_runs, n_mfcc, out);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -509,21 +408,21 @@ extern "C" int ast_mfcc_distance_len(const float* generated, int n_gen, const fl
                                      long ws_floats, float* out, void* stream) {
   const char* me = "ast_mfcc_distance_len";
   if (!generated || !reference || !out) AST_FAIL("%s: null pointer", me);
-  if (mfcc_check(me, n_mfcc, hop, mel_table) || rows_check(me, B, n_gen, BE_NFFT, pad_mode) || rows_check(me, B, n_ref, BE_NFFT, pad_mode)) return -1;
-  const int P_max = mfcc_frames(std::min(n_gen, n_ref), hop);
-  const long need = mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * P_max;
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (mfcc_check(me, n_mfcc, MEL_N, hop, mel_table) || rows_check(me, B, n_gen, WIDE_NFFT, pad_mode) || rows_check(me, B, n_ref, WIDE_NFFT, pad_mode))
+    return -1;
+  const int P_max = frames_of(std::min(n_gen, n_ref), hop);
+  if (ws_check(me, ws, ws_floats, mfcc_pass1_floats(B, n_gen, hop) + mfcc_pass1_floats(B, n_ref, hop) + (long)B * P_max)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int Tg = mfcc_frames(n_gen, hop), Tr = mfcc_frames(n_ref, hop), runs_g = mfcc_runs(n_gen, hop), runs_r = mfcc_runs(n_ref, hop);
+  const int Tg = frames_of(n_gen, hop), Tr = frames_of(n_ref, hop), runs_g = mfcc_runs(n_gen, hop), runs_r = mfcc_runs(n_ref, hop);
   float* db_g = ws;
   float* max_g = db_g + (size_t)B * Tg * MEL_N;
   float* db_r = max_g + (size_t)B * runs_g;
   float* max_r = db_r + (size_t)B * Tr * MEL_N;
   float* part = max_r + (size_t)B * runs_r;
-  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  const int lo = min_count(pad_mode, WIDE_NFFT);
   mel_db_launch(generated, B, n_gen, len_gen, hop, pad_mode, mel_table, db_g, max_g, s);
   mel_db_launch(reference, B, n_ref, len_ref, hop, pad_mode, mel_table, db_r, max_r, s);
-  hipLaunchKernelGGL(mfcc_dist_frames_kernel, dim3((P_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)db_g,
+  hipLaunchKernelGGL(mfcc_dist_frames_kernel, dim3(runs_of(P_max, DCT_FRAMES), B), dim3(256), 0, s, (const float*)db_g,
                      (const float*)max_g, n_gen, len_gen, Tg, runs_g, (const float*)db_r, (const float*)max_r, n_ref, len_ref, Tr, runs_r, lo, hop,
                      n_mfcc, P_max, part);
   hipLaunchKernelGGL(mfcc_dist_finish_kernel, dim3(B), dim3(64), 0, s, (const float*)part, n_gen, n_ref, len_gen, len_ref, lo, hop, P_max, out);
@@ -545,13 +444,13 @@ extern "C" int ast_mfcc_distance_len(const float* generated, int n_gen, const fl
 // The rules of the kernels above hold: no atomics, one owner and a fixed order per output, counts clamped on the device.
 namespace {
 constexpr int ON_SR = 22050, ON_HOP = BE_HOP;            // librosa's defaults: sr, hop_length
-constexpr int ON_SHIFT = 1 + BE_NFFT / (2 * ON_HOP);     // 3: lag + the frames `center=True` pads on the left
+constexpr int ON_SHIFT = 1 + WIDE_NFFT / (2 * ON_HOP);     // 3: lag + the frames `center=True` pads on the left
 constexpr int ON_PRE_MAX = (3 * ON_SR / 100) / ON_HOP;   // 0.03 sr // hop = 1   \  librosa.onset.onset_detect's peak_pick arguments
 constexpr int ON_POST_MAX = (0 * ON_SR) / ON_HOP + 1;    // 0.00 sr // hop + 1 = 1 |  at 22 050 Hz and hop 512; the window of frame n is
 constexpr int ON_PRE_AVG = (ON_SR / 10) / ON_HOP;        // 0.10 sr // hop = 4     |  n - pre .. n + post - 1
 constexpr int ON_POST_AVG = (ON_SR / 10) / ON_HOP + 1;   // 0.10 sr // hop + 1 = 5 |
 constexpr int ON_WAIT = (3 * ON_SR / 100) / ON_HOP;      // 0.03 sr // hop = 1    /
-constexpr float ON_DELTA = 0.07f, F32_TINY = 1.17549435e-38f;
+constexpr float ON_DELTA = 0.07f;
 static_assert(ON_WAIT == 1, "the pick kernel's greedy pass keeps every second frame of a run of detections: wait = 1");
 constexpr int ENV_TILE = 8;                              // frames of one clip per workgroup of the envelope kernel
 constexpr int SS_MFCC = 20;                              // librosa.feature.mfcc's default n_mfcc: the rows of the recurrence matrix
@@ -584,7 +483,7 @@ __global__ __launch_bounds__(256) void onset_env_kernel(const float* __restrict_
     if (tid < ENV_TILE && t0 + tid < T_max) env[(size_t)b * T_max + t0 + tid] = 0.f;
     return;
   }
-  const float floor_db = clip_max_db(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
+  const float floor_db = clip_max_db<256>(run_max + (size_t)b * n_runs, (T + MF_RUN - 1) / MF_RUN, red) - TOP_DB;
   for (int i = tid; i < (ENV_TILE + 1) * MEL_N; i += 256) {
     const int r = i >> 7, j = i & (MEL_N - 1), u = t0 - ON_SHIFT + r;          // row r holds dB frame u
     x[r][j] = (u >= 0 && u < T) ? fmaxf(db[((size_t)b * T_max + u) * MEL_N + j], floor_db) : 0.f;
@@ -778,18 +677,18 @@ __global__ __launch_bounds__(64) void self_sim_finish_kernel(const int32_t* __re
 }
 
 // host: sizes and launches the onset and recurrence entries share
-int on_tiles(int n) { return (mfcc_frames(n, ON_HOP) + ENV_TILE - 1) / ENV_TILE; }
-int ss_chunks(int n) { return (mfcc_frames(n, ON_HOP) + CD_CHUNK - 1) / CD_CHUNK; }
+int on_tiles(int n) { return runs_of(frames_of(n, ON_HOP), ENV_TILE); }
+int ss_chunks(int n) { return runs_of(frames_of(n, ON_HOP), CD_CHUNK); }
 long on_strength_floats(int B, int n) { return mfcc_pass1_floats(B, n, ON_HOP) + 2L * B * on_tiles(n); }
-long on_detect_floats(int B, int n) { return on_strength_floats(B, n) + (long)B * mfcc_frames(n, ON_HOP); }
+long on_detect_floats(int B, int n) { return on_strength_floats(B, n) + (long)B * frames_of(n, ON_HOP); }
 long ss_rec_floats(int B, int n) {
-  return mfcc_pass1_floats(B, n, ON_HOP) + (long)B * SS_MFCC * mfcc_frames(n, ON_HOP) + (long)B * ss_chunks(n) * SS_PAIRS;
+  return mfcc_pass1_floats(B, n, ON_HOP) + (long)B * SS_MFCC * frames_of(n, ON_HOP) + (long)B * ss_chunks(n) * SS_PAIRS;
 }
 // mel dB rows -> envelope (-> mask, unless it is null) of one batch; ws: on_strength_floats(B, n)
 void onset_launch(const float* waves, int B, int n, const int32_t* counts, int pad_mode, const int32_t* mel, float* ws, float* env,
                   int32_t* mask, hipStream_t s) {
-  const int T_max = mfcc_frames(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_tiles = on_tiles(n);
-  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  const int T_max = frames_of(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_tiles = on_tiles(n);
+  const int lo = min_count(pad_mode, WIDE_NFFT);
   float* run_max = ws + (size_t)B * T_max * MEL_N;
   float* tile_min = run_max + (size_t)B * n_runs;
   float* tile_max = tile_min + (size_t)B * n_tiles;
@@ -803,13 +702,13 @@ void onset_launch(const float* waves, int B, int n, const int32_t* counts, int p
 // mel dB rows -> 20 coefficients -> squared distances -> R of one batch; ws: ss_rec_floats(B, n)
 void recurrence_launch(const float* waves, int B, int n, const int32_t* counts, int pad_mode, const int32_t* mel, float* ws, int32_t* R,
                        float* d2, hipStream_t s) {
-  const int T_max = mfcc_frames(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_chunks = ss_chunks(n);
-  const int lo = pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1;
+  const int T_max = frames_of(n, ON_HOP), n_runs = mfcc_runs(n, ON_HOP), n_chunks = ss_chunks(n);
+  const int lo = min_count(pad_mode, WIDE_NFFT);
   float* run_max = ws + (size_t)B * T_max * MEL_N;
   float* coef = run_max + (size_t)B * n_runs;
   float* part = coef + (size_t)B * SS_MFCC * T_max;
   mel_db_launch(waves, B, n, counts, ON_HOP, pad_mode, mel, ws, run_max, s);
-  hipLaunchKernelGGL(mfcc_dct_kernel, dim3((T_max + DCT_FRAMES - 1) / DCT_FRAMES, B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
+  hipLaunchKernelGGL(mfcc_dct_kernel, dim3(runs_of(T_max, DCT_FRAMES), B), dim3(256), 0, s, (const float*)ws, (const float*)run_max, n,
                      counts, lo, ON_HOP, T_max, n_runs, SS_MFCC, coef);
   hipLaunchKernelGGL(coef_dist_chunks_kernel, dim3(n_chunks, B), dim3(256), 0, s, (const float*)coef, n, counts, lo, T_max, n_chunks, part);
   hipLaunchKernelGGL(recurrence_kernel, dim3(B), dim3(256), 0, s, (const float*)part, n, counts, lo, n_chunks, R, d2);
@@ -828,7 +727,7 @@ extern "C" long ast_onset_strength_ws_floats(int B, int n) { return (B < 1 || n 
 extern "C" long ast_onset_detect_ws_floats(int B, int n) { return (B < 1 || n < 1) ? 0 : on_detect_floats(B, n); }
 extern "C" long ast_onset_accuracy_ws_floats(int B, int n_orig, int n_gen) {
   if (B < 1 || n_orig < 1 || n_gen < 1) return 0;
-  return B + on_detect_floats(B, n_orig) + on_detect_floats(B, n_gen) + (long)B * (mfcc_frames(n_orig, ON_HOP) + mfcc_frames(n_gen, ON_HOP));
+  return B + on_detect_floats(B, n_orig) + on_detect_floats(B, n_gen) + (long)B * (frames_of(n_orig, ON_HOP) + frames_of(n_gen, ON_HOP));
 }
 extern "C" long ast_recurrence_ws_floats(int B, int n) { return (B < 1 || n < 1) ? 0 : ss_rec_floats(B, n); }
 extern "C" long ast_self_similarity_distance_ws_floats(int B, int n_a, int n_b) {
@@ -839,9 +738,8 @@ extern "C" long ast_self_similarity_distance_ws_floats(int B, int n_a, int n_b) 
 extern "C" int ast_onset_strength_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table,
                                       float* ws, long ws_floats, float* out, void* stream) {
   const char* me = "ast_onset_strength_len";
-  if (onset_check(me, waves, waves, out, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
-  const long need = on_strength_floats(B, n);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (onset_check(me, waves, waves, out, mel_table) || rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, on_strength_floats(B, n))) return -1;
   onset_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, out, nullptr, (hipStream_t)stream);
   AST_CHECK_LAUNCH();
   return 0;
@@ -850,9 +748,8 @@ extern "C" int ast_onset_strength_len(const float* waves, int B, int n, const in
 extern "C" int ast_onset_detect_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table,
                                     float* ws, long ws_floats, int32_t* mask, void* stream) {
   const char* me = "ast_onset_detect_len";
-  if (onset_check(me, waves, waves, mask, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
-  const long need = on_detect_floats(B, n);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (onset_check(me, waves, waves, mask, mel_table) || rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, on_detect_floats(B, n))) return -1;
   onset_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, ws + on_strength_floats(B, n), mask, (hipStream_t)stream);
   AST_CHECK_LAUNCH();
   return 0;
@@ -862,13 +759,12 @@ extern "C" int ast_onset_accuracy_len(const float* original, int n_orig, const f
                                       const int32_t* len_gen, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats, float* out,
                                       void* stream) {
   const char* me = "ast_onset_accuracy_len";
-  if (onset_check(me, original, generated, out, mel_table) || rows_check(me, B, n_orig, BE_NFFT, pad_mode) ||
-      rows_check(me, B, n_gen, BE_NFFT, pad_mode))
+  if (onset_check(me, original, generated, out, mel_table) || rows_check(me, B, n_orig, WIDE_NFFT, pad_mode) ||
+      rows_check(me, B, n_gen, WIDE_NFFT, pad_mode))
     return -1;
-  const long need = ast_onset_accuracy_ws_floats(B, n_orig, n_gen);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (ws_check(me, ws, ws_floats, ast_onset_accuracy_ws_floats(B, n_orig, n_gen))) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int To = mfcc_frames(n_orig, ON_HOP), Tg = mfcc_frames(n_gen, ON_HOP);
+  const int To = frames_of(n_orig, ON_HOP), Tg = frames_of(n_gen, ON_HOP);
   int32_t* L = (int32_t*)ws;                             // the pair's common counts, then the two clips' chains and masks
   float* ws_o = ws + B;
   float* env_o = ws_o + on_strength_floats(B, n_orig);
@@ -877,7 +773,7 @@ extern "C" int ast_onset_accuracy_len(const float* original, int n_orig, const f
   int32_t* mask_o = (int32_t*)(env_g + (size_t)B * Tg);
   int32_t* mask_g = mask_o + (size_t)B * To;
   hipLaunchKernelGGL(pair_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, len_orig, n_orig, len_gen, n_gen,
-                     pad_mode == AST_PAD_REFLECT ? BE_NFFT / 2 + 1 : 1, B, L);
+                     min_count(pad_mode, WIDE_NFFT), B, L);
   onset_launch(original, B, n_orig, L, pad_mode, mel_table, ws_o, env_o, mask_o, s);
   onset_launch(generated, B, n_gen, L, pad_mode, mel_table, ws_g, env_g, mask_g, s);
   hipLaunchKernelGGL(onset_f1_kernel, dim3(B), dim3(256), 0, s, (const int32_t*)mask_o, To, (const int32_t*)mask_g, Tg, (const int32_t*)L, out);
@@ -888,9 +784,8 @@ extern "C" int ast_onset_accuracy_len(const float* original, int n_orig, const f
 extern "C" int ast_recurrence_len(const float* waves, int B, int n, const int32_t* n_samples, int pad_mode, const int32_t* mel_table, float* ws,
                                   long ws_floats, int32_t* R, float* dist2, void* stream) {
   const char* me = "ast_recurrence_len";
-  if (onset_check(me, waves, waves, R, mel_table) || rows_check(me, B, n, BE_NFFT, pad_mode)) return -1;
-  const long need = ss_rec_floats(B, n);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (onset_check(me, waves, waves, R, mel_table) || rows_check(me, B, n, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, ss_rec_floats(B, n))) return -1;
   recurrence_launch(waves, B, n, n_samples, pad_mode, mel_table, ws, R, dist2, (hipStream_t)stream);
   AST_CHECK_LAUNCH();
   return 0;
@@ -900,9 +795,8 @@ extern "C" int ast_self_similarity_distance_len(const float* a, int n_a, const f
                                                 const int32_t* len_b, int pad_mode, const int32_t* mel_table, float* ws, long ws_floats,
                                                 float* out, void* stream) {
   const char* me = "ast_self_similarity_distance_len";
-  if (onset_check(me, a, b, out, mel_table) || rows_check(me, B, n_a, BE_NFFT, pad_mode) || rows_check(me, B, n_b, BE_NFFT, pad_mode)) return -1;
-  const long need = ast_self_similarity_distance_ws_floats(B, n_a, n_b);
-  if (!ws || ws_floats < need) AST_FAIL("%s: workspace of %ld floats needed, got %ld", me, need, ws ? ws_floats : 0L);
+  if (onset_check(me, a, b, out, mel_table) || rows_check(me, B, n_a, WIDE_NFFT, pad_mode) || rows_check(me, B, n_b, WIDE_NFFT, pad_mode)) return -1;
+  if (ws_check(me, ws, ws_floats, ast_self_similarity_distance_ws_floats(B, n_a, n_b))) return -1;
   hipStream_t s = (hipStream_t)stream;
   float* ws_b = ws + ss_rec_floats(B, n_a);
   int32_t* Ra = (int32_t*)(ws_b + ss_rec_floats(B, n_b));
