@@ -210,6 +210,8 @@ _SIGS = {
     "ast_pitch_mean_len": ([vp, i32, i32, vp, vp, i32, i32, vp, vp], i32),
     "ast_pitch_correlation_ws_floats": ([i32, i32, i32], C.c_long),
     "ast_pitch_correlation_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
+    # 64-bit digest over the bytes of a list of device tensors (include/ast_hip.h, ast_amd/checkpoint.py)
+    "ast_state_digest": ([C.POINTER(vp), C.POINTER(C.c_longlong), i32, vp, vp], i32),
 }
 
 EXPORTS = tuple(_SIGS) + ("ast_last_error",)

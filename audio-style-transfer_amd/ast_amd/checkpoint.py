@@ -4,6 +4,8 @@
   'content_encoder', 'style_encoder', 'decoder', 'discriminator' (evaluation_style_transfer.py:246-252).  The modules of
   this package keep the reference's parameter/buffer names (spectral-norm `weight_orig/_u/_v`, BatchNorm buffers,
   `pos_encoder.pe`, ...), so checkpoints move both ways without key mapping.
+* `state_digest`, `save_full_state`, `check_trainer_entry`: the full-state checkpoint of `Trainer.save_state` / `load_state` -- the
+  same file with one more key, "trainer" ("Resuming").
 * `UnifiedStats`: Preprocessing_Dataset/compute_unified_stats.py:25-68 -- per-bin statistics over the STFT || CQT
   concatenation (2, T, 513 + 84) of every clip -- as a streaming device reduction (mean over clips of the per-clip mean; sqrt
   of the mean per-clip unbiased variance), saved in the train_set_stats/*.npz layout.  The CQT bins come from the device
@@ -33,6 +35,62 @@ def load_checkpoint(path, content_encoder=None, style_encoder=None, decoder=None
         if mod is not None:
             mod.load_state_dict(ckpt[key], strict=strict)
     return ckpt
+
+
+# ---- full-state checkpoints (Trainer.save_state / load_state; DESIGN 10, "Resuming") ----------------------------------------
+TRAINER_KEY = "trainer"
+STATE_VERSION = 1
+
+
+def state_digest(tensors) -> int:
+    """ast_state_digest over the exact bytes of the given device tensors, in list order (tests/state_digest_ref.py states the
+    function).  Contiguous tensors only: a strided view has no byte string of its own."""
+    import ctypes as C
+    ts = list(tensors)
+    for i, t in enumerate(ts):
+        if not t.is_contiguous():
+            raise ValueError(f"state_digest: tensor {i} is not contiguous")
+    n = len(ts)
+    ptrs = (C.c_void_p * max(n, 1))(*[ptr(t) if t.numel() else None for t in ts])
+    sizes = (C.c_longlong * max(n, 1))(*[t.numel() * t.element_size() for t in ts])
+    out = torch.zeros(1, dtype=torch.int64, device=ts[0].device if ts else "cuda")
+    check(lib().ast_state_digest(ptrs, sizes, n, ptr(out), stream()), "ast_state_digest")
+    return int(out.item()) & 0xFFFFFFFFFFFFFFFF
+
+
+def save_full_state(path, modules, trainer_entry, extra):
+    """The reference's four keys first and in their order (modules: the four in the order of KEYS), then the trainer's entry,
+    then the caller's extras."""
+    state = {key: mod.state_dict() for key, mod in zip(KEYS, modules)}
+    state[TRAINER_KEY] = trainer_entry
+    for k in extra:
+        if k in state:
+            raise ValueError(f"save_state: extra entry '{k}' would overwrite a checkpoint key")
+    state.update(extra)
+    torch.save(state, path)
+
+
+def trainer_entry(ckpt):
+    entry = ckpt.get(TRAINER_KEY) if isinstance(ckpt, dict) else None
+    if not isinstance(entry, dict):
+        raise ValueError(f"{TRAINER_KEY}: the file has no full-state entry (written by save_checkpoint, not save_state?)")
+    return entry
+
+
+def check_trainer_entry(entry, decoder, dtype, deterministic, world, n_params):
+    """Refuse, before anything is loaded, a full-state entry that does not fit the Trainer described by the arguments: a
+    ValueError that starts with the name of the field.  No partial loads."""
+    if entry.get("version") != STATE_VERSION:
+        raise ValueError(f"version: the file has format version {entry.get('version')!r}, this build reads {STATE_VERSION}")
+    want = dict(decoder=decoder, dtype=dtype, deterministic=deterministic, world=world, n_params=n_params)
+    for field, mine in want.items():
+        if field not in entry:
+            raise ValueError(f"{field}: missing from the file's '{TRAINER_KEY}' entry")
+        if entry[field] != mine:
+            raise ValueError(f"{field}: the file was written with {entry[field]!r}, this Trainer has {mine!r}")
+    for field in ("optim", "dropout", "step", "cfg", "digest"):
+        if field not in entry:
+            raise ValueError(f"{field}: missing from the file's '{TRAINER_KEY}' entry")
 
 
 class StftStats:

@@ -140,6 +140,13 @@ class LengthBucketSampler(torch.utils.data.Sampler):
     def set_epoch(self, epoch: int):
         self.epoch = epoch
 
+    def state_dict(self):
+        """What the batch order of the coming epochs depends on (kept in a full-state checkpoint: Trainer.save_state)."""
+        return {"epoch": int(self.epoch), "seed": int(self.seed)}
+
+    def load_state_dict(self, state):
+        self.epoch, self.seed = int(state["epoch"]), int(state["seed"])
+
     def __iter__(self):
         g = torch.Generator().manual_seed(self.seed + self.epoch)
         batches = []

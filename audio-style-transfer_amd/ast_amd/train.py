@@ -13,6 +13,7 @@ launches) is captured into a hipGraph and replayed.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
 
@@ -179,7 +180,13 @@ class Trainer:
         self.rank, self.world = rank, world
         self._check_deterministic()
         torch.manual_seed(seed)                      # identical replicas on every rank
-        ops._DropState.seed = 0x5EED + 1000003 * int(rank)   # ... but independent dropout masks: ranks hold different clips
+        ops._DropState.seed = self._drop_seed = 0x5EED + 1000003 * int(rank)   # ... but independent dropout masks: ranks hold different clips
+        # The rest of this Trainer's dropout stream ("Resuming"): its own device step counter, made at the first step, and
+        # the value ops._DropState.calls has when a step body starts -- fixed by the first capture or eager step, or by load_state.
+        self._drop_counter = None
+        self._drop_calls = None
+        self.steps = 0                               # steps taken (host count; Adam's own counters are G.step / D.step on the device)
+        self.progress = None                         # curriculum position in [0, 1] once set_progress() was called
         self.style, self.content = StyleEncoder(), ContentEncoder()
         self._simple = self.cfg.decoder == "simple"
         if self._simple:
@@ -662,9 +669,35 @@ class Trainer:
         det = self._deterministic()
         prev, config.deterministic = config.deterministic, det       # this step's eager launches and captures
         try:
-            return self._step(x, labels_host)
+            with self._drop_scope():
+                out = self._step(x, labels_host)
+            self.steps += 1
+            return out
         finally:
             config.deterministic = prev
+
+    @contextlib.contextmanager
+    def _drop_scope(self):
+        """This Trainer's dropout stream in place of the process-wide one for the length of a step: ops._DropState.seed and .counter
+        are the Trainer's own, and .calls, which every dropout site bumps, is put back afterwards.  What a step draws is then a
+        function of the Trainer's state (seed, _drop_calls, the device counter), not of what else the process has run."""
+        ds = ops._DropState
+        prev = (ds.seed, ds.counter, ds.calls)
+        ds.seed, ds.counter = self._drop_seed, self._own_counter()
+        try:
+            yield
+        finally:
+            ds.seed, ds.counter, ds.calls = prev
+
+    def _own_counter(self):
+        if self._drop_counter is None:
+            self._drop_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._drop_counter
+
+    def set_progress(self, progress: float):
+        """Curriculum position in [0, 1]: sets the gates of curriculum_gates() and is kept in a full-state checkpoint."""
+        self.progress = float(progress)
+        self.cfg = dataclasses.replace(self.cfg, **curriculum_gates(self.progress))
 
     def _step(self, x, labels_host):
         assert not labels_host.is_cuda, "pass labels on the host: avoids a device sync per step"
@@ -672,6 +705,9 @@ class Trainer:
         if self._dist and self._dist_in_graph is None:
             self._dist_in_graph = self._probe_collective_capture()
         if not self.cfg.use_graph or (self._matched and not self._dist_in_graph):
+            if self._drop_calls is None:             # a fresh process's first eager step starts from 0, as it always has
+                self._drop_calls = 0
+            ops._DropState.calls = self._drop_calls  # every eager step draws the seeds a capture made now would bake
             self.losses = self._step_body(x, labels_host)
             return self.losses
         segmented = not self._one_graph()
@@ -770,6 +806,92 @@ class Trainer:
         if self.rank == 0:
             save_checkpoint(path, self.content, self.style, self.decoder, self.disc, **extra)
 
+    # ------------------------------------------------------------------ resumable training ("Resuming")
+    # The TrainConfig fields a step reads through _graph_key and _sync_hyper: they travel with a full-state checkpoint.
+    _STATE_CFG = ("lr_g", "lr_d", "max_grad_norm", "w_rec", "w_nce", "w_margin", "w_hsic", "w_adv", "use_hsic", "use_nce", "use_adv",
+                  "betas", "eps")
+
+    def state_digest(self) -> int:
+        """64-bit digest (ast_state_digest) over the bytes of every tensor a step mutates, in _mutable_state() order."""
+        from .checkpoint import state_digest
+        self._own_counter()
+        return state_digest(self._mutable_state())
+
+    def _state_identity(self):
+        """What a full-state checkpoint must agree with before any of it is loaded."""
+        return dict(decoder=self.cfg.decoder, dtype=str(config.compute_dtype), deterministic=bool(self._deterministic()),
+                    world=int(self.world), n_params={"G": int(self.G.n), "D": int(self.D.n)})
+
+    def save_state(self, path, sampler=None, **extra):
+        """Everything a run needs to continue: the reference's four state_dicts under their own keys, first and in order (the file
+        loads through load_checkpoint and the reference's evaluation scripts), and one more entry, "trainer": Adam moments and step
+        counters of both groups, the dropout stream (device counter, seed, call base), step count, curriculum position, step
+        scalars, optionally a LengthBucketSampler's position, and the digest of the saved state.  Rank 0 writes, after
+        sync_buffers(), as save_checkpoint does."""
+        from . import checkpoint as ck
+        self.sync_buffers()
+        self._own_counter()
+        entry = dict(self._state_identity(), version=ck.STATE_VERSION)
+        entry["optim"] = {tag: {"m": g.m, "v": g.v, "step": g.step} for tag, g in (("G", self.G), ("D", self.D))}
+        entry["dropout"] = {"counter": self._drop_counter, "seed": 0x5EED, "calls": self._drop_calls}
+        entry["step"], entry["progress"] = int(self.steps), self.progress
+        entry["cfg"] = {k: getattr(self.cfg, k) for k in self._STATE_CFG}
+        entry["sampler"] = None if sampler is None else dict(sampler.state_dict())
+        entry["digest"] = self.state_digest()
+        if self.rank == 0:
+            ck.save_full_state(path, (self.content, self.style, self.decoder, self.disc), entry, extra)
+
+    def load_state(self, path, sampler=None):
+        """Continue from a save_state file (every rank loads the same one).  The state is copied INTO the existing flat buffers,
+        module buffers and counters -- the addresses captured graphs replay over -- and the digest stored in the file is verified
+        on the restored tensors.  A file that does not fit this Trainer, or whose digest does not match, raises a ValueError naming
+        the field and leaves the Trainer as it was.  Returns the checkpoint dict."""
+        from . import checkpoint as ck
+        ckpt = torch.load(path, map_location=self.device)
+        entry = ck.trainer_entry(ckpt)
+        ck.check_trainer_entry(entry, **self._state_identity())
+        self._own_counter()
+        state = self._mutable_state()
+        addrs = [t.data_ptr() for t in state]
+        saved = [t.clone() for t in state]
+        try:
+            with torch.no_grad():
+                for key, mod in zip(ck.KEYS, (self.content, self.style, self.decoder, self.disc)):
+                    mod.load_state_dict(ckpt[key], strict=True)
+                for tag, g in (("G", self.G), ("D", self.D)):
+                    for name in ("m", "v", "step"):
+                        getattr(g, name).copy_(entry["optim"][tag][name])
+                self._drop_counter.copy_(entry["dropout"]["counter"])
+            if [t.data_ptr() for t in self._mutable_state()] != addrs:
+                raise RuntimeError("load_state: a module rebound one of its tensors; captured graphs would replay over the old one")
+            got = self.state_digest()
+            if got != int(entry["digest"]):
+                raise ValueError(f"digest: the restored state hashes to {got:#018x}, the file says {int(entry['digest']):#018x}")
+        except Exception:
+            with torch.no_grad():
+                for t, sv in zip(state, saved):
+                    t.copy_(sv)
+            raise
+        # Host state, and what is derived from the tensors.  The packed weights need nothing: every step, captured ones included,
+        # starts by packing them again from the flat parameters (WeightBank.prepare; `hold` only lives inside a step), and a bank
+        # rebuilds its descriptors when ADDRESSES change, which they did not.  Captured graphs therefore stay -- unless they baked
+        # other dropout seeds than the run in the file drew.
+        self.cfg = dataclasses.replace(self.cfg, **{k: (tuple(v) if k == "betas" else v) for k, v in entry["cfg"].items()})
+        self._hyper_sent = None
+        self.steps, self.progress = int(entry["step"]), entry["progress"]
+        calls = entry["dropout"]["calls"]
+        if calls is not None and calls != self._drop_calls:
+            self._graphs.clear()
+            self._drop_calls = int(calls)
+        ops._DropState.seed = self._drop_seed = 0x5EED + 1000003 * int(self.rank)      # per rank, as in __init__: not from the file
+        for mod in (self.style, self.content, self.decoder, self.disc):
+            bank = mod.__dict__.get("_bank")
+            if bank is not None:
+                bank.hold = False
+        if sampler is not None and entry.get("sampler") is not None:
+            sampler.load_state_dict(entry["sampler"])
+        return ckpt
+
     def _graph_key(self, x, labels_host, segmented):
         """Everything a captured step bakes in: shapes, labels (host-side class layout), dtype, curriculum gates, Adam's
         betas / eps (kernel arguments), whether the gradient norm is clipped at all, and the front-end buffer addresses.
@@ -784,8 +906,8 @@ class Trainer:
         ts = [self.G.flat_p, self.G.m, self.G.v, self.G.step, self.D.flat_p, self.D.m, self.D.v, self.D.step]
         for m in (self.style, self.content, self.decoder, self.disc):
             ts += list(m.buffers())            # BN running stats / num_batches_tracked, spectral-norm u and v
-        if ops._DropState.counter is not None:
-            ts.append(ops._DropState.counter)
+        if self._drop_counter is not None:
+            ts.append(self._drop_counter)
         return ts
 
     def _capture(self, key, x, labels_host, segmented=False):
@@ -798,11 +920,18 @@ class Trainer:
         static_x = x.clone()
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
+        ops._DropState.calls = 0                     # (step() puts the process's own value back)
         with torch.cuda.stream(side):
             for _ in range(2):                       # warm-up: builds weight banks, const tensors, caches
                 self._step_body(static_x, labels_host)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # The dropout seeds baked below are seed + 7919 * (_drop_calls + 1, + 2, ...).  A Trainer's first capture takes the value the
+        # two warm-up steps leave behind (what the first capture of a fresh process has always baked); every later capture, and one
+        # made after load_state, starts from the same value again.
+        if self._drop_calls is None:
+            self._drop_calls = ops._DropState.calls
+        ops._DropState.calls = self._drop_calls
         if not segmented:
             dot = os.environ.get("AST_GRAPH_DOT")    # tools/graph_critical_path.py: the captured step's nodes and edges
             gph = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()

@@ -797,6 +797,21 @@ int ast_mfcc_mean_len(const float* waves, int B, int n, const int32_t* n_samples
 int ast_gain_rows_len(const float* waves, int B, int n, const int32_t* n_samples, const double* sumsq, double target_rms, float* out,
                       void* stream);
 
+/* ---- state digest: what a resumable checkpoint is verified with (csrc/digest.hip; DESIGN 10, "Resuming") -------------------
+ * The reference saves four state_dicts (evaluation_style_transfer.py:246-252) and has nothing that checks a restored run; this
+ * is the project's own.  *out (device, 8-byte aligned) = one 64-bit digest over the exact bytes of the n device tensors
+ * ptrs[e][0, nbytes[e]), in list order (ptrs and nbytes are HOST arrays):
+ *   mix64(SEED + sum_e mix64((mix64(e) ^ LEN_KEY) + nbytes[e]) + sum_i mix64(mix64(i) ^ w_i))   mod 2^64,
+ * w_i the i-th little-endian 32-bit word of the list (every entry starts a new word, its last word padded with zero bytes; i runs
+ * on over the entries), mix64 the splitmix64 finaliser, SEED 0x4153545F44494753, LEN_KEY 0xA5A5A5A5A5A5A5A5
+ * (tests/state_digest_ref.py is the same function in Python).  One flipped bit changes one term and so the digest; the word
+ * index sits inside the term, so swapped words change it; the terms are combined by wrap-around integer addition, so the value
+ * is the same for every launch geometry and every order in which the workgroups finish.  Any byte count, any pointer
+ * alignment (16-byte loads where the entry allows them, byte loads for a pointer that is not 4-byte aligned), zero-length
+ * entries (their pointer may be NULL) and n = 0.  A null list, a null out, n < 0, a negative size or a null pointer with a
+ * positive size return an error before anything is launched.  2 + (entries with bytes) launches on `stream`. */
+int ast_state_digest(const void* const* ptrs, const long long* nbytes, int n, unsigned long long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
