@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("AST_HIP_LIB") or os.path.join(_HERE, "libast_hip.so")
 
 F32, BF16 = 0, 1
 MAX_TAPS = 9
+IGEMM_ACCUMULATE, IGEMM_RELU, IGEMM_WS_ZEROED, IGEMM_STATS, IGEMM_BN_SUMS, IGEMM_BN_NO_RELU, IGEMM_PER_IMAGE = (1 << b for b in range(7))
+IGEMM_SLOTS_SHIFT, IGEMM_DET = 8, 4096      # ast_igemm flags (include/ast_hip.h: AST_IGEMM_*)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 

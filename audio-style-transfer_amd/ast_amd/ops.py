@@ -85,11 +85,16 @@ def _gemm_cost(g, esize, wgrad=False):
     return flops, nbytes
 
 
-def _igemm_config(g, dt):
-    """Tile plan the library picks for this geometry (reporting only)."""
-    import ctypes
+def _igemm_plan(g, dt):
+    """ast_igemm_plan's five integers.  Never cached: the planner reads its environment on every call."""
     out = (ctypes.c_int32 * 5)()
     check(lib().ast_igemm_plan(g, dt, ctypes.byref(out)), "ast_igemm_plan")
+    return out
+
+
+def _igemm_config(g, dt):
+    """Tile plan the library picks for this geometry (reporting only)."""
+    out = _igemm_plan(g, dt)
     if out[2] < 0:                                      # patch kernel: (tile rows) x 128 pixels x channels, slab bytes per pixel
         return f"patch{-out[0]}r{'(rows,' + str(-out[3]) + 'frag)' if out[3] < 0 else ''},{out[1]}ch,slab{-out[2]}B"
     return f"{out[0]}x{out[1]},k{out[2] * 16}B" + (f",split{out[3]}" if out[3] > 1 else "") + (f",kg{out[4]}" if out[4] > 1 else "")
@@ -104,8 +109,7 @@ def _ws_need(g, dt):
     v = _ws_cache.get(key)
     if v is None:
         v = int(lib().ast_igemm_ws_floats_det(g, dt) if det else lib().ast_igemm_ws_floats(g, dt))
-        if v < 0:
-            check(-1, "ast_igemm_ws_floats")
+        check(min(v, 0), "ast_igemm_ws_floats")
         _ws_cache[key] = v
     return v
 
@@ -123,7 +127,7 @@ def stat_slots(C):
 
 
 def _slot_flags(slots):
-    return 0 if slots == 64 else ((slots.bit_length() - 1) << 8)
+    return 0 if slots == 64 else ((slots.bit_length() - 1) << _lib.IGEMM_SLOTS_SHIFT)
 
 
 class _StatArena:
@@ -184,11 +188,8 @@ class BNLink:
 
 
 def in_stats_fusable(g, dt):
-    """True when ast_igemm can add per-IMAGE statistics of its output (flags bits 3 + 6): gathered or patch kernel, no split-K."""
-    import ctypes
-    out = (ctypes.c_int32 * 5)()
-    check(lib().ast_igemm_plan(g, dt, ctypes.byref(out)), "ast_igemm_plan")
-    return out[2] != 0 and _ws_need(g, dt) == 0 and not config.deterministic
+    """True when ast_igemm can add per-IMAGE statistics of its output (IGEMM_STATS | IGEMM_PER_IMAGE): gathered or patch kernel, no split-K."""
+    return _igemm_plan(g, dt)[2] != 0 and _ws_need(g, dt) == 0 and not config.deterministic
 
 
 def _igemm(src, wgt, bias, dst, g, flags=0, stats=None, bn=None, per_image=False):
@@ -198,18 +199,18 @@ def _igemm(src, wgt, bias, dst, g, flags=0, stats=None, bn=None, per_image=False
     need = _ws_need(g, dcode(src.dtype))
     if bn is not None:                          # [slots][Cd][3]: BatchNorm-backward sums of the dy this GEMM produces
         assert need == 0 and flags == 0
-        check(lib().ast_igemm_bn(ptr(src), ptr(wgt), ptr(bias), ptr(dst), g, dcode(src.dtype), 16 | (0 if bn.relu else 32) | _slot_flags(bn.slots), ptr(bn.table),
+        check(lib().ast_igemm_bn(ptr(src), ptr(wgt), ptr(bias), ptr(dst), g, dcode(src.dtype), _lib.IGEMM_BN_SUMS | (0 if bn.relu else _lib.IGEMM_BN_NO_RELU) | _slot_flags(bn.slots), ptr(bn.table),
                                  bn.table.numel(), ptr(bn.x), ptr(bn.scale), ptr(bn.shift), stream()), "ast_igemm_bn")
     else:
-        if stats is not None:                   # [slots][Cd][2] table filled by the epilogue (flags bit 3); never with split-K
+        if stats is not None:                   # [slots][Cd][2] table filled by the epilogue; never with split-K
             assert need == 0 and flags == 0
-            ws, need, flags = stats, stats.numel(), (8 | 64 if per_image else 8 | _slot_flags(stats.numel() // (2 * g.Cd)))
-        elif config.deterministic:                 # the atomic-free kernel instantiations (flags bit 12)
+            ws, need, flags = stats, stats.numel(), _lib.IGEMM_STATS | (_lib.IGEMM_PER_IMAGE if per_image else _slot_flags(stats.numel() // (2 * g.Cd)))
+        elif config.deterministic:                 # the atomic-free kernel instantiations
             ws = det_ws(need, src.device) if need > 0 else None         # one slab per K slice, summed in order by the finish pass
-            flags |= 4096
+            flags |= _lib.IGEMM_DET
         else:
             ws = _clean_scratch(need, src.device) if need > 0 else None    # persistent, handed back zeroed by the finish pass
-            flags |= 4 if need > 0 else 0
+            flags |= _lib.IGEMM_WS_ZEROED if need > 0 else 0
         check(lib().ast_igemm(ptr(src), ptr(wgt), ptr(bias), ptr(dst), g, dcode(src.dtype), flags, ptr(ws), need,
                               stream()), "ast_igemm")
     if PROFILE is not None:
@@ -374,7 +375,7 @@ def _bn_link_ready(link, geoms, x):
 class ResHeadFn(torch.autograd.Function):
     """The two convolutions that read a ResBlock's input -- conv1 (3x3) and the 1x1 shortcut, both with the block's
     stride (style_encoder.py:50, 64-70) -- as ONE autograd node: the second data gradient is accumulated into the
-    first one's result by the GEMM epilogue (flags bit 0) instead of an ATen add over the activation map."""
+    first one's result by the GEMM epilogue (IGEMM_ACCUMULATE) instead of an ATen add over the activation map."""
 
     @staticmethod
     def forward(ctx, x, w1, wd, pw1: PackedWeight, pwd: PackedWeight, stride, stats, in_stats=None):
@@ -409,7 +410,7 @@ class ResHeadFn(torch.autograd.Function):
                 _igemm(dc1, pw1.wb, None, dx, g)
             for g in gathers_transposed(N, Ho, Wo, pwd.Cop, H, W, Cs, 1, stride, 0):
                 if g.ntaps > 0:                  # a 1x1 stride-s conv reaches one output-parity class only
-                    _igemm(didn, pwd.wb, None, dx, g, flags=1)
+                    _igemm(didn, pwd.wb, None, dx, g, flags=_lib.IGEMM_ACCUMULATE)
         return dx, None, None, None, None, None, None, None
 
 
@@ -499,7 +500,7 @@ class LinearFn(torch.autograd.Function):
             _token_call("LinearFn", "skinny_gemm", rows, "", ptr(x), pw.weight.data_ptr() + 4 * pw.w_off, b, ptr(y), rows, pw.Co, pw.Ci, pw.s_co, pw.Cop, int(relu))
         else:
             g, _ = gather_direct(rows, 1, 1, pw.Cip, pw.Cop, 1, 1, 0)
-            _igemm(x, pw.wf, pw.bias_ptr_tensor(), y, g, 2 if relu else 0)
+            _igemm(x, pw.wf, pw.bias_ptr_tensor(), y, g, _lib.IGEMM_RELU if relu else 0)
         ctx.save_for_backward(x, y if relu else None)
         ctx.pw, ctx.relu = pw, relu
         return y

@@ -109,7 +109,7 @@ __device__ __forceinline__ void epi_pixel(const EpiCtx<T>& ec, const ast_gather_
 // address of the 64-slot table, 1 345 on a per-image table.  Every thread of the workgroup must arrive.
 // flags bits 8-11: log2 of the number of statistics slots (0 = 64): wide layers take fewer slots so that the consumer, which
 // reduces the table itself (ast_bn_apply_fwd / _bwd), reads at most C x slots = 4096 entries
-__host__ __device__ __forceinline__ int stat_slot_mask(const int flags) { const int l = (flags >> 8) & 15; return l ? (1 << l) - 1 : 63; }
+__host__ __device__ __forceinline__ int stat_slot_mask(const int flags) { const int l = (flags >> AST_IGEMM_SLOTS_SHIFT) & (AST_IGEMM_SLOTS_MASK >> AST_IGEMM_SLOTS_SHIFT); return l ? (1 << l) - 1 : 63; }
 
 template <int TN>
 __device__ __forceinline__ void epi_flush(float* ws, const bool bstats, const int Cd, float (&st1)[TN][4], float (&st2)[TN][4], const int tix,
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ s
   // flags bit 6: image-aligned tiles (no tile straddles two images), so that the fused statistics can go to per-IMAGE
   // slots (InstanceNorm2d: style_encoder.py:69); M_end = end of the tile's image, else M
   const int HWm_ = g.Hm * g.Wm;
-  const bool per_image = flags & 64;
+  const bool per_image = flags & AST_IGEMM_PER_IMAGE;
   const int MTI = (HWm_ + BM - 1) / BM;
   const int MT = per_image ? g.N * MTI : (M + BM - 1) / BM, NT = (g.Cd + BN - 1) / BN;
   const int chunk = gridDim.x >> 3;
@@ -399,18 +399,18 @@ __global__ __launch_bounds__(256 * KG) void igemm_kernel(const T* __restrict__ s
         }
   }
   // epilogue: lane owns pixel (col) fr of tile j and channels fq*4..fq*4+3 (rows) of tile i
-  const bool accumulate = flags & 1, relu = flags & 2;
+  const bool accumulate = flags & AST_IGEMM_ACCUMULATE, relu = flags & AST_IGEMM_RELU;
   const bool split = gridDim.z > 1;
   // flags bit 3: `ws` is a [64][Cd][2] table of per-channel (sum, sum of squares) slots and the tile adds the
   // statistics of the values it STORES (BatchNorm2d's batch statistics without a second pass over the output);
   // slot = tile index mod 64 keeps the f32 atomics off a single address per channel
-  const bool stats = !DET && (flags & 8) && !split;
+  const bool stats = !DET && (flags & AST_IGEMM_STATS) && !split;
   // flags bit 4: this launch is the data gradient that produces dy of a BatchNorm(+ReLU) layer whose input x (bn_x, same
   // geometry as dst) and forward coefficients are given: the tile adds the layer's backward sums (sum dz, sum dz*x, with
   // dz = dy * [fma(x, scale, shift) > 0]) of the values it stores into the [64][Cd][3] slot table `ws` -- the separate
   // pass over dy and x (ast_norm_bwd_sums) disappears.  bit 5: the layer has no ReLU (mask = 1).
-  const bool bstats = !DET && (flags & 16) && !split;
-  const bool bn_relu = !(flags & 32);
+  const bool bstats = !DET && (flags & AST_IGEMM_BN_SUMS) && !split;
+  const bool bn_relu = !(flags & AST_IGEMM_BN_NO_RELU);
   EpiCtx<T> ec{dst, bias, ws, bn_x, bn_scale, bn_shift, HWm, rcp_hw, rcp_w, accumulate, relu, stats, bstats, bn_relu};
   float st1[TN][4], st2[TN][4];
 #pragma unroll
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void igemm_direct_kernel(const T* __restrict__
       wreg[i][ks] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(wgtR, (rowoff != OOB && woff[ks] != OOB) ? rowoff + woff[ks] : OOB, 0, 0));
   }
 
-  const bool accumulate = flags & 1, relu = flags & 2, stats = !DET && (flags & 8), bstats = !DET && (flags & 16), bn_relu = !(flags & 32);
+  const bool accumulate = flags & AST_IGEMM_ACCUMULATE, relu = flags & AST_IGEMM_RELU, stats = !DET && (flags & AST_IGEMM_STATS), bstats = !DET && (flags & AST_IGEMM_BN_SUMS), bn_relu = !(flags & AST_IGEMM_BN_NO_RELU);
   EpiCtx<T> ec{dst, bias, ws, bn_x, bn_scale, bn_shift, HWm, rcp_hw, rcp_w, accumulate, relu, stats, bstats, bn_relu};
   float st1[TN][4], st2[TN][4];
 #pragma unroll
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(float* __restrict__ 
     }
     float v[4] = {a[0], a[1], a[2], a[3]};
     if (bias) for (int r = 0; r < 4; ++r) v[r] += bias[co + r];
-    store4<T>(dst + pix * g.Cd + co, v, flags & 1, flags & 2);
+    store4<T>(dst + pix * g.Cd + co, v, flags & AST_IGEMM_ACCUMULATE, flags & AST_IGEMM_RELU);
   }
 }
 
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(256, (WALL ? 2 : (TM * TN <= 8 ? 4 : 2))) void pcon
   // 64-bit address arithmetic), and the mode (plain / BatchNorm forward sums / backward sums) is a wave-uniform branch
   // around three straight-line bodies.  (The shared epilogue cost this kernel ~70 VALU per 4-value block and a dependent
   // bias load per block: 1 015 VALU per 144 MFMAs on the 64-channel layers.)
-  const bool accumulate = flags & 1, relu = flags & 2, stats = !DET && (flags & 8), bstats = !DET && (flags & 16), bn_relu = !(flags & 32);
+  const bool accumulate = flags & AST_IGEMM_ACCUMULATE, relu = flags & AST_IGEMM_RELU, stats = !DET && (flags & AST_IGEMM_STATS), bstats = !DET && (flags & AST_IGEMM_BN_SUMS), bn_relu = !(flags & AST_IGEMM_BN_NO_RELU);
   const __amdgpu_buffer_rsrc_t dstR = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, dst_bytes, 0x00020000);
   f32x4 bv[TN];
   {
@@ -965,8 +965,8 @@ __global__ __launch_bounds__(256, (WALL ? 2 : (TM * TN <= 8 ? 4 : 2))) void pcon
   else if (bstats) run(std::integral_constant<int, 2>{});
   else run(std::integral_constant<int, 0>{});
   PC_STAMP(4);
-  if (stats || bstats) epi_flush<TN>(ws, bstats, g.Cd, st1, st2, (flags & 64) ? ~n : (tix & stat_slot_mask(flags)), bn0, fr, fq,
-                                       ((flags & 64) || stat_slot_mask(flags) < 63) ? reinterpret_cast<float*>(pl) : nullptr);   // per-image tables only: with 64 slots the per-wave atomics are as fast (and one barrier pair cheaper)      // bit 6: per-image slots (tiles never straddle images)
+  if (stats || bstats) epi_flush<TN>(ws, bstats, g.Cd, st1, st2, (flags & AST_IGEMM_PER_IMAGE) ? ~n : (tix & stat_slot_mask(flags)), bn0, fr, fq,
+                                       ((flags & AST_IGEMM_PER_IMAGE) || stat_slot_mask(flags) < 63) ? reinterpret_cast<float*>(pl) : nullptr);   // per-image tables only: with 64 slots the per-wave atomics are as fast (and one barrier pair cheaper)      // bit 6: per-image slots (tiles never straddle images)
   PC_STAMP(5); PC_STAMP(6);
 }
 #ifdef AST_STAMPS
@@ -977,8 +977,8 @@ extern "C" int ast_debug_read_stamps(unsigned long long* host, int n) {
 
 // Tile plan of the patch kernel, or false when the geometry should stay on the gathered kernel.
 bool plan_pconv(const ast_gather_t& g, int dtype, PconvPlan& pp, int& slb, int& tn) {
-  const char* en = getenv("AST_PCONV");                      // read per call (host side only): tests toggle it at run time
-  if ((en && atoi(en) == 0) || g.ntaps < 2 || g.sh != 1 || g.sw != 1) return false;
+  // AST_PCONV and the three knobs below are read per call (host side only): tests toggle them at run time
+  if (!env_flag("AST_PCONV", true) || g.ntaps < 2 || g.sh != 1 || g.sw != 1) return false;
   const int ES = dtype == AST_BF16 ? 2 : 4;
   const int rowb = g.Cs * ES;
   if (rowb % 64) return false;
@@ -1055,8 +1055,7 @@ bool plan_pconv(const ast_gather_t& g, int dtype, PconvPlan& pp, int& slb, int& 
   // with their 64-channel tiles (one workgroup per CU, one or two slabs) it loses: 28.0 -> 51.9, 23.2 -> 32.3, 30.7 -> 44.1 us
   // (profiles/r03/pconv_wall_layers.txt).  AST_PCONV_WALL = 0: off, 1: wherever it fits, 2: wherever it fits with 32-channel tiles.
   {
-    const char* we = getenv("AST_PCONV_WALL");
-    const int mode = we ? atoi(we) : -1, nslab = rowb / slb;
+    const int mode = env_int("AST_PCONV_WALL", -1), nslab = rowb / slb;
     const int patch = pp.PH * pp.PW * slb;
     pp.wall = 0;
     if (dtype == AST_BF16 && g.ntaps >= 3 && mode != 0) {
@@ -1079,32 +1078,11 @@ bool plan_pconv(const ast_gather_t& g, int dtype, PconvPlan& pp, int& slb, int& 
   // exactness of the multiply-shift divisions (see pc_div / pc_div20) and 24-bit operands of the address products
   if ((double)g.N * pp.tiles_h * pp.tiles_w * pp.nct * std::max(pp.nct, pp.tiles_h * pp.tiles_w) >= 4294967296.0) return false;
   if (pp.PW >= 512 || g.Wm >= 512 || g.Ws >= (1 << 12) || g.Hs >= (1 << 12) || g.Cs * ES >= (1 << 13)) return false;
-  const char* mt = getenv("AST_PCONV_MIN_TILES");
-  const long min_tiles = mt ? atol(mt) : 192;
-  if (spatial * pp.nct < min_tiles) return false;                 // under-filled grids keep the K-split plans
+  if (spatial * pp.nct < env_int("AST_PCONV_MIN_TILES", 192)) return false;                 // under-filled grids keep the K-split plans
   return pp.lds <= (pp.wall ? 150 : 64) * 1024;
 }
 
-template <typename T, int SLB, int TM, int TN, bool WALL>
-int launch_pconv(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, const PconvPlan& pp, int flags,
-                 float* ws, const void* bn_x, const float* bn_scale, const float* bn_shift, hipStream_t s) {
-  static LdsAttrOnce attr;
-  if (int rc = attr.set((WALL ? 150 : 64) * 1024, {(const void*)pconv_kernel<T, SLB, TM, TN, WALL, false>, (const void*)pconv_kernel<T, SLB, TM, TN, WALL, true>})) return rc;
-  const int tiles = g.N * pp.tiles_h * pp.tiles_w * pp.nct;
-  const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  // (a persistent variant -- <= 3 workgroups per CU walking their XCD's tiles with the next patch prefetched into
-  // registers -- measured SLOWER, 41 -> 54 us on the 64->64-channel layer: the prefetch registers cost a wave per SIMD,
-  // and what the kernel lacks is overlap between workgroups, not bandwidth)
-  const int grid = (tiles + 7) / 8 * 8;
-  const auto k = (flags & 4096) ? pconv_kernel<T, SLB, TM, TN, WALL, true> : pconv_kernel<T, SLB, TM, TN, WALL, false>;      // bit 12: DET
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), pp.lds, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                     g, pp, flags, ws, src_bytes, wgt_bytes, (const T*)bn_x, bn_scale, bn_shift);
-  AST_CHECK_LAUNCH();
-  return 0;
-}
-
-struct IgemmPlan { int bm, bn, kch, nsplit, kt_per_split, depth, kgroups; const void* bn_x; const float* bn_scale; const float* bn_shift; };
+struct IgemmPlan { int bm, bn, kch, nsplit, kt_per_split, depth, kgroups; };
 
 IgemmPlan plan_igemm(const ast_gather_t& g, int M, int dtype) {
   const int E = dtype == AST_BF16 ? 8 : 4;
@@ -1126,7 +1104,7 @@ IgemmPlan plan_igemm(const ast_gather_t& g, int M, int dtype) {
   static const long kg_blocks = getenv("AST_IGEMM_KG_BLOCKS") ? atol(getenv("AST_IGEMM_KG_BLOCKS")) : 400;
   // K tiles of 64 elements per group and barrier (kch 8): 21.0 -> 19.0 us on average over the 25 such launches of a replayed
   // step (tools/knob_ab.sh; back-to-back isolated launches had preferred 32)
-  static const int kg_kch = getenv("AST_IGEMM_KG_KCH") ? atoi(getenv("AST_IGEMM_KG_KCH")) : 8;
+  static const int kg_kch = env_int("AST_IGEMM_KG_KCH", 8);
   if (p.bm == 64 && p.bn == 64 && blocks < kg_blocks && KT >= 16) { p.kgroups = 4; p.kch = kg_kch == 4 ? 4 : 8; }
   else if (blocks < 200 && KT >= 16 && (long)M * g.Cd <= (1L << 20)) p.nsplit = blocks < 120 ? 4 : 2;
   p.depth = 2;                                          // depth 4 measured no better (the loop is not latency-bound)
@@ -1148,140 +1126,203 @@ IgemmPlan plan_igemm(const ast_gather_t& g, int M, int dtype) {
 
 // igemm_direct_kernel applies to narrow layers whose weights fit in registers (see the kernel)
 bool direct_ok(const ast_gather_t& g, const IgemmPlan& p, int dtype) {
-  static const bool enabled = !(getenv("AST_IGEMM_DIRECT") && atoi(getenv("AST_IGEMM_DIRECT")) == 0);
+  static const bool enabled = env_flag("AST_IGEMM_DIRECT", true);
   const int E = dtype == AST_BF16 ? 8 : 4;
   const int nchunks = g.ntaps * (g.Cs / E);
   // measured per layer (tools/layer_profile.py, B=8 step): wins 15-30 % for <= 16 output channels and K <= 12 chunks
   // (2 M pixels x 8 ch x 72: 79 -> 59 us; 2.4 M x 16 x 72: 100 -> 75 us); loses for 32 channels or long K, where the
   // weight registers (TN x NKS fragments) push occupancy to 2 waves and every chunk still crosses L1 once (whole step:
   // 7.04 -> 6.91 ms with this rule, 7.10 with everything up to 32 channels x 36 chunks)
-  static const int max_cd = getenv("AST_IGEMM_DIRECT_CD") ? atoi(getenv("AST_IGEMM_DIRECT_CD")) : 16;
-  static const int max_chunks = getenv("AST_IGEMM_DIRECT_CHUNKS") ? atoi(getenv("AST_IGEMM_DIRECT_CHUNKS")) : 12;
+  static const int max_cd = env_int("AST_IGEMM_DIRECT_CD", 16);
+  static const int max_chunks = env_int("AST_IGEMM_DIRECT_CHUNKS", 12);
   if ((long)g.N * g.Hd * g.Wd >= (1L << 31)) return false;     // the kernel keeps destination pixel indices in 32 bits
   return enabled && g.Cd <= std::min(max_cd, 32) && nchunks <= std::min(max_chunks, 12) && p.nsplit == 1 && p.kgroups == 1 &&
          !getenv("AST_IGEMM_FORCE");
 }
 int direct_jt(int M) {                                       // pixel tiles of 16 per wave: keep >= ~2048 workgroups when M allows
-  static const int env = getenv("AST_IGEMM_DIRECT_JT") ? atoi(getenv("AST_IGEMM_DIRECT_JT")) : 0;
+  static const int env = env_int("AST_IGEMM_DIRECT_JT", 0);
   if (env > 0) return std::min(env, 64);
   return std::max(1, std::min(8, M / (64 * 2048)));
 }
 
-template <typename T, int TN, int NKS>
-int launch_direct(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, int M, int flags, float* ws,
-                  const IgemmPlan& p, hipStream_t s) {
-  const int E = 16 / sizeof(T), cpc = g.Cs / E;
-  int shift = -1;
-  if ((cpc & (cpc - 1)) == 0) { shift = 0; while ((1 << shift) < cpc) ++shift; }
-  const int jt = direct_jt(M);
-  const int tiles = ((M + 64 * jt - 1) / (64 * jt)) * ((g.Cd + TN * 16 - 1) / (TN * 16));
-  const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  const auto k = (flags & 4096) ? igemm_direct_kernel<T, TN, NKS, true> : igemm_direct_kernel<T, TN, NKS, false>;      // bit 12: DET
-  hipLaunchKernelGGL(k, dim3((tiles + 7) / 8 * 8), dim3(256), 0, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                     g, M, flags, ws, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)p.bn_x, p.bn_scale,
-                     p.bn_shift, jt);
+// ---- one plan per geometry: what the four query functions report, what the argument check rules on and what the launch
+// dispatches on are this one value, computed once per call
+enum ConvKernel { CONV_PATCH, CONV_DIRECT, CONV_GATHERED };
+struct ConvPlan {
+  ConvKernel kernel; int M;
+  IgemmPlan ig;                         // gathered and direct kernels
+  PconvPlan pp; int slb, tn, TM;        // patch kernel; TM is the INSTANTIATED template argument (pp.tm: fragments / 4 of the tile)
+  int jt, dtn, nks;                     // direct kernel: pixel tiles per wave, 16-channel fragments, K steps of 4 chunks (>= 1: a parity class may have no tap)
+  long ws_plain, ws_det;                // split-K workspace floats: ast_igemm_ws_floats / ast_igemm_ws_floats_det
+  bool split() const { return ws_plain > 0; }
+};
+
+ConvPlan plan_conv(const ast_gather_t& g, int dtype) {
+  ConvPlan c{};
+  c.M = g.N * g.Hm * g.Wm;
+  if (plan_pconv(g, dtype, c.pp, c.slb, c.tn)) {               // the patch kernel never splits K
+    c.kernel = CONV_PATCH;
+    // instantiated: 4, 8 and 12 fragments on 128-byte slabs, 8, 12 and 16 on 64-byte slabs; any other count takes the 12-fragment body
+    c.TM = c.slb == 128 ? (c.pp.tm == 1 || c.pp.tm == 2 ? c.pp.tm : 3) : (c.pp.tm == 2 || c.pp.tm == 4 ? c.pp.tm : 3);
+    return c;
+  }
+  c.ig = plan_igemm(g, c.M, dtype);
+  c.kernel = direct_ok(g, c.ig, dtype) ? CONV_DIRECT : CONV_GATHERED;
+  if (c.kernel == CONV_DIRECT) { c.jt = direct_jt(c.M); c.dtn = g.Cd <= 16 ? 1 : 2; c.nks = std::max(1, (g.ntaps * (g.Cs / (dtype == AST_BF16 ? 8 : 4)) + 3) / 4); }
+  if (c.ig.nsplit > 1) { c.ws_plain = (long)c.M * g.Cd; c.ws_det = c.ig.nsplit * c.ws_plain; }
+  return c;
+}
+
+// The one argument check of ast_igemm / ast_igemm_bn, before any dispatch, for all three kernels: a null or short table past
+// it is a write through a bad device pointer -- a GPU fault, not an error code.
+int check_conv_args(const ConvPlan& c, const ast_gather_t& g, int flags, const float* ws, long ws_floats, const void* bn_x,
+                    const float* bn_scale, const float* bn_shift) {
+  constexpr int STORE_MODS = AST_IGEMM_ACCUMULATE | AST_IGEMM_RELU;
+  const long slots = stat_slot_mask(flags) + 1L;
+  if ((flags & AST_IGEMM_DET) && (flags & (AST_IGEMM_STATS | AST_IGEMM_BN_SUMS | AST_IGEMM_PER_IMAGE)))
+    AST_FAIL("ast_igemm: the deterministic form (flags bit 12) has no fused statistics (flags 8 / 16 / 64)");
+  if (c.split()) {
+    if (flags & (AST_IGEMM_STATS | AST_IGEMM_BN_SUMS)) AST_FAIL("ast_igemm: fused statistics (flags 8 / 16) are not available for a split-K plan (ast_igemm_ws_floats > 0)");
+    const long need = (flags & AST_IGEMM_DET) ? c.ws_det : c.ws_plain;
+    if (!ws || ws_floats < need) AST_FAIL("ast_igemm: this plan splits K and needs a workspace of %ld floats (ast_igemm_ws_floats%s), got %ld", need, (flags & AST_IGEMM_DET) ? "_det" : "", ws ? ws_floats : 0L);
+  }
+  if ((flags & AST_IGEMM_BN_SUMS) && ((flags & (STORE_MODS | AST_IGEMM_STATS)) || !ws || ws_floats < slots * g.Cd * 3 || !bn_x || !bn_scale || !bn_shift))
+    AST_FAIL("ast_igemm: fused BatchNorm-backward sums need plain stores, a zeroed [slots][Cd][3] table and the layer's x / scale / shift");
+  if ((flags & AST_IGEMM_STATS) && ((flags & STORE_MODS) || !ws || ws_floats < ((flags & AST_IGEMM_PER_IMAGE) ? (long)g.N : slots) * g.Cd * 2))
+    AST_FAIL("ast_igemm: fused channel statistics need plain stores and a zeroed [slots][Cd][2] (per image: [N][Cd][2]) table");
+  if ((flags & AST_IGEMM_PER_IMAGE) && (!(flags & AST_IGEMM_STATS) || c.split() || c.kernel == CONV_DIRECT))
+    AST_FAIL("ast_igemm: per-image statistics (flag 64) need flag 8 and the patch or gathered kernel without split-K (ast_igemm_plan: kch != 0, no split)");
+  return 0;
+}
+
+// the arguments of one ast_igemm_bn call, as the launchers take them
+struct ConvCall {
+  const void* src; const void* wgt; const float* bias; void* dst; ast_gather_t g; int flags; float* ws;
+  const void* bn_x; const float* bn_scale; const float* bn_shift; hipStream_t s;
+  unsigned src_bytes(size_t es) const { return (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * es); }
+  unsigned wgt_bytes(size_t es) const { return (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * es); }
+  // log2 of the 16-byte chunks (E elements) per pixel, -1 when their count is no power of two
+  int chunk_shift(int E) const { const int cpc = g.Cs / E; int sh = -1; if ((cpc & (cpc - 1)) == 0) { sh = 0; while ((1 << sh) < cpc) ++sh; } return sh; }
+};
+
+template <typename T, int SLB, int TM, int TN, bool WALL>
+int launch_pconv(const ConvCall& a, const ConvPlan& c) {
+  const ast_gather_t& g = a.g; const PconvPlan& pp = c.pp;
+  static LdsAttrOnce attr;
+  if (int rc = attr.set((WALL ? 150 : 64) * 1024, {(const void*)pconv_kernel<T, SLB, TM, TN, WALL, false>, (const void*)pconv_kernel<T, SLB, TM, TN, WALL, true>})) return rc;
+  const int tiles = g.N * pp.tiles_h * pp.tiles_w * pp.nct;
+  // (a persistent variant -- <= 3 workgroups per CU walking their XCD's tiles with the next patch prefetched into
+  // registers -- measured SLOWER, 41 -> 54 us on the 64->64-channel layer: the prefetch registers cost a wave per SIMD,
+  // and what the kernel lacks is overlap between workgroups, not bandwidth)
+  const int grid = (tiles + 7) / 8 * 8;
+  const auto k = (a.flags & AST_IGEMM_DET) ? pconv_kernel<T, SLB, TM, TN, WALL, true> : pconv_kernel<T, SLB, TM, TN, WALL, false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), pp.lds, a.s, (const T*)a.src, (const T*)a.wgt, a.bias, (T*)a.dst,
+                     g, pp, a.flags, a.ws, a.src_bytes(sizeof(T)), a.wgt_bytes(sizeof(T)), (const T*)a.bn_x, a.bn_scale, a.bn_shift);
   AST_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename T>
-int dispatch_direct(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, int M, int flags, float* ws,
-                    const IgemmPlan& p, hipStream_t s) {
-  const int nks = (g.ntaps * (g.Cs / (16 / (int)sizeof(T))) + 3) / 4;
-#define AST_DK(TN_, K_) return launch_direct<T, TN_, K_>(src, wgt, bias, dst, g, M, flags, ws, p, s)
-  if (g.Cd <= 16) { if (nks <= 1) AST_DK(1, 1); if (nks <= 2) AST_DK(1, 2); AST_DK(1, 3); }
-  if (nks <= 1) AST_DK(2, 1); if (nks <= 2) AST_DK(2, 2); AST_DK(2, 3);
-#undef AST_DK
+template <typename T, int TN, int NKS>
+int launch_direct(const ConvCall& a, const ConvPlan& c) {
+  const ast_gather_t& g = a.g;
+  const int tiles = ((c.M + 64 * c.jt - 1) / (64 * c.jt)) * ((g.Cd + TN * 16 - 1) / (TN * 16));
+  const auto k = (a.flags & AST_IGEMM_DET) ? igemm_direct_kernel<T, TN, NKS, true> : igemm_direct_kernel<T, TN, NKS, false>;
+  hipLaunchKernelGGL(k, dim3((tiles + 7) / 8 * 8), dim3(256), 0, a.s, (const T*)a.src, (const T*)a.wgt, a.bias, (T*)a.dst,
+                     g, c.M, a.flags, a.ws, a.chunk_shift(16 / sizeof(T)), a.src_bytes(sizeof(T)), a.wgt_bytes(sizeof(T)),
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)a.bn_x, a.bn_scale, a.bn_shift, c.jt);
+  AST_CHECK_LAUNCH();
+  return 0;
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int KCH, int D, int KG, bool UT>
-int launch_igemm_ut(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, int M, int flags,
-                 float* ws, const IgemmPlan& p, hipStream_t s) {
+int launch_igemm_ut(const ConvCall& a, const ConvPlan& c) {
+  const ast_gather_t& g = a.g; const IgemmPlan& p = c.ig; const int M = c.M, flags = a.flags;
   constexpr int LDS = KG * 2 * (KCH / 4) * (BM + BN) * 64 + 64;
   static_assert(KG == 1 || (KG - 1) * (BM / 16) * (BN / 16) / 4 * 256 * 16 <= KG * 2 * (KCH / 4) * (BM + BN) * 64, "reduce buffer fits");
   static LdsAttrOnce attr;
   if (int rc = attr.set(LDS, {(const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>, (const void*)igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true>})) return rc;
-  const int E = 16 / sizeof(T);
-  const int cpc = g.Cs / E;
-  int shift = -1;
-  if ((cpc & (cpc - 1)) == 0) { shift = 0; while ((1 << shift) < cpc) ++shift; }
-  const int mtiles = (flags & 64) ? g.N * ((g.Hm * g.Wm + BM - 1) / BM) : (M + BM - 1) / BM;     // bit 6: image-aligned tiles
+  const int mtiles = (flags & AST_IGEMM_PER_IMAGE) ? g.N * ((g.Hm * g.Wm + BM - 1) / BM) : (M + BM - 1) / BM;     // image-aligned tiles
   const int tiles = mtiles * ((g.Cd + BN - 1) / BN);
   dim3 grid((tiles + 7) / 8 * 8, 1, p.nsplit);
-  if (p.nsplit > 1 && !(flags & (4 | 4096))) AST_HIP(hipMemsetAsync(ws, 0, sizeof(float) * (size_t)M * g.Cd, s));
-  const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  const unsigned wgt_bytes = (unsigned)((size_t)g.Cd * g.wtaps * g.Cs * sizeof(T));
-  const auto k = (flags & 4096) ? igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true> : igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>;      // bit 12: DET
-  hipLaunchKernelGGL(k, grid, dim3(256 * KG), LDS, s, (const T*)src, (const T*)wgt, bias, (T*)dst,
-                     g, M, flags, ws, p.kt_per_split, shift, src_bytes, wgt_bytes, 1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm,
-                     (const T*)p.bn_x, p.bn_scale, p.bn_shift);
+  if (p.nsplit > 1 && !(flags & (AST_IGEMM_WS_ZEROED | AST_IGEMM_DET))) AST_HIP(hipMemsetAsync(a.ws, 0, sizeof(float) * (size_t)M * g.Cd, a.s));
+  const auto k = (flags & AST_IGEMM_DET) ? igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, true> : igemm_kernel<T, BM, BN, WM, WN, KCH, D, KG, UT, false>;
+  hipLaunchKernelGGL(k, grid, dim3(256 * KG), LDS, a.s, (const T*)a.src, (const T*)a.wgt, a.bias, (T*)a.dst,
+                     g, M, flags, a.ws, p.kt_per_split, a.chunk_shift(16 / sizeof(T)), a.src_bytes(sizeof(T)), a.wgt_bytes(sizeof(T)),
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, (const T*)a.bn_x, a.bn_scale, a.bn_shift);
   if (p.nsplit > 1) {
     const size_t total = (size_t)M * (g.Cd >> 2);
-    hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, s, ws, bias,
-                       (T*)dst, g, M, flags, (flags & 4096) ? p.nsplit : 0);
+    hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, a.s, a.ws, a.bias,
+                       (T*)a.dst, g, M, flags, (flags & AST_IGEMM_DET) ? p.nsplit : 0);
   }
   AST_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int KCH, int D, int KG>
-int launch_igemm(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t& g, int M, int flags,
-                 float* ws, const IgemmPlan& p, hipStream_t s) {
-  const int cpc = g.Cs / (16 / (int)sizeof(T));
-  if (cpc % KCH == 0) return launch_igemm_ut<T, BM, BN, WM, WN, KCH, D, KG, true>(src, wgt, bias, dst, g, M, flags, ws, p, s);
-  return launch_igemm_ut<T, BM, BN, WM, WN, KCH, D, KG, false>(src, wgt, bias, dst, g, M, flags, ws, p, s);
+int launch_igemm(const ConvCall& a, const ConvPlan& c) {
+  return a.g.Cs / (16 / (int)sizeof(T)) % KCH == 0 ? launch_igemm_ut<T, BM, BN, WM, WN, KCH, D, KG, true>(a, c) : launch_igemm_ut<T, BM, BN, WM, WN, KCH, D, KG, false>(a, c);
+}
+
+// The instantiations, one table per kernel, matched on the plan's fields.  128x128, 128x64, 256x32 and 256x16 are reached
+// through AST_IGEMM_FORCE only (tools/igemm_sweep.py).  A plan without an instantiation is an error, never a neighbouring kernel.
+template <typename T>
+int dispatch_conv(const ConvCall& a, const ConvPlan& c) {
+  struct Entry { int k[4]; int (*fn)(const ConvCall&, const ConvPlan&); };
+  auto run = [&](const Entry* tab, size_t n, int k0, int k1, int k2, int k3, const char* what) -> int {
+    for (size_t i = 0; i < n; ++i) if (tab[i].k[0] == k0 && tab[i].k[1] == k1 && tab[i].k[2] == k2 && tab[i].k[3] == k3) return tab[i].fn(a, c);
+    AST_FAIL("ast_igemm: no %s instantiation for the plan (%d, %d, %d, %d)", what, k0, k1, k2, k3);
+  };
+  if (c.kernel == CONV_PATCH) {
+#define AST_PC(S_, M_, N_) {{S_, M_, N_, 0}, launch_pconv<T, S_, M_, N_, false>}, {{S_, M_, N_, 1}, launch_pconv<T, S_, M_, N_, true>}
+    static const Entry tab[] = {AST_PC(128, 1, 4), AST_PC(128, 1, 2), AST_PC(128, 2, 4), AST_PC(128, 2, 2), AST_PC(128, 3, 4), AST_PC(128, 3, 2),
+                                AST_PC(64, 2, 4),  AST_PC(64, 2, 2),  AST_PC(64, 4, 4),  AST_PC(64, 4, 2),  AST_PC(64, 3, 4),  AST_PC(64, 3, 2)};
+#undef AST_PC
+    return run(tab, sizeof(tab) / sizeof(tab[0]), c.slb, c.TM, c.tn, c.pp.wall, "pconv_kernel (SLB, TM, TN, WALL)");
+  }
+  if (c.kernel == CONV_DIRECT) {
+#define AST_DK(TN_, K_) {{TN_, K_, 0, 0}, launch_direct<T, TN_, K_>}
+    static const Entry tab[] = {AST_DK(1, 1), AST_DK(1, 2), AST_DK(1, 3), AST_DK(2, 1), AST_DK(2, 2), AST_DK(2, 3)};
+#undef AST_DK
+    return run(tab, sizeof(tab) / sizeof(tab[0]), c.dtn, c.nks, 0, 0, "igemm_direct_kernel (TN, NKS)");
+  }
+#define AST_IG(BM_, BN_, WM_, WN_, K_, KG_) {{BM_, BN_, K_, KG_}, launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, KG_>}
+  static const Entry tab[] = {AST_IG(128, 128, 2, 2, 8, 1), AST_IG(128, 128, 2, 2, 4, 1), AST_IG(128, 64, 2, 2, 8, 1), AST_IG(128, 64, 2, 2, 4, 1),
+                              AST_IG(64, 64, 2, 2, 8, 4),   AST_IG(64, 64, 2, 2, 4, 4),   AST_IG(64, 64, 2, 2, 8, 1),  AST_IG(64, 64, 2, 2, 4, 1),
+                              AST_IG(64, 128, 1, 4, 8, 1),  AST_IG(64, 128, 1, 4, 4, 1),  AST_IG(128, 32, 4, 1, 4, 1), AST_IG(128, 16, 4, 1, 4, 1),
+                              AST_IG(256, 32, 4, 1, 4, 1),  AST_IG(64, 32, 4, 1, 4, 1),   AST_IG(256, 16, 4, 1, 4, 1), AST_IG(64, 16, 4, 1, 4, 1)};
+#undef AST_IG
+  return run(tab, sizeof(tab) / sizeof(tab[0]), c.ig.bm, c.ig.bn, c.ig.kch, c.ig.kgroups, "igemm_kernel (BM, BN, KCH, KG)");
+}
+
+// the four query functions: false on a null or bad geometry (error set by check_gather) or a null result array
+bool query_plan(const ast_gather_t* gp, int dtype, bool out_ok, const char* who, ConvPlan& c) {
+  if (!gp || !out_ok || check_gather(gp, who)) return false;
+  c = plan_conv(*gp, dtype);
+  return true;
 }
 
 }  // namespace
 
-extern "C" long ast_igemm_ws_floats(const ast_gather_t* gp, int dtype) {
-  if (!gp || check_gather(gp, "ast_igemm_ws_floats")) return -1;
-  const int M = gp->N * gp->Hm * gp->Wm;
-  {
-    PconvPlan pp; int slb = 0, tn = 0;
-    if (plan_pconv(*gp, dtype, pp, slb, tn)) return 0;      // the patch kernel never splits K
-  }
-  const IgemmPlan p = plan_igemm(*gp, M, dtype);
-  return p.nsplit > 1 ? (long)M * gp->Cd : 0;
-}
-
-extern "C" long ast_igemm_ws_floats_det(const ast_gather_t* gp, int dtype) {
-  if (!gp || check_gather(gp, "ast_igemm_ws_floats_det")) return -1;
-  const int M = gp->N * gp->Hm * gp->Wm;
-  {
-    PconvPlan pp; int slb = 0, tn = 0;
-    if (plan_pconv(*gp, dtype, pp, slb, tn)) return 0;
-  }
-  const IgemmPlan p = plan_igemm(*gp, M, dtype);
-  return p.nsplit > 1 ? (long)p.nsplit * M * gp->Cd : 0;
-}
+extern "C" long ast_igemm_ws_floats(const ast_gather_t* gp, int dtype) { ConvPlan c; return query_plan(gp, dtype, true, "ast_igemm_ws_floats", c) ? c.ws_plain : -1; }
+extern "C" long ast_igemm_ws_floats_det(const ast_gather_t* gp, int dtype) { ConvPlan c; return query_plan(gp, dtype, true, "ast_igemm_ws_floats_det", c) ? c.ws_det : -1; }
 
 extern "C" int ast_igemm_plan(const ast_gather_t* gp, int dtype, int* out5) {
-  if (!gp || !out5 || check_gather(gp, "ast_igemm_plan")) return -1;
-  const IgemmPlan p = plan_igemm(*gp, gp->N * gp->Hm * gp->Wm, dtype);
-  out5[0] = p.bm; out5[1] = p.bn; out5[2] = p.kch; out5[3] = p.nsplit; out5[4] = p.kgroups;
-  {
-    PconvPlan pp; int slb = 0, tn = 0;
-    if (plan_pconv(*gp, dtype, pp, slb, tn)) {  // patch kernel: reported as BM = -(tile rows), kch = -(slab bytes)
-      out5[0] = -pp.TH; out5[1] = tn * 16; out5[2] = -slb; out5[3] = pp.rows ? -(pp.tm * 4) : 1; out5[4] = 1;
-      return 0;
-    }
-  }
-  if (direct_ok(*gp, p, dtype)) {                            // LDS-free narrow-layer kernel: kch = 0 marks it
-    out5[0] = 64 * direct_jt(gp->N * gp->Hm * gp->Wm); out5[1] = gp->Cd <= 16 ? 16 : 32; out5[2] = 0;
-  }
+  ConvPlan c;
+  if (!query_plan(gp, dtype, out5 != nullptr, "ast_igemm_plan", c)) return -1;
+  const int gathered[5] = {c.ig.bm, c.ig.bn, c.ig.kch, c.ig.nsplit, c.ig.kgroups};
+  const int patch[5] = {-c.pp.TH, c.tn * 16, -c.slb, c.pp.rows ? -(c.pp.tm * 4) : 1, 1};      // BM = -(tile rows), kch = -(slab bytes), -(fragments) for row blocks
+  const int direct[5] = {64 * c.jt, c.dtn * 16, 0, c.ig.nsplit, c.ig.kgroups};                // kch = 0 marks the LDS-free kernel
+  memcpy(out5, c.kernel == CONV_PATCH ? patch : c.kernel == CONV_DIRECT ? direct : gathered, sizeof(gathered));
   return 0;
 }
 
 // The pconv_kernel<T, SLB, TM, TN, WALL> instantiation ast_igemm launches for this geometry: out4 = {SLB, TM, TN, WALL}, returns 1;
-// 0 when the patch kernel does not take the geometry.  TM follows the dispatch chain in ast_igemm_bn.
+// 0 when the patch kernel does not take the geometry.
 extern "C" int ast_pconv_variant(const ast_gather_t* gp, int dtype, int* out4) {
-  if (!gp || !out4 || check_gather(gp, "ast_pconv_variant")) return -1;
-  PconvPlan pp; int slb = 0, tn = 0;
-  if (!plan_pconv(*gp, dtype, pp, slb, tn)) return 0;
-  const int tm = slb == 128 ? (pp.tm == 1 || pp.tm == 2 ? pp.tm : 3) : (pp.tm == 2 || pp.tm == 4 ? pp.tm : 3);
-  out4[0] = slb; out4[1] = tm; out4[2] = tn; out4[3] = pp.wall;
+  ConvPlan c;
+  if (!query_plan(gp, dtype, out4 != nullptr, "ast_pconv_variant", c)) return -1;
+  if (c.kernel != CONV_PATCH) return 0;
+  out4[0] = c.slb; out4[1] = c.TM; out4[2] = c.tn; out4[3] = c.pp.wall;
   return 1;
 }
 
@@ -1290,69 +1331,13 @@ extern "C" int ast_igemm_bn(const void* src, const void* wgt, const float* bias,
                             const float* bn_shift, void* stream) {
   if (int rc = check_gather(gp, "ast_igemm")) return rc;
   if (!src || !wgt || !dst) AST_FAIL("ast_igemm: null pointer");
-  const ast_gather_t g = *gp;
-  const int M = g.N * g.Hm * g.Wm;
-  hipStream_t s = (hipStream_t)stream;
-  IgemmPlan p = plan_igemm(g, M, dtype);
-  p.bn_x = bn_x; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
-  // checked before the patch dispatch: its deterministic instantiation ignores the statistics table
-  if ((flags & 4096) && (flags & (8 | 16 | 64))) AST_FAIL("ast_igemm: the deterministic form (flags bit 12) has no fused statistics (flags 8 / 16 / 64)");
-  {
-    PconvPlan pp; int slb = 0, tn = 0;
-    if (plan_pconv(g, dtype, pp, slb, tn)) {
-      if ((flags & 16) && ((flags & 11) || !ws || ws_floats < (stat_slot_mask(flags) + 1L) * g.Cd * 3 || !bn_x || !bn_scale || !bn_shift))
-        AST_FAIL("ast_igemm: fused BatchNorm-backward sums need plain stores, a zeroed [64][Cd][3] table and the layer's x / scale / shift");
-      if ((flags & 8) && ((flags & 3) || !ws || ws_floats < ((flags & 64) ? (long)g.N : stat_slot_mask(flags) + 1L) * g.Cd * 2)) AST_FAIL("ast_igemm: fused channel statistics need plain stores and a zeroed [64][Cd][2] (per image: [N][Cd][2]) table");
-#define AST_PC(S_, M_, N_) do { if (pp.wall) return launch_pconv<T, S_, M_, N_, true>(src, wgt, bias, dst, g, pp, flags, ws, bn_x, bn_scale, bn_shift, s); \
-                                return launch_pconv<T, S_, M_, N_, false>(src, wgt, bias, dst, g, pp, flags, ws, bn_x, bn_scale, bn_shift, s); } while (0)
-      AST_DISPATCH_T(dtype, {
-        if (slb == 128 && pp.tm == 1) { if (tn == 4) AST_PC(128, 1, 4); AST_PC(128, 1, 2); }
-        if (slb == 128 && pp.tm == 2) { if (tn == 4) AST_PC(128, 2, 4); AST_PC(128, 2, 2); }
-        if (slb == 128) { if (tn == 4) AST_PC(128, 3, 4); AST_PC(128, 3, 2); }
-        if (pp.tm == 2) { if (tn == 4) AST_PC(64, 2, 4); AST_PC(64, 2, 2); }
-        if (pp.tm == 4) { if (tn == 4) AST_PC(64, 4, 4); AST_PC(64, 4, 2); }
-        if (tn == 4) AST_PC(64, 3, 4); AST_PC(64, 3, 2);
-      });
-#undef AST_PC
-    }
-  }
-  // argument checks of the gathered and direct kernels (the patch kernel's are above): a null or short workspace here is a
-  // write through a bad device pointer -- a GPU fault, not an error code
-  if (p.nsplit > 1) {
-    if (flags & (8 | 16)) AST_FAIL("ast_igemm: fused statistics (flags 8 / 16) are not available for a split-K plan (ast_igemm_ws_floats > 0)");
-    const long need = (flags & 4096) ? (long)p.nsplit * M * g.Cd : (long)M * g.Cd;
-    if (!ws || ws_floats < need) AST_FAIL("ast_igemm: this plan splits K and needs a workspace of %ld floats (ast_igemm_ws_floats%s), got %ld", need, (flags & 4096) ? "_det" : "", ws ? ws_floats : 0L);
-  }
-  if ((flags & 16) && ((flags & 11) || !ws || ws_floats < (stat_slot_mask(flags) + 1L) * g.Cd * 3 || !bn_x || !bn_scale || !bn_shift))
-    AST_FAIL("ast_igemm: fused BatchNorm-backward sums need plain stores, a zeroed [64][Cd][3] table and the layer's x / scale / shift");
-  if ((flags & 8) && !(flags & 64) && ((flags & 3) || !ws || ws_floats < (stat_slot_mask(flags) + 1L) * g.Cd * 2))
-    AST_FAIL("ast_igemm: fused channel statistics need plain stores and a zeroed [64][Cd][2] table");
-  if (flags & 64) {
-    if (!(flags & 8) || (flags & 3) || p.nsplit > 1 || direct_ok(g, p, dtype)) AST_FAIL("ast_igemm: per-image statistics (flag 64) need flag 8, plain stores and the gathered kernel (ast_igemm_plan: kch > 0, no split)");
-    if (!ws || ws_floats < (long)g.N * g.Cd * 2) AST_FAIL("ast_igemm: per-image statistics need a zeroed [N][Cd][2] table");
-  }
-  if (direct_ok(g, p, dtype)) { AST_DISPATCH_T(dtype, { return dispatch_direct<T>(src, wgt, bias, dst, g, M, flags, ws, p, s); }); }
-#define AST_IG(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 1>(src, wgt, bias, dst, g, M, flags, ws, p, s)
-#define AST_IG4(BM_, BN_, WM_, WN_, K_) return launch_igemm<T, BM_, BN_, WM_, WN_, K_, 2, 4>(src, wgt, bias, dst, g, M, flags, ws, p, s)
-  AST_DISPATCH_T(dtype, {
-    if (p.bm == 128 && p.bn == 128) { if (p.kch == 8) AST_IG(128, 128, 2, 2, 8); else AST_IG(128, 128, 2, 2, 4); }
-    if (p.bm == 128 && p.bn == 64) { if (p.kch == 8) AST_IG(128, 64, 2, 2, 8); else AST_IG(128, 64, 2, 2, 4); }
-    if (p.bm == 64 && p.bn == 64 && p.kgroups == 4) { if (p.kch == 8) AST_IG4(64, 64, 2, 2, 8); else AST_IG4(64, 64, 2, 2, 4); }
-    if (p.bm == 64 && p.bn == 64) { if (p.kch == 8) AST_IG(64, 64, 2, 2, 8); else AST_IG(64, 64, 2, 2, 4); }
-    if (p.bm == 64 && p.bn == 128) { if (p.kch == 8) AST_IG(64, 128, 1, 4, 8); else AST_IG(64, 128, 1, 4, 4); }
-    if (p.bm == 128 && p.bn == 32) AST_IG(128, 32, 4, 1, 4);
-    if (p.bm == 128 && p.bn == 16) AST_IG(128, 16, 4, 1, 4);
-    if (p.bm == 256 && p.bn == 32) AST_IG(256, 32, 4, 1, 4);
-    if (p.bm == 64 && p.bn == 32) AST_IG(64, 32, 4, 1, 4);
-    if (p.bm == 256 && p.bn == 16) AST_IG(256, 16, 4, 1, 4);
-    AST_IG(64, 16, 4, 1, 4);
-  });
-#undef AST_IG
-#undef AST_IG4
-  return 0;
+  const ConvCall a{src, wgt, bias, dst, *gp, flags, ws, bn_x, bn_scale, bn_shift, (hipStream_t)stream};
+  const ConvPlan c = plan_conv(a.g, dtype);
+  if (int rc = check_conv_args(c, a.g, flags, ws, ws_floats, bn_x, bn_scale, bn_shift)) return rc;
+  AST_DISPATCH_T(dtype, { return dispatch_conv<T>(a, c); });
 }
 
 extern "C" int ast_igemm(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t* gp,
                          int dtype, int flags, float* ws, long ws_floats, void* stream) {
-  return ast_igemm_bn(src, wgt, bias, dst, gp, dtype, flags & ~48, ws, ws_floats, nullptr, nullptr, nullptr, stream);
+  return ast_igemm_bn(src, wgt, bias, dst, gp, dtype, flags & ~(AST_IGEMM_BN_SUMS | AST_IGEMM_BN_NO_RELU), ws, ws_floats, nullptr, nullptr, nullptr, stream);
 }

@@ -405,7 +405,7 @@ extern "C" int ast_recon_loss(const float* out, const float* tgt, int64_t tgt_ld
   if (total >= (1ull << 31)) AST_FAIL("ast_recon_loss: more than 2^31 bins per section");
   // every workgroup ends in 5 same-address f32 atomics, which serialise at ~10 ns each (1024 workgroups of 256: ~50 of the
   // kernel's 95 us; 4608: +250 us): the same 256 K threads as 256 workgroups of 1024
-  static const int max_blocks = getenv("AST_RECON_BLOCKS") ? atoi(getenv("AST_RECON_BLOCKS")) : 256;
+  static const int max_blocks = env_int("AST_RECON_BLOCKS", 256);
   const int grid = (int)std::min<size_t>((total + 1023) / 1024, (size_t)std::max(1, max_blocks));
   hipLaunchKernelGGL(recon_loss_kernel<false>, dim3(grid), dim3(1024), 0, s, out, tgt, tgt_ld, B, S, T, Fq, c_mse, c_mag, c_phase, c_temporal,
                      c_spectral, sums, grad, 1);

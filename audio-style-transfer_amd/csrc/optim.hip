@@ -113,7 +113,7 @@ extern "C" int ast_sumsq(const float* x, int64_t n, float* out, void* stream) {
   if (((uintptr_t)x) & 15) AST_FAIL("ast_sumsq: x must be 16-byte aligned");
   // one same-address f32 atomic per workgroup, ~11 ns each once they queue up: 2048 workgroups 38 us, 1024 28 us,
   // 512 23 us, 256 21 us (5.9 TB/s) for the 31 M-parameter gradient (tools/sumsq_time.py)
-  static const int max_blocks = getenv("AST_SUMSQ_BLOCKS") ? atoi(getenv("AST_SUMSQ_BLOCKS")) : 256;
+  static const int max_blocks = env_int("AST_SUMSQ_BLOCKS", 256);
   const int grid = (int)std::min<size_t>(((size_t)n / 4 + 255) / 256 + 1, (size_t)std::max(1, max_blocks));
   hipLaunchKernelGGL(sumsq_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (size_t)n, out);
   AST_CHECK_LAUNCH();

@@ -58,32 +58,43 @@ typedef struct ast_gather_t {
 /* dst[pix][co] (+)= sum_{t,c} src[gather(pix,t)][c] * wgt[co][wtap[t]][c] + bias[co]
  * Replaces: nn.Conv2d fwd/bwd-data (style_encoder.py:50-67, new_decoder.py:29-61),
  * nn.ConvTranspose2d fwd/bwd-data (new_decoder.py:72-96), nn.Linear fwd/bwd-data.
- * flags: bit0 accumulate into dst, bit1 ReLU, bit2 the split-K workspace is already zero (the finish pass
- * always hands it back zeroed, so a persistent workspace never needs a memset), bit3 `ws` is a zeroed
- * [64][Cd][2] f32 table and every tile adds (sum, sum of squares) of the values it stores into slot
- * (tile index mod 64): nn.BatchNorm2d's batch statistics without a second pass over the output
- * (style_encoder.py:54-58, new_decoder.py:30-61).  Only for plans that do not split K (ast_igemm_plan)
- * and plain stores (bits 0 and 1 clear); reduce with ast_norm_finalize(N = 64, count = pixels).
- * bit6 (with bit3): the table is [N][Cd][2] and every tile adds into the row of ITS IMAGE (tiles are laid out so that none
- * straddles two images): nn.InstanceNorm2d's per-image statistics (style_encoder.py:69) without a pass over the output;
- * gathered and patch kernels only (ast_igemm_plan: kch != 0), reduce with ast_norm_finalize(instance = 1). */
+ * flags: an OR of the AST_IGEMM_* bits below; every argument is checked once, before any launch, whichever kernel the plan picks. */
+#define AST_IGEMM_ACCUMULATE  1      /* bit 0: add into dst */
+#define AST_IGEMM_RELU        2      /* bit 1: ReLU on the stored value */
+#define AST_IGEMM_WS_ZEROED   4      /* bit 2: the split-K workspace is already zero (the finish pass hands it back zeroed: a persistent one never needs a memset) */
+#define AST_IGEMM_STATS       8      /* bit 3: fused forward statistics, below */
+#define AST_IGEMM_BN_SUMS     16     /* bit 4: fused BatchNorm-backward sums: ast_igemm_bn only (ast_igemm clears bits 4 and 5) */
+#define AST_IGEMM_BN_NO_RELU  32     /* bit 5: with BN_SUMS: the BatchNorm layer has no ReLU */
+#define AST_IGEMM_PER_IMAGE   64     /* bit 6: with STATS: per-image statistics, below */
+#define AST_IGEMM_SLOTS_SHIFT 8      /* bits 8-11: log2 of the number of statistics slots, 0 = 64 */
+#define AST_IGEMM_SLOTS_MASK  (15 << AST_IGEMM_SLOTS_SHIFT)
+#define AST_IGEMM_DET         4096   /* bit 12: the atomic-free instantiations (ast_igemm_ws_floats_det); refused with STATS, BN_SUMS or PER_IMAGE */
+/* STATS: `ws` is a zeroed [slots][Cd][2] f32 table (ws_floats: its length) and every tile adds (sum, sum of squares) of the values
+ * it stores into slot (tile index mod slots): nn.BatchNorm2d's batch statistics without a second pass over the output
+ * (style_encoder.py:54-58, new_decoder.py:30-61).  Needs ACCUMULATE and RELU clear and a plan that does not split K
+ * (ast_igemm_ws_floats == 0); reduce with ast_norm_finalize(N = slots, count = pixels).
+ * STATS | PER_IMAGE: the table is [N][Cd][2] and every tile adds into the row of ITS IMAGE (tiles are laid out so that none straddles
+ * two images): nn.InstanceNorm2d's per-image statistics (style_encoder.py:69); gathered and patch kernels only (ast_igemm_plan:
+ * kch != 0); reduce with ast_norm_finalize(instance = 1).  PER_IMAGE without STATS is refused on every kernel path (the patch path
+ * used to accept and ignore it).  A split-K plan takes neither STATS nor BN_SUMS and needs its workspace in `ws`. */
 int ast_igemm(const void* src, const void* wgt, const float* bias, void* dst,
               const ast_gather_t* g, int dtype, int flags, float* ws, long ws_floats, void* stream);
-/* ast_igemm as the data-gradient GEMM that PRODUCES dy of a BatchNorm2d(+ReLU) layer (flags bit 4; bit 5: no ReLU):
+/* ast_igemm as the data-gradient GEMM that PRODUCES dy of a BatchNorm2d(+ReLU) layer (AST_IGEMM_BN_SUMS; BN_NO_RELU: no ReLU):
  * bn_x is that layer's input (same geometry and dtype as dst), bn_scale/bn_shift its forward coefficients; every tile adds
- * (sum dz, sum dz*x), dz = dy*[fma(x, scale, shift) > 0], of the values it stores into the zeroed [64][Cd][3] table `ws`,
- * so ast_norm_bwd_sums need not run (reduce with ast_norm_bwd_finalize(N = 64, count = pixels)).  Plans without split-K. */
+ * (sum dz, sum dz*x), dz = dy*[fma(x, scale, shift) > 0], of the values it stores into the zeroed [slots][Cd][3] table `ws`,
+ * so ast_norm_bwd_sums need not run (reduce with ast_norm_bwd_finalize(N = slots, count = pixels)).  Needs ACCUMULATE, RELU and
+ * STATS clear, all three BatchNorm pointers and a plan without split-K. */
 int ast_igemm_bn(const void* src, const void* wgt, const float* bias, void* dst, const ast_gather_t* g, int dtype, int flags,
                  float* ws, long ws_floats, const void* bn_x, const float* bn_scale, const float* bn_shift, void* stream);
-/* Narrow layers (Cd <= 16, ntaps*Cs <= 12 sixteen-byte chunks) run an LDS-free kernel: each lane's gather load is its
- * MFMA fragment, the weights stay in registers (ast_igemm_plan reports it as kch = 0).  Same results, same flags. */
-/* f32 workspace (floats) ast_igemm needs for this geometry: >0 when the launch is split over K
- * (under-filled grids of the deep, small-M layers), 0 otherwise, <0 on a bad geometry. */
+/* Queries (host side, no launch; <0 on a bad geometry), all answered from the one plan ast_igemm computes per call.
+ * ast_igemm_ws_floats: the f32 workspace (floats) ast_igemm needs: >0 when the launch is split over K (under-filled grids of the
+ * deep, small-M layers), 0 otherwise.  ast_igemm_plan: out5 = {BM, BN, 16-byte chunks per row per barrier (kch), grid-level
+ * split-K slices, in-workgroup K groups} of the gathered kernel; {-(tile rows), channel tile, -(slab bytes), -(fragments) for row
+ * blocks else 1, 1} for the patch-staged kernel; {64 * pixel tiles per wave, 16 or 32, 0, 1, 1} for the LDS-free kernel of narrow
+ * layers (Cd <= 16, ntaps*Cs <= 12 chunks: each lane's gather load is its MFMA fragment, the weights stay in registers).
+ * ast_pconv_variant: out4 = {slab bytes, TM, TN, WALL} of the pconv_kernel instantiation and returns 1; 0 for the other two kernels. */
 long ast_igemm_ws_floats(const ast_gather_t* g, int dtype);
-/* the tile plan ast_igemm will use: out5 = {BM, BN, 16-byte chunks per row per barrier, grid-level split-K slices, in-workgroup K groups} */
 int ast_igemm_plan(const ast_gather_t* g, int dtype, int* out5);
-/* the patch-staged kernel ast_igemm will launch: out4 = {slab bytes, TM, TN, WALL} of pconv_kernel, returns 1; 0 when the
- * geometry goes to the gathered or direct kernel, <0 on a bad geometry (reporting only, host side) */
 int ast_pconv_variant(const ast_gather_t* g, int dtype, int* out4);
 
 /* dw[cd][wtap[t]][c] += sum_pix dy[pix][cd] * src[gather(pix,t)][c]   (f32 atomics)

@@ -209,6 +209,7 @@ def test_igemm_argument_validation_returns_error_codes():
     gp, _ = ops.gather_direct(16, 72, 150, 64, 64, 3, 1, 1)
     assert lib.ast_igemm_plan(gp, bf16, ctypes.byref(out)) == 0 and out[2] < 0, list(out)
     assert igemm(gp, 8, None, 64 * 64 * 2) != 0
+    assert igemm(gp, 64, fake, 16 * 64 * 2) != 0       # per-image slots without flag 8: refused on the patch path as on the others
     assert igemm_bn(gp, 16, fake, 64 * 64 * 3, sf=None) != 0
     assert igemm(gp, 4096 | 8, fake, 64 * 64 * 2) != 0 and b"deterministic" in lib.ast_last_error()      # refused on the patch path too
     assert igemm(gg, 4096 | 8, fake, 64 * 64 * 2) != 0 and igemm_bn(gp, 4096 | 16, fake, 64 * 64 * 3) != 0
