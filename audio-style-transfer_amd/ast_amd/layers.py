@@ -51,6 +51,11 @@ class WeightBank:
     def add(self, weight, kind, dtype_fn, u=None, v=None, bias=None, rows=None):
         """kind: 'conv' (Co,Ci,k,k) | 'convT' (Ci,Co,k,k) | 'linear' (Co,Ci); rows=(r0,r1) selects output rows
         of a linear weight (packed q/k/v projections).  dtype_fn() gives the packed dtype at build time."""
+        if kind in ("conv", "convT") and weight.shape[2] * weight.shape[3] > 9:
+            # the pack and flush kernels stage a 32x32-channel tile with ALL taps in a fixed float[9*32*33] of LDS (csrc/weights.hip)
+            # and the descriptors live in device memory, where the C ABI cannot check them: a larger kernel would write past it
+            raise ValueError(f"WeightBank.add: a {weight.shape[2]}x{weight.shape[3]} kernel has {weight.shape[2] * weight.shape[3]} taps; "
+                             "the weight bank's pack and flush kernels hold at most 9 (3x3) per tile")
         self.specs.append((weight, kind, dtype_fn, u, v, bias, rows))
         self.entries.append(PackedWeight())
         return self.entries[-1]

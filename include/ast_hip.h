@@ -156,6 +156,9 @@ int ast_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int W, int Cp
 int ast_cast(const void* x, int dtype_in, void* y, int dtype_out, int64_t n, void* stream);
 
 /* ---- spectral norm + weight packing (torch spectral_norm.py:92-114) --------- */
+/* KK <= 9: the pack and flush kernels stage one 32x32-channel tile with all KK taps in a fixed float[9*32*33] of LDS and a larger
+ * KK writes past it.  The descriptors are read on the device, so the entry points below CANNOT check this: the caller must
+ * (layers.WeightBank.add raises ValueError for a conv / conv-transpose kernel of more than 9 taps). */
 typedef struct ast_weight_desc_t {
   const float* w;       /* weight_orig; element (co,ci,tap) at co*s_co + ci*s_ci + tap */
   float* u;             /* weight_u [Co] or NULL (no spectral norm) */
