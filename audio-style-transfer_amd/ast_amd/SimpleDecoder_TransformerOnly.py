@@ -52,8 +52,8 @@ class Decoder(DecoderTrunk):
     def create_causal_mask(self, seq_len, device=None):
         return torch.triu(torch.ones(seq_len, seq_len, device=device), diagonal=1).bool()
 
-    def _training_pass(self, y, memory):
-        return self._teacher_forced(self._encode(y), memory)
+    def _training_pass(self, y, memory, lengths=None):
+        return self._teacher_forced(self._encode(y), memory, lengths)
 
     def forward(self, content_emb, class_emb, y=None, target_length=None, lengths=None):
         """SimpleDecoder_TransformerOnly.py:127-133.

@@ -212,6 +212,9 @@ _SIGS = {
     "ast_pitch_mean_len": ([vp, i32, i32, vp, vp, i32, i32, vp, vp], i32),
     "ast_pitch_correlation_ws_floats": ([i32, i32, i32], C.c_long),
     "ast_pitch_correlation_len": ([vp, i32, vp, i32, i32, vp, vp, i32, vp, C.c_long, vp, vp], i32),
+    # per-clip reconstruction loss of a padded batch, section counts read from the device (include/ast_hip.h, ast_amd/losses.py)
+    "ast_recon_loss_len_ws_floats": ([i32, i32, i32, i32], C.c_long),
+    "ast_recon_loss_len": ([vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(f32), vp, C.c_long, vp, vp], i32),
     # 64-bit digest over the bytes of a list of device tensors (include/ast_hip.h, ast_amd/checkpoint.py)
     "ast_state_digest": ([C.POINTER(vp), C.POINTER(C.c_longlong), i32, vp, vp], i32),
 }
@@ -245,6 +248,8 @@ CALL_BYTES = {
     # compute_comprehensive_loss: read output and target, write the gradient (f32)
     "ast_recon_loss": lambda a: 3 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
     "ast_recon_loss_total": lambda a: 3 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
+    # the per-clip values-only form: read output and target once (an upper bound for a ragged batch: padded sections are skipped)
+    "ast_recon_loss_len": lambda a: 2 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
     "ast_adam": lambda a: 7 * 4 * a[4],                    # read p, g, m, v; write p, m, v
     "ast_sumsq": lambda a: 4 * a[1],
     "ast_weights_prepare_t": None,                         # bytes from NEXT_BYTES (WeightBank)

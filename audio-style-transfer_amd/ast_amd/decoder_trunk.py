@@ -92,17 +92,36 @@ class DecoderTrunk(nn.Module):
             tgt = lyr(tgt, memory, self.training, lengths)
         return tgt
 
-    def _teacher_forced(self, emb, memory):
+    def _teacher_forced(self, emb, memory, lengths=None):
         """emb (B, S, d), the embedded target sections: shifted right behind the start token, through the stack, to sections
-        (the second half of forward_training: new_decoder.py:231-269, SimpleDecoder_TransformerOnly.py:80-102)."""
+        (the second half of forward_training: new_decoder.py:231-269, SimpleDecoder_TransformerOnly.py:80-102).  lengths (a padded
+        batch, eval mode): clip b's target tokens s >= lengths[b] are replaced by zeros first -- the causal self-attention gives
+        them weight 0 in every real row, and 0 times whatever a padded target section embeds to must stay 0 -- and the
+        cross-attention sees the clip's own memory tokens only."""
+        if lengths is not None:
+            S = emb.shape[1]
+            keep = torch.arange(S, device=emb.device)[None, :] < lengths.clamp(1, S)[:, None]
+            emb = torch.where(keep[:, :, None], emb, torch.zeros_like(emb))
         tgt = torch.cat([self.start_token.expand(emb.shape[0], 1, -1), emb[:, :-1, :]], dim=1)
         tgt = L.layer_norm(self.pos_encoding(tgt), self.input_norm)
-        return self._generate(self._stack(tgt, memory), None)
+        return self._generate(self._stack(tgt, memory, lengths), lengths)
 
     def forward_training(self, y, memory):
         """new_decoder.py:231-269, SimpleDecoder_TransformerOnly.py:80-102."""
         self._prepare()
         return self._training_pass(y, memory)
+
+    def forward_teacher_forced(self, content_emb, class_emb, y, lengths=None):
+        """The teacher-forced pass of forward_training on (content_emb, class_emb) in whatever mode the module is in: in eval mode
+        under torch.no_grad() it gives the validation output comparable to the training loss (forward() in eval mode decodes
+        autoregressively, as the reference does: new_decoder.py:337-345).  y (B, S, 2, 287, 513): the target sections.
+        lengths: None, or an int32 (B,) device tensor for a zero-padded batch (eval mode only): clip b holds lengths[b] real
+        sections; its rows s < lengths[b] are what the clip gives alone, the rest is as forward() documents."""
+        self._check_lengths(lengths, content_emb.shape[0])
+        if y.dim() != 5:
+            raise ValueError(f"Expected y to have shape [B, S, 2, 287, 513], got {tuple(y.shape)}")
+        self._prepare()
+        return self._training_pass(y, self._memory(content_emb, class_emb), lengths=lengths)
 
     def _inference_pass_cached(self, memory, target_length, lengths=None):
         B = memory.size(0)

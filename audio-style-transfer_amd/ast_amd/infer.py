@@ -27,6 +27,35 @@ from ._lib import len_tensor
 SAMPLE_RATE = 22050                                      # the models' rate: what load_audio resamples to
 
 
+def replay_graph(graphs, use_graph, key, fn, inputs):
+    """fn(*inputs), as one hipGraph per key of the cache `graphs`: captured on first use over clones of the inputs (after two
+    warm-up runs on a side stream: weight banks -- eval: sigma from the stored u, v -- and caches), then replayed, with every input
+    that is not its clone already copied in first.  Returns the captured outputs.  Without use_graph: fn(*inputs).  fn must leave
+    no state behind (an eval-mode, no-grad pass): the warm-up runs are real runs.  The inference session and Trainer.evaluate
+    replay through here."""
+    if not use_graph:
+        return fn(*inputs)
+    if key not in graphs:
+        static = [t.detach().clone() for t in inputs]
+        side = torch.cuda.Stream(device=inputs[0].device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                fn(*static)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            outs = fn(*static)
+        graphs[key] = (g, static, outs)
+    g, static, outs = graphs[key]
+    for dst, src in zip(static, inputs):
+        if dst.data_ptr() != src.data_ptr():
+            dst.copy_(src)
+    g.replay()
+    return outs
+
+
 class StyleTransferSession:
     def __init__(self, content_encoder, decoder, use_graph: bool = True, overlap: int = U.OVERLAP_FRAMES):
         self.content, self.decoder = content_encoder.eval(), decoder.eval()
@@ -49,30 +78,7 @@ class StyleTransferSession:
             return U.inverse_STFT_batch(spec, nf), out, (nf - 1) * 256
 
     def _replay(self, key, fn, inputs):
-        """fn(*inputs), as one hipGraph per key: captured on first use over clones of the inputs (after two warm-up runs on a side
-        stream: weight banks -- eval: sigma from the stored u, v -- and caches), then replayed, with every input that is not its
-        clone already copied in first.  Returns the captured outputs.  Without use_graph: fn(*inputs)."""
-        if not self.use_graph:
-            return fn(*inputs)
-        if key not in self._graphs:
-            static = [t.detach().clone() for t in inputs]
-            side = torch.cuda.Stream(device=inputs[0].device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    fn(*static)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                outs = fn(*static)
-            self._graphs[key] = (g, static, outs)
-        g, static, outs = self._graphs[key]
-        for dst, src in zip(static, inputs):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src)
-        g.replay()
-        return outs
+        return replay_graph(self._graphs, self.use_graph, key, fn, inputs)
 
     def __call__(self, sections: torch.Tensor, class_emb: torch.Tensor, original_frames=None, n_sections: torch.Tensor = None):
         """sections (B,S,2,287,597) f32, class_emb (B,d) f32 on the device -> (waveforms (B, 256*(T-1)), stft sections).

@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._lib import check, len_tensor, lib, ptr, stream
 
 
 def _labels32(labels, device):
@@ -48,3 +49,91 @@ def disentanglement_loss(style_emb: torch.Tensor, content_emb: torch.Tensor, use
     if not use_hsic:
         return ops.CrossCovFn.apply(style_emb, content_emb)
     return ops.HSICFn.apply(style_emb, content_emb)
+
+
+# ---- validation: values only, for padded batches ---------------------------------------------------------------------------
+RECON_KEYS = ("mse_loss", "mag_loss", "phase_loss", "temporal_loss", "spectral_loss")
+
+
+def _spectrogram_arg(t, what, shape=None):
+    """output / target of reconstruction_losses: (B, S, 2, T, F) float32 -> its shape"""
+    if not torch.is_tensor(t) or t.dim() != 5 or t.dtype != torch.float32 or t.shape[2] != 2 or t.numel() == 0:
+        got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"reconstruction_losses: {what} must be a non-empty (B, S, 2, T, F) float32 tensor, got {got}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"reconstruction_losses: {what} has shape {tuple(t.shape)}, output has {tuple(shape)}")
+    return tuple(t.shape)
+
+
+def reconstruction_losses(output, target, n_sections=None, lambda_temporal=0.3, lambda_phase=0.2, lambda_spectral=0.1, mse_weight=2.0):
+    """compute_comprehensive_loss (new_decoder.py:348-420; mse_weight=1.0: SimpleDecoder_TransformerOnly.py:136-204) for every clip
+    of a zero-padded batch by itself: entry b of each result is the reference's value for (output[b:b+1, :n_b], target[b:b+1, :n_b]),
+    n_b = n_sections[b] clamped to [1, S] on the device (None: every clip holds S sections).  Sections s >= n_b of either tensor
+    are not read, so they may hold anything.  Returns a dict of (B,) float32 device tensors under the reference's keys.  Values
+    only: nothing here carries a gradient.  No host read and no atomics (ast_recon_loss_len): the call can be captured, one graph
+    serves every mix of lengths, and the values are bit-identical from run to run."""
+    import ctypes as C
+    B, S, _, T, Fq = _spectrogram_arg(output, "output")
+    _spectrogram_arg(target, "target", output.shape)
+    n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
+    for what, t in (("output", output), ("target", target)):
+        if not t.is_cuda:
+            raise ValueError(f"reconstruction_losses: {what} must be on the GPU, got a tensor on {t.device} (there is no CPU path)")
+    for name, v in (("lambda_temporal", lambda_temporal), ("lambda_phase", lambda_phase), ("lambda_spectral", lambda_spectral),
+                    ("mse_weight", mse_weight)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError(f"reconstruction_losses: {name} must be a number, got {v!r}")
+    need = int(lib().ast_recon_loss_len_ws_floats(B, S, T, Fq))
+    if need < 0:
+        raise ValueError(f"reconstruction_losses: output of shape {tuple(output.shape)} is out of range: {lib().ast_last_error().decode()}")
+    out, tgt = output.detach().contiguous(), target.detach()
+    ld = tgt.stride(3)
+    if tgt.stride(4) != 1 or ld < Fq or tuple(tgt.stride()[:3]) != (S * 2 * T * ld, 2 * T * ld, T * ld):
+        tgt, ld = tgt.contiguous(), Fq               # anything but a [..., :F] slice of a contiguous tensor
+    ws = torch.empty(need, dtype=torch.float32, device=out.device)
+    res = torch.empty((B, 11), dtype=torch.float32, device=out.device)
+    c5 = (C.c_float * 5)(float(mse_weight), 0.5, float(lambda_phase), float(lambda_temporal), float(lambda_spectral))
+    check(lib().ast_recon_loss_len(ptr(out), ptr(tgt), ld, B, S, T, Fq, ptr(n), c5, ptr(ws), need, ptr(res), stream()), "ast_recon_loss_len")
+    parts = {"total_loss": res[:, 5]}
+    parts.update({k: res[:, 6 + i] for i, k in enumerate(RECON_KEYS)})
+    return parts
+
+
+def _value(dev, call, what):
+    """call(loss) launches one loss kernel with null gradient pointers -> the scalar it wrote"""
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(call(loss), what)
+    return loss[0]
+
+
+def embedding_loss_values(style_emb, class_emb, content_mean, discriminator, labels, temperature=0.1, margin=2.0,
+                          lambda_content=1.0, lambda_class=0.5, lambda_style=1.0):
+    """The embedding losses of this file forward only (the same kernels with null gradient pointers), for a validation pass:
+    -> dict of scalar device tensors nce, margin, hsic (HSIC with the median heuristic, the term the train step uses), adv_d, adv_g.
+    content_mean: (B, d), the content embedding already averaged over each clip's own sections."""
+    dev = style_emb.device
+    s, c, k = style_emb.detach().contiguous(), content_mean.detach().contiguous(), class_emb.detach().contiguous()
+    B, D = s.shape
+    lab = _labels32(labels, dev)
+    L = lib()
+    ws = torch.empty(max(2 * B * B + B, 6 * B * B + 2 * B + 8), dtype=torch.float32, device=dev)      # InfoNCE's and HSIC's scratch
+    out = {"nce": _value(dev, lambda o: L.ast_infonce(ptr(s), ptr(lab), B, D, float(temperature), ptr(o), None, ptr(ws), stream()), "ast_infonce"),
+           "margin": _value(dev, lambda o: L.ast_margin(ptr(k), k.shape[0], k.shape[1], float(margin), ptr(o), None, stream()), "ast_margin")}
+    out["hsic"] = _value(dev, lambda o: L.ast_hsic(ptr(s), ptr(c), B, D, ptr(o), None, None, ptr(ws), stream()), "ast_hsic")
+
+    def ce(logits, target32):
+        z = logits.contiguous()
+        return _value(dev, lambda o: L.ast_cross_entropy(ptr(z), ptr(target32), z.shape[0], z.shape[1], ptr(o), None, stream()), "ast_cross_entropy")
+
+    # losses.py:69-123 with the discriminator as it stands: its loss and the generator's entropy term from the same predictions
+    content_pred = discriminator(c).contiguous()
+    terms = [(lambda_style, ce(discriminator(s), lab)), (lambda_content, ce(content_pred, lab)),
+             (lambda_class, ce(discriminator(k), ops.const_tensor((0, 1), torch.int32, dev)))]
+    d_loss = None
+    for w, t in terms:
+        t = t if w == 1.0 else w * t
+        d_loss = t if d_loss is None else d_loss + t
+    ent = _value(dev, lambda o: L.ast_softmax_entropy(ptr(content_pred), content_pred.shape[0], content_pred.shape[1], ptr(o), None, stream()),
+                 "ast_softmax_entropy")
+    out["adv_d"], out["adv_g"] = d_loss, -(ent if lambda_content == 1.0 else lambda_content * ent)
+    return out

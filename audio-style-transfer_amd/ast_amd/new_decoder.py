@@ -106,8 +106,8 @@ class Decoder(DecoderTrunk):
         self._prepare()
         return self._embed_target(y)
 
-    def _training_pass(self, y, memory, y_embeddings=None):
-        return self._teacher_forced(self._embed_target(y) if y_embeddings is None else y_embeddings, memory)
+    def _training_pass(self, y, memory, y_embeddings=None, lengths=None):
+        return self._teacher_forced(self._embed_target(y) if y_embeddings is None else y_embeddings, memory, lengths)
 
     def forward(self, content_emb, class_emb, y=None, target_length=None, y_embeddings=None, lengths=None):
         """new_decoder.py:321-345 (+ optional precomputed encode_target(y)).

@@ -21,10 +21,11 @@ import torch
 import torch.distributed as dist
 
 from . import config, ops, streams
-from ._lib import check, lib, ptr, stream
+from ._lib import check, len_tensor, lib, ptr, stream
 from .content_encoder import ContentEncoder
 from .discriminator import Discriminator
-from .losses import adversarial_loss, disentanglement_loss, infoNCE_loss, margin_loss
+from .losses import (RECON_KEYS, adversarial_loss, disentanglement_loss, embedding_loss_values, infoNCE_loss, margin_loss,
+                     reconstruction_losses)
 from .new_decoder import Decoder, compute_comprehensive_loss
 from .parallel import gather_rows, global_labels
 from .style_encoder import StyleEncoder, _module_bank, class_prototypes, initialize_weights
@@ -242,6 +243,7 @@ class Trainer:
         self._pre_zeroed = False
         self._stream_fe = None
         self._graphs = {}
+        self._eval_graphs = {}                       # evaluate(): one captured validation pass per key
         self._streams = None
         self._y_emb = None
         self._carry = None
@@ -676,6 +678,95 @@ class Trainer:
         finally:
             config.deterministic = prev
 
+    # ------------------------------------------------------------------ validation ("Validation")
+    DECODE_MODES = ("teacher_forced", "autoregressive")
+
+    def evaluate(self, x: torch.Tensor, labels_host: torch.Tensor, n_sections: torch.Tensor = None, decode: str = "teacher_forced"):
+        """Losses on held-out data: x and labels_host as step() takes them, all four models in eval mode under torch.no_grad()
+        (BatchNorm running statistics, no dropout, spectral norm from the stored u / v without a power-iteration step).
+
+        n_sections (int32 (B,) device tensor): x is zero-padded to S_max sections and clip b holds n_sections[b] of them, clamped to
+        [1, S_max] on the device; nothing of it is read on the host, so one captured graph serves every mix of lengths.
+        decode: "teacher_forced" (DecoderTrunk.forward_teacher_forced: the number comparable to the training loss) or
+        "autoregressive" (the reference's model.eval() semantics, new_decoder.py:337-345, through the trunk's inference pass).
+
+        Returns device tensors, nothing is synchronised: rec (B,) and rec_parts (dict of (B,)) from losses.reconstruction_losses
+        with the configured decoder's MSE weight; nce, margin, hsic, adv_d, adv_g (scalars, forward only; the content embedding
+        averaged over each clip's own sections; adv_d and adv_g from the discriminator as it stands); total = the mean of rec over
+        the clips plus the other terms under the trainer's w_* weights and current use_* gates, summed in _g_phase's order.  With
+        cfg.use_graph they are the outputs of a replayed graph, overwritten by the next evaluate of the same key.
+
+        No training state changes (state_digest() is the same before and after), the models are back in training mode on return,
+        also when this raises, and the next step() is what it would have been without the call."""
+        if self.world > 1:
+            raise ValueError("evaluate: validation runs per process (world > 1 has no gathered form); call it on one rank's Trainer "
+                             "built with world=1")
+        if decode not in self.DECODE_MODES:
+            raise ValueError(f"evaluate: decode must be one of {self.DECODE_MODES}, got {decode!r}")
+        if not (torch.is_tensor(x) and x.dim() == 5 and x.dtype == torch.float32 and x.is_cuda and x.shape[2] == 2 and x.shape[-1] >= 513):
+            raise ValueError("evaluate: x must be a (B, S, 2, 287, >= 513) float32 cuda tensor")
+        assert not labels_host.is_cuda, "pass labels on the host: avoids a device sync"
+        B, S = x.shape[:2]
+        n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
+        self._check_deterministic()
+        det = self._deterministic()
+        self._sync_hyper()
+        c = self.cfg
+        key = (B, S, decode, n is None, tuple(x.shape[2:]), tuple(labels_host.tolist()), config.compute_dtype, c.use_nce, c.use_hsic, c.use_adv,
+               det, self.decoder.decode_mode)
+        models = (self.style, self.content, self.decoder, self.disc)
+        prev, config.deterministic = config.deterministic, det
+        try:
+            for m in models:
+                m.eval()
+            with torch.no_grad():
+                from .infer import replay_graph
+                fn = (lambda xs: self._evaluate_body(xs, labels_host, None, decode)) if n is None else \
+                     (lambda xs, ns: self._evaluate_body(xs, labels_host, ns, decode))
+                flat = replay_graph(self._eval_graphs, c.use_graph, key, fn, [x] if n is None else [x, n])
+        finally:
+            config.deterministic = prev
+            for m in models:
+                m.train()
+        names = ("rec", "total", "nce", "margin", "hsic", "adv_d", "adv_g", "total_loss") + RECON_KEYS
+        out = dict(zip(names[:7], flat[:7]))
+        out["rec_parts"] = dict(zip(names[7:], flat[7:]))
+        return out
+
+    def _evaluate_body(self, x, labels_host, n, decode):
+        """The validation pass itself (eval mode, no grad) -> a flat tuple of device tensors (what a captured graph hands back)."""
+        c = self.cfg
+        B, S = x.shape[:2]
+        y = x[..., :513]
+        if n is not None:
+            n = n.clamp(1, S)            # once, for every consumer (the style encoder forms lengths + 1 for its CLS token before its kernels clamp)
+        with ops.shared_nhwc(x, config.compute_dtype):
+            style_emb, class_emb = self.style(x, labels_host, n)
+            content_emb = self.content(x, n)
+        cls_rows = ops.class_rows(class_emb, labels_host)
+        if decode == "teacher_forced":
+            out = self.decoder.forward_teacher_forced(content_emb, cls_rows, y, lengths=n)
+        else:
+            out = self.decoder(content_emb, cls_rows, lengths=n)
+        rec = reconstruction_losses(out, y, n, mse_weight=1.0 if self._simple else 2.0)
+        emb = embedding_loss_values(style_emb, class_emb, self._content_mean(content_emb, n), self.disc, labels_host)
+        aux = [(H_W_MARGIN, emb["margin"])] + ([(H_W_NCE, emb["nce"])] if c.use_nce else []) + ([(H_W_HSIC, emb["hsic"])] if c.use_hsic else [])
+        terms = [(H_W_REC, rec["total_loss"].mean()), (-1, ops.weighted_sum(self.hyper, aux))] + ([(H_W_ADV, emb["adv_g"])] if c.use_adv else [])
+        total = ops.weighted_sum(self.hyper, terms)
+        return (rec["total_loss"], total, emb["nce"], emb["margin"], emb["hsic"], emb["adv_d"], emb["adv_g"], rec["total_loss"]) + \
+            tuple(rec[k] for k in RECON_KEYS)
+
+    def _content_mean(self, content_emb, n):
+        """(B, S, d) -> (B, d): the mean over clip b's own n[b] sections (n: None, or int32 (B,) on the device, already in [1, S]).
+        As the style encoder forms it without a CLS token: padded rows are selected away (they are unspecified), the sum times the
+        correctly rounded f32 reciprocal of the count, looked up on the device."""
+        if n is None:
+            return ops.mean_over_sections(content_emb)
+        S = content_emb.shape[1]
+        keep = torch.arange(S, device=content_emb.device)[None, :] < n[:, None]
+        return torch.where(keep[:, :, None], content_emb, torch.zeros_like(content_emb)).sum(dim=1) * \
+            self.style._recip(S, content_emb.device)[n.long() - 1][:, None]
+
     @contextlib.contextmanager
     def _drop_scope(self):
         """This Trainer's dropout stream in place of the process-wide one for the length of a step: ops._DropState.seed and .counter
@@ -765,6 +856,7 @@ class Trainer:
             print(f"[ast_amd] {e}; falling back to per-op token launches (AST_TOK_PROGRAMS=1)", flush=True)
             config.tok_programs = 1
             self._graphs.clear()
+            self._eval_graphs.clear()
 
     def _check_replicas_after_first_replay(self):
         """Once, after the first replay with the collectives inside the graph: every rank must hold the same parameters

@@ -107,6 +107,96 @@ __global__ __launch_bounds__(320) void recon_finish_det_kernel(const float* __re
   if (threadIdx.x == 0) out[5] = (((a.c[0] * sk[0] + a.c[1] * sk[1]) + a.c[2] * sk[2]) + a.c[3] * sk[3]) + a.c[4] * sk[4];
 }
 
+// ---- compute_comprehensive_loss per clip of a zero-padded batch (values only) --------
+// Row b is the loss of clip b alone over its own n_b = clamp(n_sections[b], 1, S) sections.  grid (workgroups per clip, B):
+// a workgroup belongs to ONE clip, thread = one (t, f) bin of it, looping over the clip's n_b sections with the section
+// difference in registers; sections s >= n_b are never loaded, the last real section has no successor.  Values only, so the
+// t - 1 neighbour and e[s-1] of recon_loss_kernel (gradient terms) are not read.  Every workgroup STORES its five partial sums
+// into its own slot part[(b * gridDim.x + blockIdx.x) * 5 ..]: no atomics, nothing to zero.
+constexpr int RLEN_THREADS = 256;
+constexpr int RLEN_MAX_BLOCKS = 4096;           // workgroups per clip; past 4096 * 256 bins a thread strides over several
+
+__device__ __forceinline__ int clip_sections(const int32_t* __restrict__ n_sections, int b, int S) {
+  return n_sections ? min(max(n_sections[b], 1), S) : S;
+}
+
+__global__ __launch_bounds__(RLEN_THREADS) void recon_len_kernel(const float* __restrict__ out, const float* __restrict__ tgt, int64_t tld,
+                                                                  int S, int T, int Fq, const int32_t* __restrict__ n_sections,
+                                                                  float* __restrict__ part) {
+  __shared__ float red[17];
+  const int b = blockIdx.y;
+  const int nb = clip_sections(n_sections, b, S);
+  const unsigned bins = (unsigned)T * Fq;                       // < 2^31 (host check)
+  const size_t plane_o = (size_t)T * Fq, plane_t = (size_t)T * tld;
+  const float* ob = out + (size_t)b * S * 2 * plane_o;
+  const float* tb = tgt + (size_t)b * S * 2 * plane_t;
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (unsigned i = blockIdx.x * RLEN_THREADS + threadIdx.x; i < bins; i += gridDim.x * RLEN_THREADS) {
+    const int f = (int)(i % (unsigned)Fq), t = (int)(i / (unsigned)Fq);
+    const bool down = t + 1 < T;
+    const float* po = ob + (size_t)t * Fq + f;
+    const float* pt = tb + (size_t)t * tld + f;
+    float o[2] = {po[0], po[plane_o]}, g[2] = {pt[0], pt[plane_t]};
+    for (int s = 0; s < nb; ++s) {
+      const bool more = s + 1 < nb;                             // the last REAL section has no successor, whatever lies behind it
+      float e[2], edn[2] = {0.f, 0.f}, on[2] = {0.f, 0.f}, gn[2] = {0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float* qo = po + (size_t)(2 * s + c) * plane_o;
+        const float* qt = pt + (size_t)(2 * s + c) * plane_t;
+        e[c] = o[c] - g[c];
+        if (down) edn[c] = qo[Fq] - qt[tld];
+        if (more) { on[c] = qo[2 * plane_o]; gn[c] = qt[2 * plane_t]; }
+      }
+      const float mo = sqrtf(o[0] * o[0] + o[1] * o[1] + 1e-8f), mt = sqrtf(g[0] * g[0] + g[1] * g[1] + 1e-8f);
+      float dphi = atan2f(o[1], o[0]) - atan2f(g[1], g[0]);
+      dphi = dphi + PI_F;
+      dphi = dphi - 2.f * PI_F * floorf(dphi / (2.f * PI_F)) - PI_F;      // torch.remainder(., 2pi) - pi
+      acc[0] += e[0] * e[0] + e[1] * e[1];
+      acc[1] += (mo - mt) * (mo - mt);
+      acc[2] += dphi * dphi;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        if (more) { const float d = (on[c] - gn[c]) - e[c]; acc[3] += d * d; }
+        if (down) { const float d = edn[c] - e[c]; acc[4] += d * d; }
+        o[c] = on[c]; g[c] = gn[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float v = block_sum(acc[k], red);
+    if (threadIdx.x == 0) part[((size_t)b * gridDim.x + blockIdx.x) * 5 + k] = v;
+  }
+}
+
+// One workgroup per clip, the order of recon_finish_det_kernel: wave k sums quantity k, lane l the slots l, l + 64, ... in order,
+// then wave_sum's fixed butterfly.  The counts of new_decoder.py:402-418 for the clip alone and their reciprocals are formed here
+// from n_sections (no host read); a term without elements (temporal at n_b == 1, axis-3 difference at T == 1) has sum, mean and
+// coefficient exactly 0.  res (B, 11) = [5 sums][total = sum_k (w[k] / count_k) * sums[k]][5 means = sums[k] / count_k].
+struct ReconLenW { float w[5]; };
+__global__ __launch_bounds__(320) void recon_len_finish_kernel(const float* __restrict__ part, int nslots, int S, int T, int Fq,
+                                                                const int32_t* __restrict__ n_sections, ReconLenW a,
+                                                                float* __restrict__ res) {
+  __shared__ float sk[5];
+  const int b = blockIdx.x, k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* ws = part + (size_t)b * nslots * 5;
+  float* out = res + (size_t)b * 11;
+  const long long nb = clip_sections(n_sections, b, S);
+  const long long bins = (long long)T * Fq;
+  const long long count = k == 0 ? 2 * nb * bins : k == 3 ? 2 * (nb - 1) * bins : k == 4 ? 2 * nb * (long long)(T - 1) * Fq : nb * bins;
+  float v = 0.f;
+  for (int i = lane; i < nslots; i += 64) v += ws[(size_t)i * 5 + k];
+  v = wave_sum(v);
+  if (lane == 0) {
+    out[k] = v;
+    out[6 + k] = count > 0 ? v * (float)(1.0 / (double)count) : 0.f;
+    sk[k] = count > 0 ? (float)((double)a.w[k] / (double)count) * v : 0.f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) out[5] = (((sk[0] + sk[1]) + sk[2]) + sk[3]) + sk[4];
+}
+
 // ---- InfoNCE (losses.py:9-36), one workgroup of 1024 -------------------------------
 __global__ __launch_bounds__(1024) void infonce_kernel(const float* __restrict__ x, const int* __restrict__ labels, int B, int D,
                                                         float temperature, float* __restrict__ loss, float* __restrict__ dx,
@@ -449,6 +539,40 @@ extern "C" int ast_recon_loss_total_det(const float* out, const float* tgt, int6
   ReconFin a;
   for (int k = 0; k < 5; ++k) { a.c[k] = coef5[k]; a.inv[k] = inv5[k]; }
   hipLaunchKernelGGL(recon_finish_det_kernel, dim3(1), dim3(320), 0, s, ws, (int)grid, a, res11);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// workgroups per clip of recon_len_kernel (one bin per thread up to RLEN_MAX_BLOCKS), or 0 for sizes the entry refuses
+static long recon_len_blocks(int B, int S, int T, int Fq) {
+  if (B <= 0 || B > 65535 || S <= 0 || T <= 0 || Fq <= 0) return 0;
+  const size_t bins = (size_t)T * Fq;
+  if ((size_t)B * bins >= (1ull << 31)) return 0;
+  return (long)std::min<size_t>((bins + RLEN_THREADS - 1) / RLEN_THREADS, RLEN_MAX_BLOCKS);
+}
+
+extern "C" long ast_recon_loss_len_ws_floats(int B, int S, int T, int Fq) {
+  const long nblk = recon_len_blocks(B, S, T, Fq);
+  if (nblk <= 0) AST_FAIL("ast_recon_loss_len_ws_floats: bad sizes (1 <= B <= 65535, S, T, Fq >= 1, B*T*Fq < 2^31)");
+  return 5 * nblk * B;
+}
+
+// The per-clip form of ast_recon_loss_total for a padded batch: one pass of stores, one finishing launch, no atomics and no host
+// read of n_sections, so the pair is capturable and bit-reproducible as it stands (default and deterministic mode alike).
+extern "C" int ast_recon_loss_len(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const int32_t* n_sections,
+                                  const float* coef5, float* ws, long ws_floats, float* res, void* stream) {
+  if (!out || !tgt || !coef5 || !ws || !res) AST_FAIL("ast_recon_loss_len: bad args (null out, tgt, coef5, ws or res)");
+  if (B <= 0 || S <= 0 || T <= 0 || Fq <= 0) AST_FAIL("ast_recon_loss_len: bad args (B=%d S=%d T=%d Fq=%d must all be >= 1)", B, S, T, Fq);
+  if (tgt_ld < Fq) AST_FAIL("ast_recon_loss_len: bad args (tgt_ld %lld < Fq %d)", (long long)tgt_ld, Fq);
+  if ((size_t)B * T * Fq >= (1ull << 31)) AST_FAIL("ast_recon_loss_len: more than 2^31 bins per section");
+  const long nblk = recon_len_blocks(B, S, T, Fq);
+  if (nblk <= 0) AST_FAIL("ast_recon_loss_len: bad args (B %d > 65535)", B);
+  if (ws_floats < 5 * nblk * B) AST_FAIL("ast_recon_loss_len: ws needs %ld floats, got %ld", 5 * nblk * B, ws_floats);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(recon_len_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(RLEN_THREADS), 0, s, out, tgt, tgt_ld, S, T, Fq, n_sections, ws);
+  ReconLenW a;
+  for (int k = 0; k < 5; ++k) a.w[k] = coef5[k];
+  hipLaunchKernelGGL(recon_len_finish_kernel, dim3((unsigned)B), dim3(320), 0, s, ws, (int)nblk, S, T, Fq, n_sections, a, res);
   AST_CHECK_LAUNCH();
   return 0;
 }

@@ -357,6 +357,22 @@ int ast_recon_loss(const float* out, const float* tgt, int64_t tgt_ld, int B, in
 #define AST_RECON_SLOTS 64
 int ast_recon_loss_total(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const float* coef5,
                          const float* inv5, float* ws, float* res11, float* grad, void* stream);
+/* compute_comprehensive_loss (new_decoder.py:348-420, SimpleDecoder_TransformerOnly.py:136-204) per clip of a zero-padded batch,
+ * values only (no gradient path): row b of res is the loss of out[b, :n_b] against tgt[b, :n_b] alone,
+ * n_b = clamp(n_sections[b], 1, S).  out (B,S,2,T,Fq) f32 contiguous, tgt as in ast_recon_loss; n_sections int32 (B,) ON THE DEVICE,
+ * NULL = every clip holds S sections.  coef5 is a HOST array of the five weights (mse, magnitude, phase, temporal, spectral:
+ * 2.0 of new_decoder.py:406 or 1.0 of SimpleDecoder_TransformerOnly.py:194, then 0.5, lambda_phase, lambda_temporal,
+ * lambda_spectral).  The counts of new_decoder.py:402-418 are clip b's own and are formed on the device, without a host read:
+ * mse 2 n_b T Fq; magnitude, phase n_b T Fq; temporal 2 (n_b - 1) T Fq (the term is exactly 0 at n_b == 1, new_decoder.py:387-392);
+ * axis-3 difference 2 n_b (T - 1) Fq.  res (B, 11) = [5 raw sums][total = sum_k coef5[k] / count_k * sums[k]][5 means], the layout
+ * of ast_recon_loss_total's res11.  Sections s >= n_b of either tensor are never read (they may hold NaN), and the last real
+ * section's temporal difference does not look at section n_b.  No floating-point atomics: every workgroup stores its partials
+ * into ws, a finishing launch sums them in a fixed order, so a clip's eleven numbers are bit-identical from run to run.
+ * ws >= ast_recon_loss_len_ws_floats(B, S, T, Fq) floats (ws_floats is checked; ws is written completely, never zeroed); the
+ * query returns < 0 for sizes the entry refuses.  Needs B <= 65535 and B*T*Fq < 2^31 (ast_recon_loss's index-width condition). */
+long ast_recon_loss_len_ws_floats(int B, int S, int T, int Fq);
+int ast_recon_loss_len(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const int32_t* n_sections,
+                       const float* coef5, float* ws, long ws_floats, float* res, void* stream);
 /* losses.py on (B,256) embeddings; each writes loss[0] and optional gradients */
 int ast_infonce(const float* emb, const int32_t* labels, int B, int D, float temperature,
                 float* loss, float* demb, float* ws /* 2*B*B + B floats */, void* stream);
