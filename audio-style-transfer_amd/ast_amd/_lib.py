@@ -148,6 +148,10 @@ _SIGS = {
     "ast_tok_program": ([vp, i32, i32, i32, vp, vp, vp, vp], i32),
     # ragged inference batches: per-clip lengths read from the device (include/ast_hip.h)
     "ast_attn_fwd_len": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
+    # the same core in training: mask and dropout, forward and backward
+    "ast_attn_fwd_len_p": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, f32, C.c_uint64, vp, vp], i32),
+    "ast_attn_bwd_len_p": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, f32, C.c_uint64, vp,
+                            vp], i32),
     "ast_sections_overlap_avg_len": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp], i32),
     "ast_istft_len": ([vp, i32, i32, vp, vp, vp, vp], i32),
     # ragged waveforms: per-clip sample counts read from the device (include/ast_hip.h)

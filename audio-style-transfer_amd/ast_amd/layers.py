@@ -514,7 +514,8 @@ class MHA:
 
     def __call__(self, x, mem, training, p_drop, causal=False, key_mask=None):
         """x: (B,Lq,d), mem: (B,Lk,d) or None for self-attention.  key_mask: None or (key_len int32 (B,), key_period): key j of
-        batch b counts iff (j % key_period) < key_len[b] (inference only, ops.AttnCoreFn)."""
+        batch b counts iff (j % key_period) < key_len[b].  With training it goes through ops.MaskedAttnFn (dropout and a backward
+        under the mask); otherwise through ops.AttnCoreFn, which is inference only under a mask."""
         B, Lq, d = x.shape
         dh = d // self.h
         if self.cross:
@@ -526,6 +527,9 @@ class MHA:
             Lk = Lq
             q = kv = linear(x.reshape(B * Lq, d), self.qkv)
             k_off, v_off = d, 2 * d
+        if key_mask is not None and training:
+            o = ops.MaskedAttnFn.apply(q, kv, B, self.h, Lq, Lk, dh, k_off, v_off, causal, float(p_drop), *key_mask)
+            return linear(o, self.out).view(B, Lq, d)
         if key_mask is not None:
             ops.require_inference(q, kv)
         o = ops.AttnCoreFn.apply(q, kv, B, self.h, Lq, Lk, dh, k_off, v_off, causal, float(p_drop) if training else 0.0,
@@ -543,7 +547,8 @@ class EncoderLayer:
         self.ff2 = bank.add(layer.linear2.weight, "linear", tok_dtype, bias=layer.linear2.bias)
 
     def __call__(self, x, training, lengths=None):
-        """lengths: None, or int32 (B,) -- row b attends to its first lengths[b] tokens only (a padded batch at inference)."""
+        """lengths: None, or int32 (B,) -- row b attends to its first lengths[b] tokens only (a padded batch; with training the
+        attention differentiates under the mask, and the rows past lengths[b] must get no gradient from the loss)."""
         l, p = self.l, self.l.dropout.p
         B, L, d = x.shape
         km = None if lengths is None else (lengths, L)

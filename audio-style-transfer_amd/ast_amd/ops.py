@@ -1299,6 +1299,50 @@ class AttnCoreFn(torch.autograd.Function):
         return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None, None, None
 
 
+class MaskedAttnFn(torch.autograd.Function):
+    """AttnCoreFn under a key mask, for training: key j of batch b counts iff (j % key_period) < key_len[b] (key_len an int32 (B,)
+    device tensor the kernels read and clamp to [1, key_period], so a captured graph serves every mix of lengths).  Forward
+    ast_attn_fwd_len_p, backward ast_attn_bwd_len_p; dropout is drawn in both from _DropState as in AttnCoreFn.  Masked keys get
+    probability 0 and dk = dv = 0 and are never read; every query row is computed, a padded one from the gradient it is given."""
+
+    @staticmethod
+    def forward(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop, key_len, key_period):
+        if key_len is None:
+            raise ValueError("MaskedAttnFn needs key_len (the unmasked core is AttnCoreFn)")
+        key_len = len_tensor(key_len, B, "key_len", device=True, contiguous=True)
+        d = H * dh
+        o = torch.empty((B * Lq, d), dtype=torch.float32, device=q.device)
+        probs = torch.empty((B, H, Lq, Lk), dtype=torch.float32, device=q.device)
+        seed, ctr = 0, None
+        if p_drop > 0.0:
+            if _DropState.counter is None or _DropState.counter.device != q.device:
+                _DropState.counter = torch.zeros(1, dtype=torch.int64, device=q.device)
+            _DropState.calls += 1
+            seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
+        check(lib().ast_attn_fwd_len_p(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
+                                       B, H, Lq, Lk, dh, q.stride(0), kv.stride(0), d, int(causal), ptr(key_len), int(key_period),
+                                       None, float(p_drop), seed, ptr(ctr), stream()), "ast_attn_fwd_len_p")
+        ctx.save_for_backward(q, kv, probs, key_len)
+        ctx.dims = (B, H, Lq, Lk, dh, k_off, v_off, int(key_period))
+        ctx.drop = (float(p_drop), seed, ctr)
+        ctx.same = q.data_ptr() == kv.data_ptr()
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, kv, probs, key_len = ctx.saved_tensors
+        B, H, Lq, Lk, dh, k_off, v_off, key_period = ctx.dims
+        p_drop, seed, ctr = ctx.drop
+        do = do.contiguous()
+        dq = torch.empty_like(q)                    # the kernel writes every q / k / v column of every row, masked keys as 0
+        dkv = dq if ctx.same else torch.empty_like(kv)
+        check(lib().ast_attn_bwd_len_p(ptr(do), q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(probs),
+                                       dq.data_ptr(), dkv.data_ptr() + 4 * k_off, dkv.data_ptr() + 4 * v_off, B, H, Lq, Lk, dh,
+                                       q.stride(0), kv.stride(0), H * dh, ptr(key_len), key_period, None, p_drop, seed, ptr(ctr),
+                                       stream()), "ast_attn_bwd_len_p")
+        return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None, None, None
+
+
 def require_inference(*tensors):
     """The key-masked attention core has no backward: refuse inputs that autograd would track.  AttnCoreFn.forward runs with
     grad mode off and cannot see the caller's, so the callers that pass a key mask (layers.MHA, DecoderLayer.step) ask here."""

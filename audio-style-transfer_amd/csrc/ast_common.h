@@ -166,3 +166,13 @@ AST_HIDDEN int attn_long_fwd_len_launch(const float* q, const float* k, const fl
 AST_HIDDEN int attn_long_bwd_launch(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
                                     float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
                                     const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream);
+// The key mask of the training kernels (ast_attn_fwd_len_p / ast_attn_bwd_len_p), one kernel argument next to the dropout ones:
+// key j of batch b counts iff (j % period) < clamp(len[b], 1, period).  len is an int32 (B,) DEVICE array.
+struct AttnKeyLen { const int32_t* len; int period; };
+AST_HIDDEN int attn_long_fwd_len_p_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq,
+                                          int Lk, int dh, int ldq, int ldk, int ldo, int causal, AttnKeyLen kl, const float* drop_mask,
+                                          float p, uint64_t seed, const int64_t* d_offset, void* stream);
+AST_HIDDEN int attn_long_bwd_len_p_launch(const float* dout, const float* q, const float* k, const float* v, const float* probs,
+                                          float* dq, float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk,
+                                          int ldo, AttnKeyLen kl, const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset,
+                                          void* stream);

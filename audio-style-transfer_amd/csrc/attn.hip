@@ -17,7 +17,8 @@
 // so every output element has one owner and a fixed summation order: the path is bit-reproducible as it stands.
 // Rows past Lq / Lk and columns past dh are predicated: loaded as zero, never stored.
 //
-// ast_attn_fwd_len (inference with ragged batches) is FORWARD ONLY: NO dropout and NO backward are built.  It runs the
+// ast_attn_fwd_len (inference with ragged batches) is forward only and has no dropout; the masked forward with dropout and
+// the masked backward are ast_attn_fwd_len_p / ast_attn_bwd_len_p (the *_len_kernel templates below).  ast_attn_fwd_len runs the
 // instantiations NS + ATTN_MASK of the forward kernel: key j of batch b counts iff (j % key_period) < key_len[b].  key_len is
 // read from the device and clamped to [1, key_period], so key 0 stays valid, which is all the merge of the four lane groups
 // needs (see there).  Masked K / V rows are treated like the rows past Lk: loaded as zero, scored -inf, probability 0; a key
@@ -198,14 +199,16 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(const float* __restri
 }
 
 // dP^T tile (lane: query q0 + (l&15), keys k0 + 4g + r) -> p, p * mask, dP * mask at the lane's four positions
+// keys_ok bit r: key k0 + 4g + r counts (a masked key gets p = 0 and mask 0 without a read of probs or a draw)
 template <int NS>
 __device__ __forceinline__ void bwd_tile_t(const f32x4 (&vf)[NS], const f32x4 (&dof)[NS], const float* __restrict__ probs, const Drop& dr,
-                                           size_t prow, bool qv, int k0, int Lk, int g, f32x4& p, f32x4& pm, f32x4& dpm) {
+                                           size_t prow, bool qv, int k0, int Lk, int g, f32x4& p, f32x4& pm, f32x4& dpm,
+                                           unsigned keys_ok = 15u) {
   const f32x4 dp = dot_tile<NS>(vf, dof);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int j = k0 + 4 * g + r;
-    const bool ok = qv && j < Lk;
+    const bool ok = qv && j < Lk && (keys_ok >> r & 1u);
     const float mk = ok ? dr.at(prow + j) : 0.f;
     p[r] = ok ? probs[prow + j] : 0.f;
     pm[r] = p[r] * mk;
@@ -314,6 +317,224 @@ __global__ __launch_bounds__(64) void attn_long_dkdv_kernel(const float* __restr
   store_rows<NS>(avv, dv + (size_t)b * Lk * ldk + h * dh, ldk, kj, kv, dh, g);
 }
 
+// ---- the key-masked training kernels (ast_attn_fwd_len_p / ast_attn_bwd_len_p): mask AND dropout, so they take the mask as an
+// argument of its own (AttnKeyLen) where the inference instantiations above borrow the dropout slots.  Kernels of their own
+// rather than a body shared with the unmasked ones, so that those stay the code they were (tools/kernel_diff.py).  Per element
+// they do the arithmetic of the unmasked kernels in the same order over the live keys; with full lengths they are bit-equal.
+__device__ __forceinline__ KeyMask make_key_mask(const AttnKeyLen& kl, int b) {
+  KeyMask km;
+  km.period = kl.period;
+  km.kl = min(max(kl.len[b], 1), kl.period);
+  return km;
+}
+// bit r: key k0 + 4g + r counts
+__device__ __forceinline__ unsigned keys_ok4(const KeyMask& km, int k0, int g) {
+  unsigned ok = 0u;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ok |= (km.key(k0 + 4 * g + r) ? 1u : 0u) << r;
+  return ok;
+}
+
+// attn_long_fwd_kernel<NS + ATTN_MASK> with dropout
+template <int NS>
+__global__ __launch_bounds__(64) void attn_long_fwd_len_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                const float* __restrict__ v, float* __restrict__ o,
+                                                                float* __restrict__ probs, int H, int Lq, int Lk, int dh, int ldq, int ldk,
+                                                                int ldo, int causal, AttnKeyLen klen, const float* __restrict__ drop,
+                                                                float pdrop, uint64_t seed, const int64_t* __restrict__ d_offset) {
+  const Drop dr = make_drop(drop, pdrop, seed, d_offset);
+  const int b = blockIdx.y / H, h = blockIdx.y % H, q0 = blockIdx.x * 16;
+  const KeyMask km = make_key_mask(klen, b);
+  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
+  const float scale = rsqrtf((float)dh);
+  const float* qb = q + (size_t)b * Lq * ldq + h * dh;
+  const float* kb = k + (size_t)b * Lk * ldk + h * dh;
+  const float* vb = v + (size_t)b * Lk * ldk + h * dh;
+  const int nkt = (Lk + 15) / 16;
+  const int kt_end = causal ? min(nkt, (q0 + 15) / 16 + 1) : nkt;
+  const int qi = q0 + i;
+  f32x4 qf[NS], kf[NS];
+  load_frag<NS>(qf, qb, ldq, q0, Lq, dh, i, g);
+#pragma unroll
+  for (int s = 0; s < NS; ++s) qf[s] *= scale;
+
+  float m = -INFINITY, l = 0.f;
+  for (int kt = 0; kt < kt_end; ++kt) {
+    if (!km.tile_live(kt, Lk)) continue;
+    load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g, km.key(kt * 16 + i));
+    f32x4 s = dot_tile<NS>(kf, qf);
+    float tm = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = kt * 16 + 4 * g + r;
+      if (j >= Lk || (causal && j > qi) || !km.key(j)) s[r] = -INFINITY;
+      tm = fmaxf(tm, s[r]);
+    }
+    const float mn = fmaxf(m, tm);
+    const float mref = mn == -INFINITY ? 0.f : mn;
+    l *= __expf(m - mref);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) l += __expf(s[r] - mref);
+    m = mn;
+  }
+  const float M = g4_max(m);                                           // finite: key 0 is never masked (key_len >= 1)
+  const float den = g4_sum(l * __expf(m - M));
+
+  f32x4 acc[NS];
+#pragma unroll
+  for (int t = 0; t < NS; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const size_t prow = (((size_t)b * H + h) * Lq + qi) * Lk;
+  const bool qv = qi < Lq;
+  for (int kt = 0; kt < nkt; ++kt) {
+    f32x4 p = {0.f, 0.f, 0.f, 0.f};
+    const bool live = kt < kt_end && km.tile_live(kt, Lk);
+    const unsigned vok = keys_ok4(km, kt * 16, g);
+    if (live) {
+      load_frag<NS>(kf, kb, ldk, kt * 16, Lk, dh, i, g, km.key(kt * 16 + i));
+      const f32x4 s = dot_tile<NS>(kf, qf);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = kt * 16 + 4 * g + r;
+        p[r] = (j >= Lk || (causal && j > qi) || !(vok >> r & 1u)) ? 0.f : __expf(s[r] - M) / den;
+      }
+    }
+    f32x4 pd = p;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = kt * 16 + 4 * g + r;
+      if (qv && j < Lk) {
+        probs[prow + j] = p[r];                                        // a masked key, a skipped tile: exactly 0
+        pd[r] = (vok >> r & 1u) ? p[r] * dr.at(prow + j) : 0.f;
+      } else {
+        pd[r] = 0.f;
+      }
+    }
+    if (live) rows_mma<NS>(acc, vb, ldk, kt * 16, Lk, dh, pd, i, g, vok);
+  }
+  store_rows<NS>(acc, o + (size_t)b * Lq * ldo + h * dh, ldo, qi, qv, dh, g);
+}
+
+// attn_long_dot_kernel under the mask: a key tile with no live key adds nothing and is skipped; a masked V row is not read
+template <int NS>
+__global__ __launch_bounds__(64) void attn_long_dot_len_kernel(const float* __restrict__ dout, const float* __restrict__ v,
+                                                                const float* __restrict__ probs, float* __restrict__ dq, int H, int Lq,
+                                                                int Lk, int dh, int ldq, int ldk, int ldo, AttnKeyLen klen,
+                                                                const float* __restrict__ drop, float pdrop, uint64_t seed,
+                                                                const int64_t* __restrict__ d_offset) {
+  const Drop dr = make_drop(drop, pdrop, seed, d_offset);
+  const int b = blockIdx.y / H, h = blockIdx.y % H, q0 = blockIdx.x * 16;
+  const KeyMask km = make_key_mask(klen, b);
+  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4, qi = q0 + i;
+  const float* vb = v + (size_t)b * Lk * ldk + h * dh;
+  f32x4 dof[NS], vf[NS];
+  load_frag<NS>(dof, dout + (size_t)b * Lq * ldo + h * dh, ldo, q0, Lq, dh, i, g);
+  const size_t prow = (((size_t)b * H + h) * Lq + qi) * Lk;
+  const bool qv = qi < Lq;
+  float dot = 0.f;
+  for (int k0 = 0; k0 < Lk; k0 += 16) {
+    if (!km.tile_live(k0 / 16, Lk)) continue;
+    load_frag<NS>(vf, vb, ldk, k0, Lk, dh, i, g, km.key(k0 + i));
+    f32x4 p, pm, dpm;
+    bwd_tile_t<NS>(vf, dof, probs, dr, prow, qv, k0, Lk, g, p, pm, dpm, keys_ok4(km, k0, g));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dot += dpm[r] * p[r];
+  }
+  dot = g4_sum(dot);
+  if (qv && g == 0) dq[((size_t)b * Lq + qi) * ldq + h * dh] = dot;
+}
+
+// attn_long_dq_kernel under the mask: dS of a masked key is 0 and its K and V rows are not read; dead tiles are skipped
+template <int NS>
+__global__ __launch_bounds__(64) void attn_long_dq_len_kernel(const float* __restrict__ dout, const float* __restrict__ k,
+                                                               const float* __restrict__ v, const float* __restrict__ probs, float* dq,
+                                                               int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, AttnKeyLen klen,
+                                                               const float* __restrict__ drop, float pdrop, uint64_t seed,
+                                                               const int64_t* __restrict__ d_offset) {
+  const Drop dr = make_drop(drop, pdrop, seed, d_offset);
+  const int b = blockIdx.y / H, h = blockIdx.y % H, q0 = blockIdx.x * 16;
+  const KeyMask km = make_key_mask(klen, b);
+  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4, qi = q0 + i;
+  const float scale = rsqrtf((float)dh);
+  const float* kb = k + (size_t)b * Lk * ldk + h * dh;
+  const float* vb = v + (size_t)b * Lk * ldk + h * dh;
+  float* dqb = dq + (size_t)b * Lq * ldq + h * dh;
+  const bool qv = qi < Lq;
+  const float dot = qv ? dqb[(size_t)qi * ldq] : 0.f;                  // parked by attn_long_dot_len_kernel; overwritten below
+  f32x4 dof[NS], vf[NS], acc[NS];
+  load_frag<NS>(dof, dout + (size_t)b * Lq * ldo + h * dh, ldo, q0, Lq, dh, i, g);
+#pragma unroll
+  for (int t = 0; t < NS; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const size_t prow = (((size_t)b * H + h) * Lq + qi) * Lk;
+  for (int k0 = 0; k0 < Lk; k0 += 16) {
+    if (!km.tile_live(k0 / 16, Lk)) continue;
+    const unsigned kok = keys_ok4(km, k0, g);
+    load_frag<NS>(vf, vb, ldk, k0, Lk, dh, i, g, km.key(k0 + i));
+    f32x4 p, pm, dpm, ds;
+    bwd_tile_t<NS>(vf, dof, probs, dr, prow, qv, k0, Lk, g, p, pm, dpm, kok);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ds[r] = p[r] * (dpm[r] - dot) * scale;
+    rows_mma<NS>(acc, kb, ldk, k0, Lk, dh, ds, i, g, kok);
+  }
+  store_rows<NS>(acc, dqb, ldq, qi, qv, dh, g);
+}
+
+// attn_long_dkdv_kernel under the mask.  A workgroup whose key tile has no live key stores its zeros and leaves before the query
+// loop (uniform: b is).  In a live tile a masked key's V row is not read, its lane takes p = 0 and mask 0 without a read, and its
+// dk / dv rows are stored as literal zeros, whatever dout holds.
+template <int NS>
+__global__ __launch_bounds__(64) void attn_long_dkdv_len_kernel(const float* __restrict__ dout, const float* __restrict__ q,
+                                                                 const float* __restrict__ v, const float* __restrict__ probs,
+                                                                 const float* dq, float* __restrict__ dk, float* __restrict__ dv, int H,
+                                                                 int Lq, int Lk, int dh, int ldq, int ldk, int ldo, AttnKeyLen klen,
+                                                                 const float* __restrict__ drop, float pdrop, uint64_t seed,
+                                                                 const int64_t* __restrict__ d_offset) {
+  const Drop dr = make_drop(drop, pdrop, seed, d_offset);
+  const int b = blockIdx.y / H, h = blockIdx.y % H, k0 = blockIdx.x * 16;
+  const KeyMask km = make_key_mask(klen, b);
+  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4, kj = k0 + i;
+  const float scale = rsqrtf((float)dh);
+  const float* qb = q + (size_t)b * Lq * ldq + h * dh;
+  const float* dob = dout + (size_t)b * Lq * ldo + h * dh;
+  const float* dotb = dq + (size_t)b * Lq * ldq + h * dh;
+  float* dkb = dk + (size_t)b * Lk * ldk + h * dh;
+  float* dvb = dv + (size_t)b * Lk * ldk + h * dh;
+  const bool kv = kj < Lk;
+  const bool klive = kv && km.key(kj);
+  f32x4 vf[NS], dof[NS], akv[NS], avv[NS];
+#pragma unroll
+  for (int t = 0; t < NS; ++t) { akv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; avv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  if (!km.tile_live(blockIdx.x, Lk)) {
+    store_rows<NS>(akv, dkb, ldk, kj, kv, dh, g);
+    store_rows<NS>(avv, dvb, ldk, kj, kv, dh, g);
+    return;
+  }
+  load_frag<NS>(vf, v + (size_t)b * Lk * ldk + h * dh, ldk, k0, Lk, dh, i, g, klive);
+  for (int q0 = 0; q0 < Lq; q0 += 16) {
+    load_frag<NS>(dof, dob, ldo, q0, Lq, dh, i, g);
+    const f32x4 dp = dot_tile<NS>(dof, vf);
+    f32x4 pm, ds;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qi = q0 + 4 * g + r;
+      const bool ok = klive && qi < Lq;
+      const size_t idx = (((size_t)b * H + h) * Lq + (ok ? qi : 0)) * Lk + (ok ? kj : 0);
+      const float p = ok ? probs[idx] : 0.f;
+      const float mk = ok ? dr.at(idx) : 0.f;
+      const float dot = ok ? dotb[(size_t)qi * ldq] : 0.f;
+      pm[r] = p * mk;
+      ds[r] = p * (dp[r] * mk - dot) * scale;
+    }
+    rows_mma<NS>(avv, dob, ldo, q0, Lq, dh, pm, i, g);
+    rows_mma<NS>(akv, qb, ldq, q0, Lq, dh, ds, i, g);
+  }
+  if (!klive) {                                                        // 0 * dout is not 0 for a dout that is not finite
+#pragma unroll
+    for (int t = 0; t < NS; ++t) { akv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; avv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  }
+  store_rows<NS>(akv, dkb, ldk, kj, kv, dh, g);
+  store_rows<NS>(avv, dvb, ldk, kj, kv, dh, g);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
@@ -382,6 +603,37 @@ int attn_long_bwd_launch(const float* dout, const float* q, const float* k, cons
   AST_CHECK_LAUNCH();
   AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_dq_kernel<NS>, qgrid, dim3(64), 0, st, dout, k, v, probs, dq, H, Lq, Lk, dh, ldq, ldk,
                                      ldo, drop_mask, p, seed, d_offset));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+int attn_long_fwd_len_p_launch(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                               int dh, int ldq, int ldk, int ldo, int causal, AttnKeyLen kl, const float* drop_mask, float p,
+                               uint64_t seed, const int64_t* d_offset, void* stream) {
+  const void* ptrs[] = {q, k, v, o};
+  if (int rc = attn_long_check("ast_attn_fwd_len_p", B, H, Lq, Lk, dh, ldq, ldk, ldo, ptrs, 4)) return rc;
+  const dim3 grid((Lq + 15) / 16, B * H);
+  AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_fwd_len_kernel<NS>, grid, dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H, Lq, Lk,
+                                     dh, ldq, ldk, ldo, causal, kl, drop_mask, p, seed, d_offset));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+int attn_long_bwd_len_p_launch(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
+                               float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, AttnKeyLen kl,
+                               const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream) {
+  const void* ptrs[] = {dout, q, k, v, dq, dk, dv};
+  if (int rc = attn_long_check("ast_attn_bwd_len_p", B, H, Lq, Lk, dh, ldq, ldk, ldo, ptrs, 7)) return rc;
+  const dim3 qgrid((Lq + 15) / 16, B * H), kgrid((Lk + 15) / 16, B * H);
+  hipStream_t st = (hipStream_t)stream;
+  AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_dot_len_kernel<NS>, qgrid, dim3(64), 0, st, dout, v, probs, dq, H, Lq, Lk, dh, ldq, ldk,
+                                     ldo, kl, drop_mask, p, seed, d_offset));
+  AST_CHECK_LAUNCH();
+  AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_dkdv_len_kernel<NS>, kgrid, dim3(64), 0, st, dout, q, v, probs, (const float*)dq, dk, dv,
+                                     H, Lq, Lk, dh, ldq, ldk, ldo, kl, drop_mask, p, seed, d_offset));
+  AST_CHECK_LAUNCH();
+  AST_ATTN_NS(dh, hipLaunchKernelGGL(attn_long_dq_len_kernel<NS>, qgrid, dim3(64), 0, st, dout, k, v, probs, dq, H, Lq, Lk, dh, ldq,
+                                     ldk, ldo, kl, drop_mask, p, seed, d_offset));
   AST_CHECK_LAUNCH();
   return 0;
 }

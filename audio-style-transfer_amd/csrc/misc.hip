@@ -194,7 +194,8 @@ __global__ void bilinear_bwd_kernel(const float* __restrict__ dy, T* __restrict_
 // ML = the compile-time key-count bound (4, 8 or 16): every per-key array is indexed by a fully unrolled loop under a
 // `j < Lk` predicate, so it lives in registers (runtime-indexed arrays went to scratch memory).
 //
-// The instantiations ML + ATTN_MASK are the key-masked forward of ast_attn_fwd_len (inference: no dropout, no backward).  They
+// The instantiations ML + ATTN_MASK are the key-masked forward of ast_attn_fwd_len (inference: no dropout; the masked forward
+// with dropout and the masked backward are attn_fwd_len_kernel / attn_bwd_len_kernel below).  They
 // are the same template, so they keep its signature: with no dropout to describe, `drop` carries key_len, an int32 (B,) device
 // array, and `seed` carries key_period (pdrop = 0, d_offset = null).  Key j of batch b counts iff (j % key_period) < key_len[b],
 // key_len clamped here to [1, key_period] -- key 0 is therefore always valid and every row has a finite maximum.  A masked
@@ -310,6 +311,115 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const float* __restrict__ 
     for (int j = 0; j < ML; ++j) {
       if (j >= Lk) continue;
       dk[((size_t)b * Lk + j) * ldk + h * dh + lane] = dkv[j];
+      dv[((size_t)b * Lk + j) * ldk + h * dh + lane] = dvv[j];
+    }
+  }
+}
+
+// The key-masked training kernels of ast_attn_fwd_len_p / ast_attn_bwd_len_p: mask AND dropout, so the mask is an argument of
+// its own (AttnKeyLen).  They are kernels of their own, so the ones above stay the code they were; per element they do the
+// arithmetic of the unmasked kernels in the same order over the live keys (full lengths: bit-equal, dropout included).
+// A masked key is never loaded, takes no part in any sum, is saved with probs == 0 and gets dk = dv = 0.
+template <int ML>
+__global__ __launch_bounds__(64) void attn_fwd_len_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                           const float* __restrict__ v, float* __restrict__ o, float* __restrict__ probs,
+                                                           int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, int causal,
+                                                           AttnKeyLen klen, const float* __restrict__ drop, float pdrop, uint64_t seed,
+                                                           const int64_t* __restrict__ d_offset) {
+  const uint64_t dbase = pdrop > 0.f ? mix64(seed ^ mix64((uint64_t)(d_offset ? *d_offset : 0))) : 0;
+  const float dkeep = 1.f / (1.f - pdrop);
+  const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+  const float scale = rsqrtf((float)dh);
+  const int period = klen.period, kl = min(max(klen.len[b], 1), period);
+  float kv[ML], vv[ML];
+#pragma unroll
+  for (int j = 0; j < ML; ++j) {
+    if (j >= Lk) continue;
+    const bool ld = lane < dh && j % period < kl;
+    kv[j] = ld ? k[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+    vv[j] = ld ? v[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+  }
+  for (int i = 0; i < Lq; ++i) {
+    const float qi = lane < dh ? q[((size_t)b * Lq + i) * ldq + h * dh + lane] * scale : 0.f;
+    float s[ML];
+    float mx = -INFINITY;
+  #pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      if (j >= Lk) continue;
+      s[j] = wave_sum(qi * kv[j]);
+      if ((causal && j > i) || j % period >= kl) s[j] = -INFINITY;     // key 0 is live and never causal-masked: mx is finite
+      mx = fmaxf(mx, s[j]);
+    }
+    float den = 0.f;
+  #pragma unroll
+    for (int j = 0; j < ML; ++j) if (j < Lk) { s[j] = __expf(s[j] - mx); den += s[j]; }
+    float acc = 0.f;
+    const size_t pbase = (((size_t)b * H + h) * Lq + i) * Lk;
+  #pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      if (j >= Lk) continue;
+      const float p = s[j] / den;                                      // masked: exp(-inf - mx) / den = exactly 0
+      if (lane == 0) probs[pbase + j] = p;
+      if (j % period >= kl) continue;
+      acc += (drop ? p * drop[pbase + j] : (pdrop > 0.f ? p * dropout_keep(dbase, pbase + j, pdrop, dkeep) : p)) * vv[j];
+    }
+    if (lane < dh) o[((size_t)b * Lq + i) * ldo + h * dh + lane] = acc;
+  }
+}
+
+template <int ML>
+__global__ __launch_bounds__(64) void attn_bwd_len_kernel(const float* __restrict__ dout, const float* __restrict__ q,
+                                                           const float* __restrict__ k, const float* __restrict__ v,
+                                                           const float* __restrict__ probs, float* __restrict__ dq, float* __restrict__ dk,
+                                                           float* __restrict__ dv, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
+                                                           AttnKeyLen klen, const float* __restrict__ drop, float pdrop, uint64_t seed,
+                                                           const int64_t* __restrict__ d_offset) {
+  const uint64_t dbase = pdrop > 0.f ? mix64(seed ^ mix64((uint64_t)(d_offset ? *d_offset : 0))) : 0;
+  const float dkeep = 1.f / (1.f - pdrop);
+  const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+  const float scale = rsqrtf((float)dh);
+  const int period = klen.period, kl = min(max(klen.len[b], 1), period);
+  float kv[ML], vv[ML], dkv[ML], dvv[ML];
+#pragma unroll
+  for (int j = 0; j < ML; ++j) {
+    if (j >= Lk) continue;
+    const bool ld = lane < dh && j % period < kl;
+    kv[j] = ld ? k[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+    vv[j] = ld ? v[((size_t)b * Lk + j) * ldk + h * dh + lane] : 0.f;
+    dkv[j] = 0.f; dvv[j] = 0.f;
+  }
+  for (int i = 0; i < Lq; ++i) {
+    const float qi = lane < dh ? q[((size_t)b * Lq + i) * ldq + h * dh + lane] : 0.f;
+    const float doi = lane < dh ? dout[((size_t)b * Lq + i) * ldo + h * dh + lane] : 0.f;
+    const size_t pbase = (((size_t)b * H + h) * Lq + i) * Lk;
+    float dp[ML], p[ML];
+    float dot = 0.f;
+  #pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      if (j >= Lk) continue;
+      p[j] = 0.f; dp[j] = 0.f;
+      if (j % period >= kl) continue;                                  // uniform over the wave: the wave_sum below is safe
+      p[j] = probs[pbase + j];
+      const float m = drop ? drop[pbase + j] : (pdrop > 0.f ? dropout_keep(dbase, pbase + j, pdrop, dkeep) : 1.f);
+      dvv[j] += p[j] * m * doi;
+      dp[j] = wave_sum(doi * vv[j]) * m;
+      dot += dp[j] * p[j];
+    }
+    float dqi = 0.f;
+  #pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      if (j >= Lk || j % period >= kl) continue;
+      const float ds = p[j] * (dp[j] - dot) * scale;
+      dqi += ds * kv[j];
+      dkv[j] += ds * qi;
+    }
+    if (lane < dh) dq[((size_t)b * Lq + i) * ldq + h * dh + lane] = dqi;
+  }
+  if (lane < dh) {
+#pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      if (j >= Lk) continue;
+      dk[((size_t)b * Lk + j) * ldk + h * dh + lane] = dkv[j];         // a masked key: still the 0 it was set to
       dv[((size_t)b * Lk + j) * ldk + h * dh + lane] = dvv[j];
     }
   }
@@ -565,6 +675,53 @@ extern "C" int ast_attn_bwd(const float* dout, const float* q, const float* k, c
                             float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, const float* drop_mask,
                             void* stream) {
   return ast_attn_bwd_p(dout, q, k, v, probs, dq, dk, dv, B, H, Lq, Lk, dh, ldq, ldk, ldo, drop_mask, 0.f, 0, nullptr, stream);
+}
+
+// what ast_attn_fwd_len checks of the mask, for the two training entries
+static int attn_len_p_check(const char* who, const int32_t* key_len, int key_period, int Lq, int Lk, int dh, float p) {
+  if (!key_len) AST_FAIL("%s: key_len is NULL (the unmasked core is ast_attn_fwd_p / ast_attn_bwd_p)", who);
+  if (!(p >= 0.f && p < 1.f)) AST_FAIL("%s: needs 0 <= p < 1 (p=%g)", who, (double)p);
+  if (Lq < 1 || Lk < 1 || dh < 1 || dh > 64) AST_FAIL("%s: needs 1<=L and 1<=dh<=64 (Lq=%d Lk=%d dh=%d)", who, Lq, Lk, dh);
+  if (key_period < 1 || key_period > Lk || Lk % key_period != 0)
+    AST_FAIL("%s: needs 1 <= key_period <= Lk and Lk %% key_period == 0 (key_period=%d Lk=%d)", who, key_period, Lk);
+  return 0;
+}
+extern "C" int ast_attn_fwd_len_p(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                                  int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len, int key_period,
+                                  const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream) {
+  if (!q || !k || !v || !o || !probs) AST_FAIL("ast_attn_fwd_len_p: bad args");
+  if (int rc = attn_len_p_check("ast_attn_fwd_len_p", key_len, key_period, Lq, Lk, dh, p)) return rc;
+  const AttnKeyLen kl = {key_len, key_period};
+  if (Lq > MAXL || Lk > MAXL)
+    return attn_long_fwd_len_p_launch(q, k, v, o, probs, B, H, Lq, Lk, dh, ldq, ldk, ldo, causal, kl, drop_mask, p, seed, d_offset,
+                                      stream);
+  if (B < 1 || H < 1) AST_FAIL("ast_attn_fwd_len_p: needs B >= 1 and H >= 1 (B=%d H=%d)", B, H);
+#define AST_ATTN_FWD(ML_)                                                                                                              \
+  hipLaunchKernelGGL(attn_fwd_len_kernel<ML_>, dim3(B * H), dim3(64), 0, (hipStream_t)stream, q, k, v, o, probs, H, Lq, Lk, dh, ldq, ldk, \
+                     ldo, causal, kl, drop_mask, p, seed, d_offset)
+  if (Lk <= 4) AST_ATTN_FWD(4); else if (Lk <= 8) AST_ATTN_FWD(8); else AST_ATTN_FWD(16);
+#undef AST_ATTN_FWD
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int ast_attn_bwd_len_p(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
+                                  float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
+                                  const int32_t* key_len, int key_period, const float* drop_mask, float p, uint64_t seed,
+                                  const int64_t* d_offset, void* stream) {
+  if (!dout || !q || !k || !v || !probs || !dq || !dk || !dv) AST_FAIL("ast_attn_bwd_len_p: bad args");
+  if (int rc = attn_len_p_check("ast_attn_bwd_len_p", key_len, key_period, Lq, Lk, dh, p)) return rc;
+  const AttnKeyLen kl = {key_len, key_period};
+  if (Lq > MAXL || Lk > MAXL)
+    return attn_long_bwd_len_p_launch(dout, q, k, v, probs, dq, dk, dv, B, H, Lq, Lk, dh, ldq, ldk, ldo, kl, drop_mask, p, seed,
+                                      d_offset, stream);
+  if (B < 1 || H < 1) AST_FAIL("ast_attn_bwd_len_p: needs B >= 1 and H >= 1 (B=%d H=%d)", B, H);
+#define AST_ATTN_BWD(ML_)                                                                                                          \
+  hipLaunchKernelGGL(attn_bwd_len_kernel<ML_>, dim3(B * H), dim3(64), 0, (hipStream_t)stream, dout, q, k, v, probs, dq, dk, dv, H, Lq, \
+                     Lk, dh, ldq, ldk, ldo, kl, drop_mask, p, seed, d_offset)
+  if (Lk <= 4) AST_ATTN_BWD(4); else if (Lk <= 8) AST_ATTN_BWD(8); else AST_ATTN_BWD(16);
+#undef AST_ATTN_BWD
+  AST_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int ast_add(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream) {

@@ -325,13 +325,33 @@ int ast_attn_fwd_p(const float* q, const float* k, const float* v, float* o, flo
  * key and no value can produce NaN or an out-of-range access.  Masked keys contribute nothing, their probs entries are
  * written as 0, and their K / V rows are never read (NaN there does not reach o).  Every query row is computed; rows of
  * padded queries are finite and unspecified.  Same dispatch as ast_attn_fwd (csrc/misc.hip up to 16 x 16 tokens, csrc/attn.hip
- * past that, Lq = 1 included).  NOT built: dropout and a backward -- inference only. */
+ * past that, Lq = 1 included).  No dropout and no backward: those are ast_attn_fwd_len_p / ast_attn_bwd_len_p below. */
 int ast_attn_fwd_len(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
                      int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len /* (B,) device */, int key_period,
                      void* stream);
 int ast_attn_bwd_p(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq, float* dk,
                    float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo, const float* drop_mask,
                    float p, uint64_t seed, const int64_t* d_offset, void* stream);
+/* The key-masked core in TRAINING: zero-padded batches of clips of different lengths through the same attention calls
+ * (evaluation_style_transfer.py:135-159 for the padded batch, content_encoder.py:24-26 and new_decoder.py:208-229 for the two
+ * masks, style_encoder.py:181-187 and new_decoder.py:111-118 for nn.MultiheadAttention(dropout=0.1)).  key_len / key_period as
+ * ast_attn_fwd_len, read from the device and clamped to [1, key_period]; drop_mask / p / seed / d_offset as ast_attn_fwd_p and
+ * ast_attn_bwd_p: the element index of the draw is ((b*H + h)*Lq + i)*Lk + j whatever the mask, so with key_len[b] ==
+ * key_period everywhere both entries reproduce the unmasked ones bit for bit, dropout included.  A masked key is scored
+ * -inf and saved with probs == 0; its K and V rows are never read by the forward or by any backward kernel (NaN there
+ * reaches none of o, dq, or the dk / dv of live keys), and its dk and dv rows are WRITTEN as exactly 0: the backward still
+ * writes every element of dq, dk, dv (and uses dq as scratch before it does).  Every query row is computed from the dout it
+ * is given; the caller's loss must ignore padded query rows (dout == 0 there).  Key tiles without a live key are skipped.  No
+ * float atomics, one owner per output element, fixed summation order: bit-reproducible.  Checked on the host (error through
+ * ast_last_error): everything ast_attn_fwd_len and ast_attn_bwd_p check (key_len != NULL, 1 <= key_period <= Lk,
+ * Lk % key_period == 0, the long path's alignment and stride rules) and 0 <= p < 1. */
+int ast_attn_fwd_len_p(const float* q, const float* k, const float* v, float* o, float* probs, int B, int H, int Lq, int Lk,
+                       int dh, int ldq, int ldk, int ldo, int causal, const int32_t* key_len /* (B,) device */, int key_period,
+                       const float* drop_mask, float p, uint64_t seed, const int64_t* d_offset, void* stream);
+int ast_attn_bwd_len_p(const float* dout, const float* q, const float* k, const float* v, const float* probs, float* dq,
+                       float* dk, float* dv, int B, int H, int Lq, int Lk, int dh, int ldq, int ldk, int ldo,
+                       const int32_t* key_len /* (B,) device */, int key_period, const float* drop_mask, float p, uint64_t seed,
+                       const int64_t* d_offset, void* stream);
 
 /* ---- elementwise ------------------------------------------------------------- */
 /* out[c] += sum_r x[r][c], c < Creal  (bias gradients of Conv2d / Linear) */
