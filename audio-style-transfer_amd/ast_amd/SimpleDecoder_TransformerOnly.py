@@ -45,6 +45,22 @@ class Decoder(DecoderTrunk):
             return ops.big_out_linear(h, lin.weight, lin.bias, S, lengths).view(B, S, 2, 287, 513)
         return ops.BigLinearFn.apply(h, lin.weight, lin.bias).view(B, S, 2, 287, 513)
 
+    # ---- the same two for DecoderTrunk.forward_training_ragged: no BatchNorm here, only the two linears need the lengths ----------
+    def _check_ragged(self):
+        pass
+
+    def _encode_ragged(self, y, n_sections):
+        """_encode whose weight gradient skips the rows of padded sections (ast_linear_wgrad_len): they are user data."""
+        B, S = y.shape[:2]
+        lin = self.stft_to_embedding
+        return ops.BigLinearFn.apply(y.contiguous().reshape(B * S, -1), lin.weight, lin.bias, S, n_sections).view(B, S, self.d_model)
+
+    def _generate_ragged(self, tok, n_sections):
+        B, S, D = tok.shape
+        lin = self.embedding_to_stft
+        h = L.layer_norm(tok, self.output_norm).reshape(B * S, D)
+        return ops.BigOutLinearLenFn.apply(h, lin.weight, lin.bias, S, n_sections).view(B, S, 2, 287, 513)
+
     def generate_output(self, decoder_outputs):
         """SimpleDecoder_TransformerOnly.py:62-66."""
         return self._generate(decoder_outputs)

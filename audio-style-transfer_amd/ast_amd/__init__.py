@@ -12,6 +12,7 @@ from .content_encoder import ContentEncoder  # noqa: F401
 from .new_decoder import Decoder, compute_comprehensive_loss  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401
 from .losses import infoNCE_loss, margin_loss, adversarial_loss, disentanglement_loss, reconstruction_losses  # noqa: F401
+from .losses import ragged_reconstruction_loss  # noqa: F401
 from .metrics import mse_spectrogram, band_energy, instrumentation_similarity, mfcc, mfcc_distance  # noqa: F401
 from .metrics import estimate_tuning, chroma_stft, chroma_distance, chroma_similarity, pitch_mean, pitch_correlation  # noqa: F401
 from .metrics import onset_strength, onset_detect, onset_accuracy, recurrence_matrix, self_similarity_distance  # noqa: F401

@@ -219,6 +219,13 @@ _SIGS = {
     # per-clip reconstruction loss of a padded batch, section counts read from the device (include/ast_hip.h, ast_amd/losses.py)
     "ast_recon_loss_len_ws_floats": ([i32, i32, i32, i32], C.c_long),
     "ast_recon_loss_len": ([vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(f32), vp, C.c_long, vp, vp], i32),
+    # training on a padded batch: the same loss with its gradient, and the backward of the length-masked output linear
+    "ast_recon_loss_len_grad_ws_floats": ([i32, i32, i32, i32], C.c_long),
+    "ast_recon_loss_len_grad": ([vp, vp, i64, i32, i32, i32, i32, vp, vp, C.POINTER(f32), vp, C.c_long, vp, vp, vp, vp], i32),
+    "ast_bign_dgrad_len": ([vp, vp, vp, i32, i32, i32, i32, i32, vp, vp], i32),
+    "ast_bign_dgrad_len_det_ws_floats": ([i32, i32, i32], C.c_long),
+    "ast_bign_dgrad_len_det": ([vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_long, vp], i32),
+    "ast_linear_wgrad_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
     # 64-bit digest over the bytes of a list of device tensors (include/ast_hip.h, ast_amd/checkpoint.py)
     "ast_state_digest": ([C.POINTER(vp), C.POINTER(C.c_longlong), i32, vp, vp], i32),
 }
@@ -254,6 +261,12 @@ CALL_BYTES = {
     "ast_recon_loss_total": lambda a: 3 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
     # the per-clip values-only form: read output and target once (an upper bound for a ragged batch: padded sections are skipped)
     "ast_recon_loss_len": lambda a: 2 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
+    # the per-clip form with the gradient: read output and target, write the gradient (an upper bound for a ragged batch)
+    "ast_recon_loss_len_grad": lambda a: 3 * 4 * a[3] * a[4] * 2 * a[5] * a[6],
+    # backward of the length-masked output linear: the weight stream (N x K) plus dy; dW read and written plus dy and x
+    "ast_bign_dgrad_len": lambda a: 4 * (a[4] * a[5] + a[3] * a[4] + a[3] * a[5]),
+    "ast_bign_dgrad_len_det": lambda a: 4 * (a[4] * a[5] + a[3] * a[4] + a[3] * a[5]),
+    "ast_linear_wgrad_len": lambda a: 4 * (2 * a[5] * a[6] + a[4] * (a[5] + a[6])),
     "ast_adam": lambda a: 7 * 4 * a[4],                    # read p, g, m, v; write p, m, v
     "ast_sumsq": lambda a: 4 * a[1],
     "ast_weights_prepare_t": None,                         # bytes from NEXT_BYTES (WeightBank)

@@ -98,13 +98,54 @@ class DecoderTrunk(nn.Module):
         batch, eval mode): clip b's target tokens s >= lengths[b] are replaced by zeros first -- the causal self-attention gives
         them weight 0 in every real row, and 0 times whatever a padded target section embeds to must stay 0 -- and the
         cross-attention sees the clip's own memory tokens only."""
+        return self._generate(self._shifted_stack(emb, memory, lengths), lengths)
+
+    def _shifted_stack(self, emb, memory, lengths=None):
+        """_teacher_forced up to the stack's output tokens (B, S, d)."""
         if lengths is not None:
             S = emb.shape[1]
             keep = torch.arange(S, device=emb.device)[None, :] < lengths.clamp(1, S)[:, None]
             emb = torch.where(keep[:, :, None], emb, torch.zeros_like(emb))
         tgt = torch.cat([self.start_token.expand(emb.shape[0], 1, -1), emb[:, :-1, :]], dim=1)
         tgt = L.layer_norm(self.pos_encoding(tgt), self.input_norm)
-        return self._generate(self._stack(tgt, memory, lengths), lengths)
+        return self._stack(tgt, memory, lengths)
+
+    # ---- training on a padded batch of clips of different lengths ------------------------------------------------------------------
+    def _check_ragged(self):
+        """Subclass hook: return if this decoder has _encode_ragged and _generate_ragged, else raise NotImplementedError saying why.
+        _encode_ragged(y, n_sections): target sections (B, S, 2, 287, 513) -> (B, S, d) with nothing of sections s >= n_sections[b]
+        reaching a parameter gradient; _generate_ragged(tok, n_sections): stack output (B, S, d) -> sections, rows s >= n_sections[b]
+        exactly 0."""
+        raise NotImplementedError(f"{type(self).__module__}.{type(self).__name__} has no length-aware training pass")
+
+    def forward_training_ragged(self, content_emb, class_emb, y, n_sections):
+        """The teacher-forced training pass (forward_training) on a zero-padded batch of clips of different lengths.
+        content_emb (B, S, d), class_emb (B, d), y (B, S, 2, 287, 513) the target sections, n_sections an int32 (B,) device tensor:
+        clip b holds n_b = n_sections[b] real sections (clamped to [1, S] on the device, no host read: one captured graph serves
+        every mix of lengths).  Training mode only (eval mode: forward_teacher_forced(..., lengths=)).  Output rows s < n_b, and
+        with ast_amd.ragged_reconstruction_loss on top every gradient, are what the clips give one by one.
+        - Output sections s >= n_b are exactly 0.
+        - Padded sections of y may hold anything (NaN included): their embeddings are replaced by zeros and the weight gradient of
+          the embedding never reads them.
+        - Padded rows of content_emb must be finite: the cross-attention never sees them, but the weight gradient of their
+          projection multiplies them by an exact 0.
+        The loss must give rows s >= n_b no gradient, as ragged_reconstruction_loss does."""
+        if not self.training:
+            raise ValueError("forward_training_ragged is the training pass: call .train() first "
+                             "(in eval mode a padded batch goes through forward_teacher_forced(..., lengths=))")
+        self._check_ragged()
+        B = content_emb.shape[0]
+        if n_sections is None:
+            raise ValueError(f"n_sections must be an int32 device tensor of shape ({B},), got None")
+        n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
+        if y.dim() != 5:
+            raise ValueError(f"Expected y to have shape [B, S, 2, 287, 513], got {tuple(y.shape)}")
+        if y.shape[0] * y.shape[1] > ops.WIDE_MAX_ROWS:
+            raise RuntimeError(f"forward_training_ragged: {y.shape[0] * y.shape[1]} token rows > {ops.WIDE_MAX_ROWS} "
+                               "(the cap of the wide token path, AST_WIDE_MAX_ROWS)")
+        self._prepare()
+        memory = self._memory(content_emb, class_emb)
+        return self._generate_ragged(self._shifted_stack(self._encode_ragged(y, n), memory, n), n)
 
     def forward_training(self, y, memory):
         """new_decoder.py:231-269, SimpleDecoder_TransformerOnly.py:80-102."""

@@ -55,14 +55,43 @@ def disentanglement_loss(style_emb: torch.Tensor, content_emb: torch.Tensor, use
 RECON_KEYS = ("mse_loss", "mag_loss", "phase_loss", "temporal_loss", "spectral_loss")
 
 
-def _spectrogram_arg(t, what, shape=None):
+def _spectrogram_arg(t, what, shape=None, who="reconstruction_losses"):
     """output / target of reconstruction_losses: (B, S, 2, T, F) float32 -> its shape"""
     if not torch.is_tensor(t) or t.dim() != 5 or t.dtype != torch.float32 or t.shape[2] != 2 or t.numel() == 0:
         got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"reconstruction_losses: {what} must be a non-empty (B, S, 2, T, F) float32 tensor, got {got}")
+        raise ValueError(f"{who}: {what} must be a non-empty (B, S, 2, T, F) float32 tensor, got {got}")
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"reconstruction_losses: {what} has shape {tuple(t.shape)}, output has {tuple(shape)}")
+        raise ValueError(f"{who}: {what} has shape {tuple(t.shape)}, output has {tuple(shape)}")
     return tuple(t.shape)
+
+
+def _recon_len_args(who, ws_query, output, target, n_sections, lambda_temporal, lambda_phase, lambda_spectral, mse_weight):
+    """The one argument check of the per-clip reconstruction losses -> (n_sections, target as a [..., :F] slice, its row stride,
+    workspace floats, the five weights).  Every refusal is a ValueError that names `who` and the argument."""
+    B, S, _, T, Fq = _spectrogram_arg(output, "output", who=who)
+    _spectrogram_arg(target, "target", output.shape, who=who)
+    n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
+    for what, t in (("output", output), ("target", target)):
+        if not t.is_cuda:
+            raise ValueError(f"{who}: {what} must be on the GPU, got a tensor on {t.device} (there is no CPU path)")
+    for name, v in (("lambda_temporal", lambda_temporal), ("lambda_phase", lambda_phase), ("lambda_spectral", lambda_spectral),
+                    ("mse_weight", mse_weight)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError(f"{who}: {name} must be a number, got {v!r}")
+    need = int(ws_query(B, S, T, Fq))
+    if need < 0:
+        raise ValueError(f"{who}: output of shape {tuple(output.shape)} is out of range: {lib().ast_last_error().decode()}")
+    tgt = target.detach()
+    ld = tgt.stride(3)
+    if tgt.stride(4) != 1 or ld < Fq or tuple(tgt.stride()[:3]) != (S * 2 * T * ld, 2 * T * ld, T * ld):
+        tgt, ld = tgt.contiguous(), Fq               # anything but a [..., :F] slice of a contiguous tensor
+    return n, tgt, ld, need, (float(mse_weight), 0.5, float(lambda_phase), float(lambda_temporal), float(lambda_spectral))
+
+
+def _parts(res):
+    parts = {"total_loss": res[:, 5]}
+    parts.update({k: res[:, 6 + i] for i, k in enumerate(RECON_KEYS)})
+    return parts
 
 
 def reconstruction_losses(output, target, n_sections=None, lambda_temporal=0.3, lambda_phase=0.2, lambda_spectral=0.1, mse_weight=2.0):
@@ -70,33 +99,44 @@ def reconstruction_losses(output, target, n_sections=None, lambda_temporal=0.3, 
     of a zero-padded batch by itself: entry b of each result is the reference's value for (output[b:b+1, :n_b], target[b:b+1, :n_b]),
     n_b = n_sections[b] clamped to [1, S] on the device (None: every clip holds S sections).  Sections s >= n_b of either tensor
     are not read, so they may hold anything.  Returns a dict of (B,) float32 device tensors under the reference's keys.  Values
-    only: nothing here carries a gradient.  No host read and no atomics (ast_recon_loss_len): the call can be captured, one graph
-    serves every mix of lengths, and the values are bit-identical from run to run."""
+    only: nothing here carries a gradient (training: ragged_reconstruction_loss).  No host read and no atomics
+    (ast_recon_loss_len): the call can be captured, one graph serves every mix of lengths, and the values are bit-identical from
+    run to run."""
     import ctypes as C
-    B, S, _, T, Fq = _spectrogram_arg(output, "output")
-    _spectrogram_arg(target, "target", output.shape)
-    n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
-    for what, t in (("output", output), ("target", target)):
-        if not t.is_cuda:
-            raise ValueError(f"reconstruction_losses: {what} must be on the GPU, got a tensor on {t.device} (there is no CPU path)")
-    for name, v in (("lambda_temporal", lambda_temporal), ("lambda_phase", lambda_phase), ("lambda_spectral", lambda_spectral),
-                    ("mse_weight", mse_weight)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
-            raise ValueError(f"reconstruction_losses: {name} must be a number, got {v!r}")
-    need = int(lib().ast_recon_loss_len_ws_floats(B, S, T, Fq))
-    if need < 0:
-        raise ValueError(f"reconstruction_losses: output of shape {tuple(output.shape)} is out of range: {lib().ast_last_error().decode()}")
-    out, tgt = output.detach().contiguous(), target.detach()
-    ld = tgt.stride(3)
-    if tgt.stride(4) != 1 or ld < Fq or tuple(tgt.stride()[:3]) != (S * 2 * T * ld, 2 * T * ld, T * ld):
-        tgt, ld = tgt.contiguous(), Fq               # anything but a [..., :F] slice of a contiguous tensor
+    n, tgt, ld, need, w5 = _recon_len_args("reconstruction_losses", lib().ast_recon_loss_len_ws_floats, output, target, n_sections,
+                                           lambda_temporal, lambda_phase, lambda_spectral, mse_weight)
+    B, S, _, T, Fq = output.shape
+    out = output.detach().contiguous()
     ws = torch.empty(need, dtype=torch.float32, device=out.device)
     res = torch.empty((B, 11), dtype=torch.float32, device=out.device)
-    c5 = (C.c_float * 5)(float(mse_weight), 0.5, float(lambda_phase), float(lambda_temporal), float(lambda_spectral))
-    check(lib().ast_recon_loss_len(ptr(out), ptr(tgt), ld, B, S, T, Fq, ptr(n), c5, ptr(ws), need, ptr(res), stream()), "ast_recon_loss_len")
-    parts = {"total_loss": res[:, 5]}
-    parts.update({k: res[:, 6 + i] for i, k in enumerate(RECON_KEYS)})
-    return parts
+    check(lib().ast_recon_loss_len(ptr(out), ptr(tgt), ld, B, S, T, Fq, ptr(n), (C.c_float * 5)(*w5), ptr(ws), need, ptr(res), stream()),
+          "ast_recon_loss_len")
+    return _parts(res)
+
+
+def ragged_reconstruction_loss(output, target, n_sections=None, clip_weights=None, lambda_temporal=0.3, lambda_phase=0.2,
+                               lambda_spectral=0.1, mse_weight=2.0):
+    """The training loss of a zero-padded batch of clips of different lengths: -> (loss, parts).
+    loss = sum_b w_b * total_b, a 0-d tensor differentiable with respect to `output`; total_b is compute_comprehensive_loss of
+    clip b alone, (output[b:b+1, :n_b], target[b:b+1, :n_b]) with n_b = n_sections[b] clamped to [1, S] on the device (None:
+    every clip holds S sections), and w_b = clip_weights[b] (float32 (B,) device tensor; None: 1/B, the batch mean -- at equal
+    lengths loss is then compute_comprehensive_loss(output, target)["total_loss"] and has its gradient).  parts is the dict of
+    (B,) tensors of reconstruction_losses and carries no gradient.  The gradient rows of sections s >= n_b are exactly 0 and those
+    sections of either tensor are never read.  One streaming pass computes values and gradient (ast_recon_loss_len_grad); no host
+    read, no atomics: capturable, one graph for every mix of lengths, bit-identical from run to run.  As with the reference, the
+    phase term's gradient is undefined where an output bin is exactly 0."""
+    who = "ragged_reconstruction_loss"
+    n, tgt, ld, _, w5 = _recon_len_args(who, lib().ast_recon_loss_len_grad_ws_floats, output, target, n_sections, lambda_temporal,
+                                        lambda_phase, lambda_spectral, mse_weight)
+    B = output.shape[0]
+    cw = clip_weights
+    if cw is not None:
+        if not (torch.is_tensor(cw) and cw.dtype == torch.float32 and tuple(cw.shape) == (B,) and cw.is_cuda):
+            got = f"{cw.dtype} {tuple(cw.shape)} on {cw.device}" if torch.is_tensor(cw) else type(cw).__name__
+            raise ValueError(f"{who}: clip_weights must be a float32 device tensor of shape ({B},), got {got}")
+        cw = cw.detach().contiguous()
+    loss, res = ops.ReconLenGradFn.apply(output.contiguous(), tgt, ld, n, cw, w5)
+    return loss, _parts(res)
 
 
 def _value(dev, call, what):

@@ -88,6 +88,11 @@ class Decoder(DecoderTrunk):
         out = ops.BilinearToNCHWFn.apply(h, 2, 287, 513)
         return out.view(B, S, 2, 287, 513)
 
+    def _check_ragged(self):
+        raise NotImplementedError("new_decoder.Decoder has no length-aware training pass: the BatchNorm layers of its CNNs take their "
+                                  "statistics over every section of the batch, padded ones included "
+                                  "(SimpleDecoder_TransformerOnly.Decoder has forward_training_ragged)")
+
     def generate_output(self, decoder_outputs):
         """new_decoder.py:170-193."""
         self._prepare()

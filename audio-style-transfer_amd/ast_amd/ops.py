@@ -547,15 +547,26 @@ class BigLinearFn(torch.autograd.Function):
     """nn.Linear with one HUGE dimension on <= 1024 token rows (above 64: the row-blocked ast_*_wide entries), straight on the f32 parameter (no packed copies: the
     weight is 301 MB) -- SimpleDecoder_TransformerOnly.py:16-17.  in_features huge: ast_bigk_gemm (the input is data,
     no input gradient exists on the reference's path); out_features huge: ast_skinny_gemm forward, ast_bign_dgrad
-    backward.  Weight/bias gradients: ast_linear_wgrad into the parameter gradients."""
+    backward.  Weight/bias gradients: ast_linear_wgrad into the parameter gradients.
+    S, lengths (optional, huge in_features only): x holds the (B*S) sections of a padded batch and lengths (int32 (B,) device
+    tensor, clamped to [1, S] on the device) each clip's real ones -- the weight gradient then goes through ast_linear_wgrad_len,
+    which reads neither x nor dy in the rows of sections s >= lengths[b] (padded target sections are user data and may hold
+    anything; the forward is unchanged, so their output rows may too).  Without them the function is what it was."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, S=None, lengths=None):
         x = x.contiguous()
         rows, K = x.shape
         N = weight.shape[0]
         assert weight.shape[1] == K and x.dtype == torch.float32 and weight.is_contiguous()
         ctx.big_in = K > N
+        ctx.mask = None
+        if lengths is not None:
+            if not ctx.big_in:
+                raise ValueError("BigLinearFn: lengths belong to the huge-input linear; the huge-output one is BigOutLinearLenFn")
+            if S is None or S < 1 or rows % S:
+                raise ValueError(f"BigLinearFn: {rows} rows are not a whole number of clips of {S} sections")
+            ctx.mask = (int(S), len_tensor(lengths, rows // S, "lengths", device=True, contiguous=True))
         stem, tail = ("bigk_gemm", "_det" if config.deterministic else "") if ctx.big_in else ("skinny_gemm", "")
         _token_entry("BigLinearFn", stem, rows, tail)      # more than WIDE_MAX_ROWS rows raise before anything is allocated
         y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
@@ -577,7 +588,12 @@ class BigLinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         rows, K = x.shape
         N = w.shape[0]
-        _token_call("BigLinearFn", "linear_wgrad", rows, "", ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, rows, N, K, N, K)
+        gb = ptr(acc_grad(b)) if b is not None else None
+        if ctx.mask is not None:
+            S, lengths = ctx.mask
+            check(lib().ast_linear_wgrad_len(ptr(dy), ptr(x), ptr(acc_grad(w)), gb, rows, N, K, N, K, S, ptr(lengths), stream()), "ast_linear_wgrad_len")
+        else:
+            _token_call("BigLinearFn", "linear_wgrad", rows, "", ptr(dy), ptr(x), ptr(acc_grad(w)), gb, rows, N, K, N, K)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.big_in:
@@ -588,7 +604,56 @@ class BigLinearFn(torch.autograd.Function):
                 _token_call("BigLinearFn", "bign_dgrad", rows, "_det", ptr(dy), ptr(w), ptr(dx), rows, N, K, N, ptr(ws), ws.numel())
             else:
                 _token_call("BigLinearFn", "bign_dgrad", rows, "", ptr(dy), ptr(w), ptr(dx), rows, N, K, N)
-        return dx, None, None
+        return dx, None, None, None, None
+
+
+class BigOutLinearLenFn(torch.autograd.Function):
+    """big_out_linear for training: nn.Linear with a huge out_features on the (B*S, K) f32 rows of a padded batch, up to
+    WIDE_MAX_ROWS rows.  Forward ast_bign_gemm_len (rows of sections s >= lengths[b] are exactly 0 and their inputs never read; a
+    row that counts has the bits BigLinearFn gives it).  Backward: ast_linear_wgrad_len into the parameter gradients and
+    ast_bign_dgrad_len (deterministic mode: ast_bign_dgrad_len_det) for the input -- rows that do not count are read from neither
+    the incoming gradient nor x, and their input gradient is exactly 0.  lengths: int32 (B,) device tensor, clamped to [1, S] on
+    the device, or None (every row counts)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, S, lengths):
+        rows, K = x.shape
+        N = weight.shape[0]
+        if rows > WIDE_MAX_ROWS:                    # before anything is allocated
+            raise RuntimeError(f"BigOutLinearLenFn: {rows} token rows > {WIDE_MAX_ROWS} (the cap of the wide token path, AST_WIDE_MAX_ROWS)")
+        if S < 1 or rows % S:
+            raise ValueError(f"BigOutLinearLenFn: {rows} rows are not a whole number of clips of {S} sections")
+        lengths = len_tensor(lengths, rows // S, "lengths", device=True, contiguous=True)
+        assert weight.shape[1] == K and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.is_contiguous()
+        x = x.contiguous()
+        y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+        check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
+              "ast_bign_gemm_len")
+        ctx.save_for_backward(x)
+        ctx.weight, ctx.bias, ctx.mask = weight, bias, (int(S), lengths)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        w, b = ctx.weight, ctx.bias
+        S, lengths = ctx.mask
+        dy = dy.contiguous()
+        rows, K = x.shape
+        N = w.shape[0]
+        L = lib()
+        check(L.ast_linear_wgrad_len(ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, rows, N, K, N, K, S,
+                                     ptr(lengths), stream()), "ast_linear_wgrad_len")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            if config.deterministic:                # per-n-chunk slabs added in chunk order
+                ws = det_ws(L.ast_bign_dgrad_len_det_ws_floats(rows, N, K), x.device)
+                check(L.ast_bign_dgrad_len_det(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, S, ptr(lengths), ptr(ws), ws.numel(), stream()),
+                      "ast_bign_dgrad_len_det")
+            else:
+                check(L.ast_bign_dgrad_len(ptr(dy), ptr(w), ptr(dx), rows, N, K, N, S, ptr(lengths), stream()), "ast_bign_dgrad_len")
+        return dx, None, None, None, None
 
 
 BIGN_MAX_ROWS = 4096            # AST_BIGN_MAX_ROWS: ast_bign_gemm_len takes 1 .. 4096 rows
@@ -1492,6 +1557,35 @@ class ReconTotalFn(torch.autograd.Function):
     def backward(ctx, gtotal, gsums, gparts):
         (grad,) = ctx.saved_tensors
         return _scaled(grad, gtotal), None, None, None
+
+
+class ReconLenGradFn(torch.autograd.Function):
+    """The loss of a padded batch clip by clip, with its gradient (ast_recon_loss_len_grad): loss = sum_b w_b total_b, total_b
+    compute_comprehensive_loss of clip b alone over its own n_b sections.  Returns (loss, res (B, 11)); as in ReconTotalFn the
+    gradient with respect to out is computed in the forward pass and scaled by the upstream scalar in backward.  The arguments
+    are checked by losses.ragged_reconstruction_loss: out contiguous, tgt a [..., :F] slice with row stride ld, n_sections int32
+    (B,) and clip_weights float32 (B,) on the device or None, weights the five host numbers (mse, 0.5, phase, temporal, spectral)."""
+
+    @staticmethod
+    def forward(ctx, out, tgt, ld, n_sections, clip_weights, weights):
+        import ctypes as C
+        B, S, _, T, Fq = out.shape
+        need = int(lib().ast_recon_loss_len_grad_ws_floats(B, S, T, Fq))
+        ws = torch.empty(need, dtype=torch.float32, device=out.device)
+        res = torch.empty((B, 11), dtype=torch.float32, device=out.device)
+        loss = torch.empty(1, dtype=torch.float32, device=out.device)
+        grad = torch.empty_like(out)
+        c5 = (C.c_float * 5)(*[float(c) for c in weights])
+        check(lib().ast_recon_loss_len_grad(ptr(out), ptr(tgt), ld, B, S, T, Fq, ptr(n_sections), ptr(clip_weights), c5, ptr(ws), need,
+                                            ptr(res), ptr(loss), ptr(grad), stream()), "ast_recon_loss_len_grad")
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(res)
+        return loss[0], res
+
+    @staticmethod
+    def backward(ctx, gloss, gres):
+        (grad,) = ctx.saved_tensors
+        return _scaled(grad, gloss), None, None, None, None, None
 
 
 class InfoNCEFn(torch.autograd.Function):

@@ -197,6 +197,100 @@ __global__ __launch_bounds__(320) void recon_len_finish_kernel(const float* __re
   if (threadIdx.x == 0) out[5] = (((sk[0] + sk[1]) + sk[2]) + sk[3]) + sk[4];
 }
 
+// ---- the same per clip WITH the gradient: loss = sum_b w_b total_b and d loss / d out in one pass ----------------------------------
+// recon_len_kernel's shape (grid (workgroups per clip, B), thread = one (t, f) bin walking the clip's n_b sections, the next
+// section's values carried in registers) plus what the gradient needs: e[s-1] kept in registers and the t - 1 neighbour loaded, as
+// recon_loss_kernel does.  The five coefficients cf[k] = w_b * (weight_k / count_k(n_b)) are formed once per workgroup from
+// n_sections with recon_len_finish_kernel's counts; a term without elements has coefficient exactly 0 (and its differences are
+// never formed), so it contributes gradient exactly 0.  Sections s >= n_b are never loaded; their gradient rows are stored as
+// exactly 0 (grad arrives uninitialised).  The value side is recon_len_kernel's, sum for sum: the same slots, the same finish.
+__global__ __launch_bounds__(RLEN_THREADS) void recon_len_grad_kernel(const float* __restrict__ out, const float* __restrict__ tgt, int64_t tld,
+                                                                       int B, int S, int T, int Fq, const int32_t* __restrict__ n_sections,
+                                                                       const float* __restrict__ clip_weights, ReconLenW a,
+                                                                       float* __restrict__ part, float* __restrict__ grad) {
+  __shared__ float red[17];
+  __shared__ float cfs[5];
+  const int b = blockIdx.y;
+  const int nb = clip_sections(n_sections, b, S);
+  const unsigned bins = (unsigned)T * Fq;                       // < 2^31 (host check)
+  if (threadIdx.x < 5) {
+    const int k = threadIdx.x;
+    const long long n = nb, tf = (long long)T * Fq;
+    const long long count = k == 0 ? 2 * n * tf : k == 3 ? 2 * (n - 1) * tf : k == 4 ? 2 * n * (long long)(T - 1) * Fq : n * tf;
+    const float wb = clip_weights ? clip_weights[b] : 1.f / (float)B;
+    cfs[k] = count > 0 ? wb * (float)((double)a.w[k] / (double)count) : 0.f;
+  }
+  __syncthreads();
+  const float c_mse = cfs[0], c_mag = cfs[1], c_ph = cfs[2], c_tmp = cfs[3], c_spc = cfs[4];
+  const size_t plane_o = (size_t)T * Fq, plane_t = (size_t)T * tld;
+  const float* ob = out + (size_t)b * S * 2 * plane_o;
+  const float* tb = tgt + (size_t)b * S * 2 * plane_t;
+  float* gb = grad + (size_t)b * S * 2 * plane_o;
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (unsigned i = blockIdx.x * RLEN_THREADS + threadIdx.x; i < bins; i += gridDim.x * RLEN_THREADS) {
+    const int f = (int)(i % (unsigned)Fq), t = (int)(i / (unsigned)Fq);
+    const bool down = t + 1 < T, up = t > 0;
+    const float* po = ob + (size_t)t * Fq + f;
+    const float* pt = tb + (size_t)t * tld + f;
+    float* pg = gb + (size_t)t * Fq + f;
+    float o[2] = {po[0], po[plane_o]}, g[2] = {pt[0], pt[plane_t]};
+    float eprev[2] = {0.f, 0.f};                                // e[s-1] at (t, f)
+    for (int s = 0; s < nb; ++s) {
+      const bool more = s + 1 < nb;                             // the last REAL section has no successor, whatever lies behind it
+      float e[2], edn[2] = {0.f, 0.f}, eup[2] = {0.f, 0.f}, on[2] = {0.f, 0.f}, gn[2] = {0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float* qo = po + (size_t)(2 * s + c) * plane_o;
+        const float* qt = pt + (size_t)(2 * s + c) * plane_t;
+        e[c] = o[c] - g[c];
+        if (down) edn[c] = qo[Fq] - qt[tld];
+        if (up) eup[c] = qo[-(long)Fq] - qt[-tld];
+        if (more) { on[c] = qo[2 * plane_o]; gn[c] = qt[2 * plane_t]; }
+      }
+      const float mo2 = o[0] * o[0] + o[1] * o[1];
+      const float mo = sqrtf(mo2 + 1e-8f), mt = sqrtf(g[0] * g[0] + g[1] * g[1] + 1e-8f);
+      float dphi = atan2f(o[1], o[0]) - atan2f(g[1], g[0]);
+      dphi = dphi + PI_F;
+      dphi = dphi - 2.f * PI_F * floorf(dphi / (2.f * PI_F)) - PI_F;      // torch.remainder(., 2pi) - pi
+      acc[0] += e[0] * e[0] + e[1] * e[1];
+      acc[1] += (mo - mt) * (mo - mt);
+      acc[2] += dphi * dphi;
+      const float inv2 = 1.f / mo2;                             // atan2 backward: (-im, re) / (re^2 + im^2)
+      const float gph[2] = {-o[1] * inv2, o[0] * inv2};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        float gt = 0.f, gs = 0.f;
+        if (more) { const float d = (on[c] - gn[c]) - e[c]; acc[3] += d * d; gt -= d; }
+        if (s > 0) gt += e[c] - eprev[c];
+        if (down) { const float d = edn[c] - e[c]; acc[4] += d * d; gs -= d; }
+        if (up) gs += e[c] - eup[c];
+        pg[(size_t)(2 * s + c) * plane_o] =
+            2.f * (c_mse * e[c] + c_mag * (mo - mt) * o[c] / mo + c_ph * dphi * gph[c] + c_tmp * gt + c_spc * gs);
+        eprev[c] = e[c];
+        o[c] = on[c]; g[c] = gn[c];
+      }
+    }
+    for (int s = nb; s < S; ++s) {                              // padded sections: gradient exactly 0
+      pg[(size_t)(2 * s) * plane_o] = 0.f;
+      pg[(size_t)(2 * s + 1) * plane_o] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float v = block_sum(acc[k], red);
+    if (threadIdx.x == 0) part[((size_t)b * gridDim.x + blockIdx.x) * 5 + k] = v;
+  }
+}
+
+// loss = sum_b w_b * res[b][5]: one wave, lane l adds the clips l, l + 64, ... in order, then wave_sum's fixed butterfly
+__global__ __launch_bounds__(64) void recon_len_loss_kernel(const float* __restrict__ res, const float* __restrict__ clip_weights, int B,
+                                                             float* __restrict__ loss) {
+  float v = 0.f;
+  for (int b = threadIdx.x; b < B; b += 64) v += (clip_weights ? clip_weights[b] : 1.f / (float)B) * res[(size_t)b * 11 + 5];
+  v = wave_sum(v);
+  if (threadIdx.x == 0) loss[0] = v;
+}
+
 // ---- InfoNCE (losses.py:9-36), one workgroup of 1024 -------------------------------
 __global__ __launch_bounds__(1024) void infonce_kernel(const float* __restrict__ x, const int* __restrict__ labels, int B, int D,
                                                         float temperature, float* __restrict__ loss, float* __restrict__ dx,
@@ -573,6 +667,37 @@ extern "C" int ast_recon_loss_len(const float* out, const float* tgt, int64_t tg
   ReconLenW a;
   for (int k = 0; k < 5; ++k) a.w[k] = coef5[k];
   hipLaunchKernelGGL(recon_len_finish_kernel, dim3((unsigned)B), dim3(320), 0, s, ws, (int)nblk, S, T, Fq, n_sections, a, res);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" long ast_recon_loss_len_grad_ws_floats(int B, int S, int T, int Fq) {
+  const long nblk = recon_len_blocks(B, S, T, Fq);
+  if (nblk <= 0) AST_FAIL("ast_recon_loss_len_grad_ws_floats: bad sizes (1 <= B <= 65535, S, T, Fq >= 1, B*T*Fq < 2^31)");
+  return 5 * nblk * B;
+}
+
+// ast_recon_loss_len plus the scalar loss = sum_b w_b total_b and its gradient: the pass (stores only), ast_recon_loss_len's finish
+// and a one-wave launch for the scalar.  No atomics, no memset, no host read: capturable, bit-reproducible in both modes.
+extern "C" int ast_recon_loss_len_grad(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq,
+                                       const int32_t* n_sections, const float* clip_weights, const float* coef5, float* ws, long ws_floats,
+                                       float* res, float* loss, float* grad, void* stream) {
+  if (!out || !tgt || !coef5 || !ws || !res || !loss || !grad)
+    AST_FAIL("ast_recon_loss_len_grad: bad args (null out, tgt, coef5, ws, res, loss or grad)");
+  if (B <= 0 || S <= 0 || T <= 0 || Fq <= 0) AST_FAIL("ast_recon_loss_len_grad: bad args (B=%d S=%d T=%d Fq=%d must all be >= 1)", B, S, T, Fq);
+  if (tgt_ld < Fq) AST_FAIL("ast_recon_loss_len_grad: bad args (tgt_ld %lld < Fq %d)", (long long)tgt_ld, Fq);
+  const size_t bins = (size_t)T * Fq;                           // < 2^62: the product below cannot wrap once bins < 2^31
+  if (bins >= (1ull << 31) || (size_t)B * bins >= (1ull << 31)) AST_FAIL("ast_recon_loss_len_grad: B*T*Fq = %d*%d*%d must be < 2^31", B, T, Fq);
+  const long nblk = recon_len_blocks(B, S, T, Fq);
+  if (nblk <= 0) AST_FAIL("ast_recon_loss_len_grad: bad args (B %d > 65535)", B);
+  if (ws_floats < 5 * nblk * B) AST_FAIL("ast_recon_loss_len_grad: ws needs %ld floats, got %ld", 5 * nblk * B, ws_floats);
+  hipStream_t s = (hipStream_t)stream;
+  ReconLenW a;
+  for (int k = 0; k < 5; ++k) a.w[k] = coef5[k];
+  hipLaunchKernelGGL(recon_len_grad_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(RLEN_THREADS), 0, s, out, tgt, tgt_ld, B, S, T, Fq, n_sections,
+                     clip_weights, a, ws, grad);
+  hipLaunchKernelGGL(recon_len_finish_kernel, dim3((unsigned)B), dim3(320), 0, s, ws, (int)nblk, S, T, Fq, n_sections, a, res);
+  hipLaunchKernelGGL(recon_len_loss_kernel, dim3(1), dim3(64), 0, s, res, clip_weights, B, loss);
   AST_CHECK_LAUNCH();
   return 0;
 }

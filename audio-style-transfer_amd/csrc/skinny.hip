@@ -480,6 +480,186 @@ __global__ __launch_bounds__(256) void bign_dgrad_kernel(const float* __restrict
   }
 }
 
+// ---- backward of the length-masked output linear (ast_bign_gemm_len in training) ------------------------------------------------
+// Row m = b S + s counts iff s < clamp(n_valid[b], 1, S) (n_valid == null: every row counts); the clamp makes row 0 of every clip
+// count, so the clamped address of a masked row (row 0) is always a row that may be read.
+__device__ __forceinline__ bool row_counts(int m, int M, int S, const int32_t* __restrict__ n_valid) {
+  if (m >= M) return false;
+  if (!n_valid) return true;
+  const int b = m / S, nb = n_valid[b];
+  return m - b * S < (nb < 1 ? 1 : nb > S ? S : nb);
+}
+
+// bign_dgrad_kernel with the row mask.  A row that does not count is masked like a row >= M (its dy row is never read: clamped
+// address, operand selected to zero) and its dx row is exactly 0; a 16-row tile without a row that counts issues no dy load and no
+// MFMA; a workgroup whose RT tiles are all such tiles leaves before any load (DET: after storing the zeros of its slab).  Both
+// tests are wave-uniform (a ballot over the tile's rows).  Loop structure and MFMA order are bign_dgrad_kernel's, so with every
+// row counting the DET form gives its bits.  A second copy of the text for the reason given at bign_gemm_len_kernel.
+template <int RT, bool DET>
+__global__ __launch_bounds__(256) void bign_dgrad_len_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                              float* __restrict__ dx, int M, int N, int K, int lddy, int S,
+                                                              const int32_t* __restrict__ n_valid) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int nb0 = blockIdx.x * 512, m0 = blockIdx.y * 16 * RT;
+  const int kt0 = wave * 4;                                    // first of this wave's four 16-wide k tiles (K <= 256)
+  const float* dr[RT];
+  bool mv[RT], live[RT];                                       // lane's row of tile u counts; tile u holds such a row (wave-uniform)
+  bool any_live = false;
+  f32x4 acc[RT][4];                                            // [row tile][k tile]
+#pragma unroll
+  for (int u = 0; u < RT; ++u) {
+    const int m = m0 + 16 * u + i;
+    mv[u] = row_counts(m, M, S, n_valid);
+    live[u] = __any(mv[u]);
+    any_live = any_live || live[u];
+    dr[u] = dy + (size_t)(mv[u] ? m : 0) * lddy;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (any_live) {                                              // the same answer in every wave
+#pragma unroll 1
+    for (int sb = 0; sb < 128; sb += 8) {
+      float a[8][4], b[RT][8];
+#pragma unroll
+      for (int u = 0; u < RT; ++u) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) b[u][s] = 0.f;
+        if (!live[u]) continue;                                // one uniform branch per row tile
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          const int n = nb0 + (sb + s) * 4 + g;
+          b[u][s] = dr[u][n < N ? n : 0];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int n = nb0 + (sb + s) * 4 + g;
+        const float* wrow = w + (size_t)(n < N ? n : 0) * K;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int k = (kt0 + t) * 16 + i;
+          a[s][t] = wrow[k < K ? k : 0];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                       // the loads of the batch in flight together (see skinny_gemm_kernel)
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const bool nvv = nb0 + (sb + s) * 4 + g < N;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float aq = (nvv && (kt0 + t) * 16 + i < K) ? a[s][t] : 0.f;
+#pragma unroll
+          for (int u = 0; u < RT; ++u) {
+            if (!live[u]) continue;
+            const float bq = (nvv && mv[u]) ? b[u][s] : 0.f;
+            acc[u][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq, bq, acc[u][t], 0, 0, 0);
+          }
+        }
+      }
+    }
+  } else if (!DET) {
+    return;                                                    // dx was zeroed by the launcher
+  }
+#pragma unroll
+  for (int u = 0; u < RT; ++u) {
+    const int m = m0 + 16 * u + i;                             // D[row = 4 g + r (k)][col = i (m)]
+    if (m >= M) continue;
+    if (!DET && !mv[u]) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int k = (kt0 + t) * 16 + 4 * g + r;
+        if (k >= K) continue;
+        if constexpr (DET) dx[((size_t)blockIdx.x * M + m) * K + k] = mv[u] ? acc[u][t][r] : 0.f;
+        else unsafeAtomicAdd(dx + (size_t)m * K + k, acc[u][t][r]);
+      }
+  }
+}
+
+// linear_wgrad_tile<MS, LOOP> (MS = 4, 8, 16 without a loop for <= 64 rows, <16, true> = the row-chunked form of
+// linear_wgrad_rows_kernel beyond; no atomics, both modes) with the row mask: a row that does not count is read from neither dy nor
+// x (clamped addresses, operands selected to zero -- NaN there reaches nothing), and a batch of 4 MS rows without a row that counts
+// is skipped.  The mask of a batch is formed ONCE per wave: lane l tests row 4 st0 + l (one division, one n_valid load), a ballot
+// makes the 64 answers a wave-uniform 64-bit word, and the row of MFMA step st, lane group g is its bit 4 st + g.  A masked row
+// adds exact zeros, so with every row counting the result has the bits of ast_linear_wgrad[_wide].
+template <int MS, bool LOOP>
+__global__ __launch_bounds__(256) void linear_wgrad_len_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                float* __restrict__ dW, float* __restrict__ db, int M, int N, int K,
+                                                                int lddy, int ldw, int S, const int32_t* __restrict__ n_valid) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int n0 = (blockIdx.y * 4 + wave) * 16, k0 = blockIdx.x * 64;
+  if (n0 >= N) return;
+  const bool nv = n0 + i < N;
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  for (int st0 = 0; st0 * 4 < (LOOP ? M : 1); st0 += MS) {     // st0 = first MFMA k-step (4 rows each) of the batch
+    // LOOP = false: M <= 4 MS, so the lanes past 4 MS test rows >= M and answer no
+    const unsigned long long rows = __ballot(row_counts(st0 * 4 + lane, M, S, n_valid));
+    if (rows == 0) continue;
+    const unsigned long long mine = rows >> g;                 // bit 4 st: this lane's row of step st0 + st counts
+    unsigned cmask = 0;
+#pragma unroll
+    for (int st = 0; st < MS; ++st) cmask |= (unsigned)((mine >> (4 * st)) & 1ull) << st;
+    float av[MS], bv[MS][4];
+#pragma unroll
+    for (int st = 0; st < MS; ++st) {                          // raw loads first (clamped addresses) ...
+      const int m = (st0 + st) * 4 + g;
+      const bool mv = (cmask >> st) & 1u;
+      av[st] = dy[(size_t)(mv ? m : 0) * lddy + (nv ? n0 + i : 0)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int k = k0 + t * 16 + i;
+        const bool kv = mv && k < K;
+        bv[st][t] = x[(size_t)(kv ? m : 0) * K + (kv ? k : 0)];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);                         // ... so that the chunk's loads are in flight together
+#pragma unroll
+    for (int st = 0; st < MS; ++st) {
+      const bool mv = (cmask >> st) & 1u;
+      const float a = (mv && nv) ? av[st] : 0.f;
+      bsum += a;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float b = (mv && k0 + t * 16 + i < K) ? bv[st][t] : 0.f;
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // D[row = n0 + 4 g + r][col = k0 + 16 t + i]; the 16 old values are fetched together, then added and stored
+  float old[4][4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int k = k0 + t * 16 + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = n0 + 4 * g + r;
+      old[t][r] = (k < K && n < N) ? dW[(size_t)n * ldw + k] : 0.f;
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int k = k0 + t * 16 + i;
+    if (k >= K) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = n0 + 4 * g + r;
+      if (n < N) dW[(size_t)n * ldw + k] = old[t][r] + acc[t][r];
+    }
+  }
+  if (db && blockIdx.x == 0) {
+    bsum += __shfl_xor(bsum, 16, 64);
+    bsum += __shfl_xor(bsum, 32, 64);
+    if (g == 0 && nv) db[n0 + i] += bsum;
+  }
+}
+
 // ---- host side: one launcher per operation.  RT also fixes the row range an entry takes: RT = 1 -> 1 .. 64 rows, RT = 4 ->
 // 65 .. AST_WIDE_MAX_ROWS rows; only the wide entries check the leading dimensions.  `name` is the entry named in messages.
 template <int RT> constexpr int rows_lo() { return RT == 1 ? 1 : 65; }
@@ -577,7 +757,64 @@ int bign_dgrad_launch(const char* name, const float* dy, const float* w, float* 
   AST_CHECK_LAUNCH();
   return DET ? ast_ordered_sum(ws, (int64_t)M * K, nx, 1, dx, 0, stream) : 0;
 }
+// the masked data gradient: 1 .. AST_WIDE_MAX_ROWS rows, the 1- or 4-row-tile form picked here
+template <bool DET>
+int bign_dgrad_len_launch(const char* name, const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int S,
+                          const int32_t* n_valid, float* ws, long ws_floats, void* stream) {
+  if (!dy || !w || !dx || (DET && !ws)) AST_FAIL("%s: bad args (null dy, w, dx%s)", name, DET ? " or ws" : "");
+  if (M < 1 || M > AST_WIDE_MAX_ROWS || S < 1 || M % S || N < 1 || K < 1 || K > 256 || lddy < N)
+    AST_FAIL("%s: bad args M=%d (1..%d) S=%d (M %% S == 0) N=%d K=%d (K <= 256) lddy=%d", name, M, AST_WIDE_MAX_ROWS, S, N, K, lddy);
+  if ((((uintptr_t)dy) | ((uintptr_t)w) | ((uintptr_t)dx) | ((uintptr_t)ws) | ((uintptr_t)n_valid)) & 3)
+    AST_FAIL("%s: dy, w, dx, ws and n_valid must be 4-byte aligned", name);
+  const int nx = (N - 1) / 512 + 1;                             // N >= 1: no overflow at the largest int
+  if (DET && (nx > AST_DET_MAX_SLOTS || ws_floats < (long)nx * M * K)) AST_FAIL("%s: ws needs %ld floats (at most %d slabs)", name, (long)nx * M * K, AST_DET_MAX_SLOTS);
+  hipStream_t s = (hipStream_t)stream;
+  if (!DET) AST_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)M * K, s));
+  if (M <= 64)
+    hipLaunchKernelGGL((bign_dgrad_len_kernel<1, DET>), dim3(nx, (M + 15) / 16), dim3(256), 0, s, dy, w, DET ? ws : dx, M, N, K, lddy, S, n_valid);
+  else
+    hipLaunchKernelGGL((bign_dgrad_len_kernel<4, DET>), dim3(nx, (M + 63) / 64), dim3(256), 0, s, dy, w, DET ? ws : dx, M, N, K, lddy, S, n_valid);
+  AST_CHECK_LAUNCH();
+  return DET ? ast_ordered_sum(ws, (int64_t)M * K, nx, 1, dx, 0, stream) : 0;
+}
 }  // namespace
+
+// ---- backward of the length-masked output linear (include/ast_hip.h) --------------------------------------------------------------
+extern "C" int ast_bign_dgrad_len(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int S, const int32_t* n_valid,
+                                  void* stream) {
+  return bign_dgrad_len_launch<false>("ast_bign_dgrad_len", dy, w, dx, M, N, K, lddy, S, n_valid, nullptr, 0, stream);
+}
+
+extern "C" long ast_bign_dgrad_len_det_ws_floats(int M, int N, int K) {
+  if (M < 1 || M > AST_WIDE_MAX_ROWS || N < 1 || K < 1 || K > 256 || (N - 1) / 512 + 1 > AST_DET_MAX_SLOTS) return -1;
+  return (long)((N - 1) / 512 + 1) * M * K;
+}
+
+extern "C" int ast_bign_dgrad_len_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int S,
+                                      const int32_t* n_valid, float* ws, long ws_floats, void* stream) {
+  return bign_dgrad_len_launch<true>("ast_bign_dgrad_len_det", dy, w, dx, M, N, K, lddy, S, n_valid, ws, ws_floats, stream);
+}
+
+extern "C" int ast_linear_wgrad_len(const float* dy, const float* x, float* dW, float* db, int M, int N, int K, int lddy, int ldw, int S,
+                                    const int32_t* n_valid, void* stream) {
+  if (!dy || !x || !dW) AST_FAIL("ast_linear_wgrad_len: bad args (null dy, x or dW)");
+  if (M < 1 || M > AST_WIDE_MAX_ROWS || S < 1 || M % S || N < 1 || K < 1 || lddy < N || ldw < K)
+    AST_FAIL("ast_linear_wgrad_len: bad args M=%d (1..%d token rows) S=%d (M %% S == 0) N=%d K=%d lddy=%d ldw=%d", M, AST_WIDE_MAX_ROWS, S, N, K,
+             lddy, ldw);
+  if ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dW) | ((uintptr_t)db) | ((uintptr_t)n_valid)) & 3)
+    AST_FAIL("ast_linear_wgrad_len: dy, x, dW, db and n_valid must be 4-byte aligned");
+  dim3 grid((K - 1) / 64 + 1, (N - 1) / 64 + 1);              // N, K >= 1: no overflow at the largest int
+  if (grid.y > 65535) AST_FAIL("ast_linear_wgrad_len: N=%d too large (<= %d)", N, 65535 * 64);
+  hipStream_t s = (hipStream_t)stream;                         // the row batches of ast_linear_wgrad / ast_linear_wgrad_wide
+#define AST_WL(MS_, LOOP_) hipLaunchKernelGGL((linear_wgrad_len_kernel<MS_, LOOP_>), grid, dim3(256), 0, s, dy, x, dW, db, M, N, K, lddy, ldw, S, n_valid)
+  if (M <= 16) AST_WL(4, false);
+  else if (M <= 32) AST_WL(8, false);
+  else if (M <= 64) AST_WL(16, false);
+  else AST_WL(16, true);
+#undef AST_WL
+  AST_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int ast_linear_wgrad_batched_host(const void* host_table, int count, int max_tiles, void* stream) {
   if (!host_table || count <= 0 || max_tiles <= 0) AST_FAIL("ast_linear_wgrad_batched_host: bad args");

@@ -393,6 +393,24 @@ int ast_recon_loss_total(const float* out, const float* tgt, int64_t tgt_ld, int
 long ast_recon_loss_len_ws_floats(int B, int S, int T, int Fq);
 int ast_recon_loss_len(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const int32_t* n_sections,
                        const float* coef5, float* ws, long ws_floats, float* res, void* stream);
+/* ast_recon_loss_len with its gradient, for training on a padded batch: in one streaming pass the values of ast_recon_loss_len
+ * (res (B, 11), the same layout) and grad = d loss / d out for loss = sum_b w_b * total_b, total_b = res[b][5] the loss of clip b
+ * alone over its n_b = clamp(n_sections[b], 1, S) sections.  w_b = clip_weights[b] (float32 (B,) ON THE DEVICE), NULL = 1/B: at equal
+ * lengths loss is then the batch value of ast_recon_loss_total and grad its gradient.  loss receives the scalar (formed on the
+ * device in a fixed order by a one-wave third launch).  grad (B,S,2,T,Fq) f32 contiguous arrives uninitialised and is written
+ * completely: rows s >= n_b as exactly 0.  The per-clip coefficients w_b * coef5[k] / count_k(n_b) (the counts above) are formed on
+ * the device once per workgroup; a term without elements (temporal at n_b == 1, axis-3 difference at T == 1) contributes gradient
+ * exactly 0, and the last real section has no successor.  Sections s >= n_b of out and tgt are never read (they may hold NaN).
+ * out must be non-zero wherever the reference's phase gradient is to be finite (atan2 backward divides by re^2 + im^2, as
+ * ast_recon_loss does).  No atomics, no memset, no host read: capturable, one graph serves every mix of lengths, and every
+ * result is bit-identical from run to run in both modes.  ws >= ast_recon_loss_len_grad_ws_floats(B, S, T, Fq) floats (the size
+ * of ast_recon_loss_len_ws_floats; checked, written completely, never zeroed; the query returns < 0 for sizes the entry refuses).
+ * Checked on the host before any launch: out, tgt, coef5, ws, res, loss, grad non-null; B, S, T, Fq >= 1; tgt_ld >= Fq;
+ * B <= 65535; B*T*Fq < 2^31; ws_floats. */
+long ast_recon_loss_len_grad_ws_floats(int B, int S, int T, int Fq);
+int ast_recon_loss_len_grad(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const int32_t* n_sections,
+                            const float* clip_weights, const float* coef5, float* ws, long ws_floats, float* res, float* loss,
+                            float* grad, void* stream);
 /* losses.py on (B,256) embeddings; each writes loss[0] and optional gradients */
 int ast_infonce(const float* emb, const int32_t* labels, int B, int D, float temperature,
                 float* loss, float* demb, float* ws /* 2*B*B + B floats */, void* stream);
@@ -773,6 +791,30 @@ int ast_bign_dgrad_wide_det(const float* dy, const float* w, float* dx, int M, i
 #define AST_BIGN_MAX_ROWS 4096          /* 8 clips x 500 sections, rounded up */
 int ast_bign_gemm_len(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int ldw, int ldy, int S,
                       const int32_t* n_valid /* (M/S,) device, or NULL */, void* stream);
+
+/* ---- backward of the length-masked output linear: training on a padded batch (f32) ----------------------------------------------
+ * The row mask of ast_bign_gemm_len (row m = b S + s counts iff s < clamp(n_valid[b], 1, S); n_valid == NULL: every row counts;
+ * n_valid an int32 (M / S,) DEVICE array, clamped by the kernels) for 1 <= M <= AST_WIDE_MAX_ROWS rows; M % S == 0 is checked on
+ * the host, and ast_last_error names the entry.
+ * ast_bign_dgrad_len[_det]: dx[m][k] = sum_n dy[m][n] w[n][k], K <= 256, lddy >= N; the entry picks the 1-row-tile (M <= 64) or the
+ *   4-row-tile form of ast_bign_dgrad[_wide] itself.  A row that does not count is never read from dy (clamped address, operand
+ *   selected to zero) and its dx row is exactly 0; a 16-row tile without a counting row issues no dy load and no MFMA; a
+ *   workgroup all of whose tiles are such tiles leaves before any load.  The default form zeroes dx and adds with f32 atomics; _det
+ *   writes one [M][K] slab per 512-n chunk into ws (ast_bign_dgrad_len_det_ws_floats = ceil(N/512) * M * K floats, -1 on refused
+ *   sizes) and adds the slabs in chunk order (ast_ordered_sum): with n_valid == NULL its bits are those of ast_bign_dgrad[_wide]_det.
+ * ast_linear_wgrad_len: dW[n][k] += sum_{m counts} dy[m][n] x[m][k], db[n] += sum_{m counts} dy[m][n] (db may be NULL); lddy >= N,
+ *   ldw >= K, x rows are K apart, N <= 64 * 65535.  The kernels of ast_linear_wgrad[_wide] (one batch of 16 / 32 / 64 rows, 64-row
+ *   chunks beyond; no atomics, both modes) with the mask, formed once per wave and batch: rows that do not count are read from
+ *   neither dy nor x (NaN there reaches nothing), a 64-row chunk without a counting row is skipped.  With n_valid == NULL the result has the bits of ast_linear_wgrad[_wide].  Needed for both big linears of
+ *   SimpleDecoder_TransformerOnly.py:16-17 on a padded batch: the padded target sections that stft_to_embedding reads are user
+ *   data and may hold anything. */
+int ast_bign_dgrad_len(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int S,
+                       const int32_t* n_valid /* (M/S,) device, or NULL */, void* stream);
+long ast_bign_dgrad_len_det_ws_floats(int M, int N, int K);
+int ast_bign_dgrad_len_det(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int S, const int32_t* n_valid,
+                           float* ws, long ws_floats, void* stream);
+int ast_linear_wgrad_len(const float* dy, const float* x, float* dW, float* db, int M, int N, int K, int lddy, int ldw, int S,
+                         const int32_t* n_valid /* (M/S,) device, or NULL */, void* stream);
 
 /* ---- token programs: transformer layers in one launch (csrc/tokprog.hip) ------------------------------------------------
  * Replaces, for the <= 64 token rows of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
