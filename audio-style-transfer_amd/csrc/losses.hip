@@ -436,22 +436,24 @@ __global__ __launch_bounds__(1024) void hsic_kernel(const float* __restrict__ s,
   }
   __syncthreads();
   for (int i = tid; i < B; i += blockDim.x) {
-    float a = 0.f, b = 0.f;
-    for (int j = 0; j < B; ++j) { a += K[i * B + j]; b += L[i * B + j]; }
-    rmK[i] = a / B; rmL[i] = b / B;
+    // the centred matrices are small differences of entries near their means (K - rmK_i - rmK_j + mK is ~0.03 where K is ~0.7),
+    // and an error of a row mean enters a whole row of them with one sign: the means are summed in double
+    double a = 0.0, b = 0.0;
+    for (int j = 0; j < B; ++j) { a += (double)K[i * B + j]; b += (double)L[i * B + j]; }
+    rmK[i] = (float)(a / B); rmL[i] = (float)(b / B);
   }
   __syncthreads();
-  float tk = 0.f, tl = 0.f;
-  for (int i = tid; i < B; i += blockDim.x) { tk += rmK[i]; tl += rmL[i]; }
-  const float mK = block_sum(tk, red) / B;
-  const float mL = block_sum(tl, red) / B;
+  double tk = 0.0, tl = 0.0;
+  for (int i = 0; i < B; ++i) { tk += (double)rmK[i]; tl += (double)rmL[i]; }      // every thread the same B <= 128 values, in order
+  const float mK = (float)(tk / B);
+  const float mL = (float)(tl / B);
   const float nrm = 1.f / ((float)(B - 1) * (B - 1));
   // hsic = sum Kc_ij L_ij * nrm ; gsig = sum (Lc K nS + Kc L nC) * nrm / sigma^3
   float hp = 0.f, gsp = 0.f;
   for (int p = tid; p < B * B; p += blockDim.x) {
     const int i = p / B, j = p % B;
     const float Kc = K[p] - rmK[i] - rmK[j] + mK, Lc = L[p] - rmL[i] - rmL[j] + mL;
-    hp += Kc * L[p];
+    hp += Kc * Lc;                              // = sum Kc L (Kc is doubly centred), without the mean of L multiplying Kc's rounding
     gsp += Lc * K[p] * d2[i * M + j] + Kc * L[p] * d2[(B + i) * M + (B + j)];
   }
   const float hsic = block_sum(hp, red) * nrm;
@@ -540,7 +542,8 @@ __global__ void cross_entropy_kernel(const float* __restrict__ logits, const int
     for (int k = 0; k < C; ++k) den += __expf(z[k] - mx);
     const float lse = mx + __logf(den);
     part += (lse - z[target[r]]) / R;
-    if (dl) for (int k = 0; k < C; ++k) dl[(size_t)r * C + k] = (__expf(z[k] - lse) - (k == target[r] ? 1.f : 0.f)) / R;
+    // softmax as exp(z - max) / den: z - lse would round at the size of the logits (ulp(150) = 1.5e-5 into the exponent)
+    if (dl) for (int k = 0; k < C; ++k) dl[(size_t)r * C + k] = (__expf(z[k] - mx) / den - (k == target[r] ? 1.f : 0.f)) / R;
   }
   part = block_sum(part, red);
   if (threadIdx.x == 0) loss[0] = part;
@@ -710,19 +713,23 @@ extern "C" int ast_infonce(const float* emb, const int32_t* labels, int B, int D
   return 0;
 }
 extern "C" int ast_margin(const float* cls, int C, int D, float margin, float* loss, float* dcls, void* stream) {
-  if (!cls || !loss || C < 2) AST_FAIL("ast_margin: bad args");
+  if (!cls || !loss || C < 2 || D < 1) AST_FAIL("ast_margin: bad args (C >= 2 rows of D >= 1 floats)");
   hipLaunchKernelGGL(margin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, cls, C, D, margin, loss, dcls);
   AST_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int ast_hsic(const float* s, const float* c, int B, int D, float* loss, float* ds, float* dc, float* ws, void* stream) {
   if (!s || !c || !loss || !ws || B < 2 || B > 128) AST_FAIL("ast_hsic: bad args (2<=B<=128)");
+  if (D < 1) AST_FAIL("ast_hsic: bad args (D >= 1)");
+  if (!ds != !dc) AST_FAIL("ast_hsic: ds and dc come together (both gradients or neither)");
   hipLaunchKernelGGL(hsic_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, s, c, B, D, loss, ds, dc, ws);
   AST_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int ast_crosscov(const float* s, const float* c, int B, int D, float* loss, float* ds, float* dc, float* ws, void* stream) {
   if (!s || !c || !loss || !ws || B < 2 || B > 256) AST_FAIL("ast_crosscov: bad args (2<=B<=256)");
+  if (D < 1) AST_FAIL("ast_crosscov: bad args (D >= 1)");
+  if (!ds != !dc) AST_FAIL("ast_crosscov: ds and dc come together (both gradients or neither)");
   hipLaunchKernelGGL(crosscov_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, s, c, B, D, loss, ds, dc, ws);
   AST_CHECK_LAUNCH();
   return 0;

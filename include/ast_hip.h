@@ -411,7 +411,8 @@ long ast_recon_loss_len_grad_ws_floats(int B, int S, int T, int Fq);
 int ast_recon_loss_len_grad(const float* out, const float* tgt, int64_t tgt_ld, int B, int S, int T, int Fq, const int32_t* n_sections,
                             const float* clip_weights, const float* coef5, float* ws, long ws_floats, float* res, float* loss,
                             float* grad, void* stream);
-/* losses.py on (B,256) embeddings; each writes loss[0] and optional gradients */
+/* losses.py on (B,256) embeddings; each writes loss[0] and optional gradients.  Every row width D must be >= 1; ast_hsic and
+ * ast_crosscov take ds and dc together (both or neither): one without the other is refused, since the kernels write both or none. */
 int ast_infonce(const float* emb, const int32_t* labels, int B, int D, float temperature,
                 float* loss, float* demb, float* ws /* 2*B*B + B floats */, void* stream);
 int ast_margin(const float* cls, int C, int D, float margin, float* loss, float* dcls, void* stream);

@@ -42,6 +42,29 @@ def recon_len_ref(out, tgt, n_sections=None, lambda_temporal=0.3, lambda_phase=0
     return res
 
 
+def recon_batch_ref(out, tgt, coef5, dtype=None):
+    """The batch form with its gradient (ast_recon_loss, ast_recon_loss_total): out, tgt (B, S, 2, T, F) torch tensors ->
+    (the five raw sums over the WHOLE batch, total = sum_k coef5[k] * sums[k], d total / d out), evaluated in `dtype`
+    (default float64; float32 gives the plain single-precision evaluation the GPU tests measure their tolerance with).  The
+    sums are those of recon_len_ref with every clip full, added over the clips; a term without elements is an empty sum, 0,
+    and sends no gradient.  The gradient is autograd's, so where a bin of `out` is exactly 0 it is whatever atan2's is."""
+    import math
+    import torch
+    dt = dtype or torch.float64
+    o = out.detach().to(dt).clone().requires_grad_(True)
+    g = tgt.detach().to(dt)
+    e = o - g
+    mo = torch.sqrt(o[:, :, 0] ** 2 + o[:, :, 1] ** 2 + 1e-8)
+    mt = torch.sqrt(g[:, :, 0] ** 2 + g[:, :, 1] ** 2 + 1e-8)
+    dphi = torch.atan2(o[:, :, 1], o[:, :, 0]) - torch.atan2(g[:, :, 1], g[:, :, 0])
+    dphi = torch.remainder(dphi + math.pi, 2 * math.pi) - math.pi
+    sums = [(e ** 2).sum(), ((mo - mt) ** 2).sum(), (dphi ** 2).sum(),
+            ((e[:, 1:] - e[:, :-1]) ** 2).sum(), ((e[:, :, :, 1:] - e[:, :, :, :-1]) ** 2).sum()]
+    total = sum(float(c) * s for c, s in zip(coef5, sums))
+    (grad,) = torch.autograd.grad(total, o)
+    return torch.stack([s.detach() for s in sums]), total.detach(), grad
+
+
 # ---- the cases of tests/test_gpu_validation.py: (name, B, S, T, F, row stride of the target, n_sections or None) ----------------
 CASES = (
     ("small-ragged", 3, 3, 5, 7, 9, (3, 1, 2)),       # an unpadded clip, a one-section clip, a clip whose last real section is followed by padding
