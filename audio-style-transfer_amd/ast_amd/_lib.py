@@ -226,6 +226,16 @@ _SIGS = {
     "ast_bign_dgrad_len_det_ws_floats": ([i32, i32, i32], C.c_long),
     "ast_bign_dgrad_len_det": ([vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_long, vp], i32),
     "ast_linear_wgrad_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
+    # BatchNorm(+ReLU) and the decoder's two layout ops over the live images of a padded batch (include/ast_hip.h)
+    "ast_chan_stats_len": ([vp, vp, i32, i32, i32, i32, i32, vp, vp], i32),
+    "ast_norm_finalize_len": ([vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp], i32),
+    "ast_affine_act_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
+    "ast_norm_bwd_sums_len": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp], i32),
+    "ast_norm_bwd_finalize_len": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    "ast_norm_bwd_apply_len": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp], i32),
+    "ast_nchw_to_nhwc_len": ([vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i32, i32, vp, vp], i32),
+    "ast_bilinear_fwd_len": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32),
+    "ast_bilinear_bwd_len": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32),
     # 64-bit digest over the bytes of a list of device tensors (include/ast_hip.h, ast_amd/checkpoint.py)
     "ast_state_digest": ([C.POINTER(vp), C.POINTER(C.c_longlong), i32, vp, vp], i32),
 }

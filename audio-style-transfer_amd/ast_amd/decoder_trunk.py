@@ -130,22 +130,30 @@ class DecoderTrunk(nn.Module):
         - Padded rows of content_emb must be finite: the cross-attention never sees them, but the weight gradient of their
           projection multiplies them by an exact 0.
         The loss must give rows s >= n_b no gradient, as ragged_reconstruction_loss does."""
-        if not self.training:
-            raise ValueError("forward_training_ragged is the training pass: call .train() first "
-                             "(in eval mode a padded batch goes through forward_teacher_forced(..., lengths=))")
-        self._check_ragged()
-        B = content_emb.shape[0]
-        if n_sections is None:
-            raise ValueError(f"n_sections must be an int32 device tensor of shape ({B},), got None")
-        n = len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
-        if y.dim() != 5:
-            raise ValueError(f"Expected y to have shape [B, S, 2, 287, 513], got {tuple(y.shape)}")
-        if y.shape[0] * y.shape[1] > ops.WIDE_MAX_ROWS:
-            raise RuntimeError(f"forward_training_ragged: {y.shape[0] * y.shape[1]} token rows > {ops.WIDE_MAX_ROWS} "
-                               "(the cap of the wide token path, AST_WIDE_MAX_ROWS)")
+        n = self._ragged_args("forward_training_ragged", content_emb, y, n_sections, self._check_ragged)
         self._prepare()
         memory = self._memory(content_emb, class_emb)
         return self._generate_ragged(self._shifted_stack(self._encode_ragged(y, n), memory, n), n)
+
+    def _ragged_args(self, who, content_emb, y, n_sections, check_supported=None):
+        """The argument checks every ragged training entry point makes, in this order and before the weight bank is prepared:
+        training mode, the subclass's own refusal (check_supported), y's rank, the row cap, n_sections (len_tensor).  Returns
+        n_sections, contiguous.  (forward_training_ragged used to look at n_sections before y's rank and the row cap; a call that
+        is wrong in both now gets the shape error first -- the shape checks need no device tensor.)"""
+        if not self.training:
+            raise ValueError(f"{who} is the training pass: call .train() first "
+                             "(in eval mode a padded batch goes through forward_teacher_forced(..., lengths=))")
+        if check_supported is not None:
+            check_supported()
+        if y.dim() != 5:
+            raise ValueError(f"Expected y to have shape [B, S, 2, 287, 513], got {tuple(y.shape)}")
+        if y.shape[0] * y.shape[1] > ops.WIDE_MAX_ROWS:
+            raise RuntimeError(f"{who}: {y.shape[0] * y.shape[1]} token rows > {ops.WIDE_MAX_ROWS} "
+                               "(the cap of the wide token path, AST_WIDE_MAX_ROWS)")
+        B = content_emb.shape[0]
+        if n_sections is None:
+            raise ValueError(f"n_sections must be an int32 device tensor of shape ({B},), got None")
+        return len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
 
     def forward_training(self, y, memory):
         """new_decoder.py:231-269, SimpleDecoder_TransformerOnly.py:80-102."""

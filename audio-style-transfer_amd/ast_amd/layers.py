@@ -495,6 +495,23 @@ def conv_bn_act(x, pw, k, stride, pad, bn: nn.BatchNorm2d, training, relu=True):
     return _bn_apply(y, bn, training, relu, stats)
 
 
+# ---- the same layers over the live images of a padded batch: lengths = (n_sections, S), see ops.BatchNormActLenFn -------------
+def bn_act_len(x, bn: nn.BatchNorm2d, lengths, relu=True):
+    n_sections, S = lengths
+    return ops.BatchNormActLenFn.apply(x, bn.weight, bn.bias, bn, relu, n_sections, S)
+
+
+def conv_bn_act_len(x, pw, k, stride, pad, bn: nn.BatchNorm2d, lengths, relu=True):
+    """conv_bn_act in training mode with the BatchNorm over live images: the convolution fills no statistics table (a slot table
+    cannot be masked) and its input carries no BNLink."""
+    return bn_act_len(ops.Conv2dFn.apply(x, pw.weight, pw, k, stride, pad, False, None, None), bn, lengths, relu)
+
+
+def convT_bn_act_len(x, pw, k, stride, pad, out_pad, bn: nn.BatchNorm2d, lengths, relu=True):
+    """convT_bn_act in training mode with the BatchNorm over live images (see conv_bn_act_len)."""
+    return bn_act_len(ops.ConvT2dFn.apply(x, pw.weight, pw, k, stride, pad, out_pad, False, None, None), bn, lengths, relu)
+
+
 def layer_norm(x, ln: nn.LayerNorm):
     return ops.LayerNormFn.apply(x, ln.weight, ln.bias, ln.eps)
 

@@ -59,12 +59,29 @@ class Decoder(DecoderTrunk):
         super().register(bank)
 
     # ---- CNN halves -----------------------------------------------------------------
-    def _encode_nhwc(self, h):
+    # One body per half for the plain pass and for the padded-batch training pass (forward_training_ragged_bn).  live = None: the
+    # plain layers.  live = (n_sections, S): every BatchNorm over the live images only (layers.conv_bn_act_len /
+    # convT_bn_act_len, training mode) and the masked bilinear.  What keeps dead images out of every result then:
+    # - every BatchNorm and the bilinear store exact zeros for dead images, forward (y) and backward (dx), without loading them;
+    # - so a dead image contributes 0 x (finite) to every weight and bias gradient, PROVIDED what it holds is finite.  It is not
+    #   always zero: a bias-carrying convolution turns a dead image of zeros into its bias before the next BatchNorm zeroes it
+    #   again, and conv_decoder[0] reads sequence_to_feature of the stack's dead token rows, which are finite but not zero.
+    #   Finite they are: the masked layout conversion feeds zeros, not the caller's padding, into conv_encoder[0].
+    def _bn_layers(self, live):
+        """(conv+BN+ReLU, convT+BN+ReLU) as callables (h, pw, stride, bn) for this pass"""
         tr = self.training
+        if live is None:
+            return (lambda h, pw, s, bn: L.conv_bn_act(h, pw, 3, s, 1, bn, tr, relu=True),
+                    lambda h, pw, s, bn: L.convT_bn_act(h, pw, 3, s, 1, 1, bn, tr, relu=True))
+        return (lambda h, pw, s, bn: L.conv_bn_act_len(h, pw, 3, s, 1, bn, live),
+                lambda h, pw, s, bn: L.convT_bn_act_len(h, pw, 3, s, 1, 1, bn, live))
+
+    def _encode_nhwc(self, h, live=None):
+        conv_bn, _ = self._bn_layers(live)
         for pw, i, (_, _, s) in zip(self._enc, (0, 3, 6, 9), ENC_CH):
-            h = L.conv_bn_act(h, pw, 3, s, 1, self.conv_encoder[i + 1], tr, relu=True)
+            h = conv_bn(h, pw, s, self.conv_encoder[i + 1])
         h = ops.AdaptivePoolFn.apply(h, self.F_compressed, self.T_compressed)
-        h = L.conv_bn_act(h, self._sp[0], 3, 1, 1, self.spatial_projection[1], tr, relu=True)
+        h = conv_bn(h, self._sp[0], 1, self.spatial_projection[1])
         h = L.conv(h, self._sp[1], 1, 1, 0, True)                          # (N,32,16,8): channel 0 is the real one
         flat = ops.CastFn.apply(h[..., 0].reshape(h.shape[0], -1), torch.float32)
         return L.linear(flat, self._f2s)
@@ -74,24 +91,56 @@ class Decoder(DecoderTrunk):
         self._prepare()
         return self._encode_nhwc(ops.nchw_to_nhwc(x, L.img_dtype()))
 
-    def _generate(self, tok, lengths=None):
-        """lengths is accepted and ignored: the CNN has no length-aware form, so output sections s >= lengths[b] are finite and
-        unspecified."""
+    def _generate(self, tok, lengths=None, live=None):
+        """lengths (inference) is accepted and ignored: without `live` the CNN takes every section, so output sections
+        s >= lengths[b] are finite and unspecified.  live = (n_sections, S), training: see the note above _bn_layers; output
+        sections of dead images are exact 0."""
         B, S, D = tok.shape
-        tr = self.training
+        _, convT_bn = self._bn_layers(live)
         h = L.linear(L.layer_norm(tok, self.output_norm).reshape(B * S, D), self._s2f)       # (N,512) f32
         h = ops.CastFn.apply(h, L.img_dtype()).view(B * S, self.F_compressed, self.T_compressed, 1)
         h = torch.cat([h, h.new_zeros(B * S, self.F_compressed, self.T_compressed, 7)], dim=3)   # pad C 1 -> 8
         for pw, i in zip(self._dec[:4], (0, 3, 6, 9)):
-            h = L.convT_bn_act(h, pw, 3, 2, 1, 1, self.conv_decoder[i + 1], tr, relu=True)
+            h = convT_bn(h, pw, 2, self.conv_decoder[i + 1])
         h = L.convT(h, self._dec[4], 3, 1, 1, 0, True)                                      # (N,512,256,8)
-        out = ops.BilinearToNCHWFn.apply(h, 2, 287, 513)
+        out = ops.BilinearToNCHWFn.apply(h, 2, 287, 513) if live is None else ops.BilinearToNCHWLenFn.apply(h, 2, 287, 513, *live)
         return out.view(B, S, 2, 287, 513)
 
     def _check_ragged(self):
-        raise NotImplementedError("new_decoder.Decoder has no length-aware training pass: the BatchNorm layers of its CNNs take their "
-                                  "statistics over every section of the batch, padded ones included "
+        raise NotImplementedError("new_decoder.Decoder.forward_training_ragged does not exist: the BatchNorm layers of its CNNs couple "
+                                  "the clips of a batch, so 'what the clips give one by one' cannot hold.  forward_training_ragged_bn "
+                                  "trains on a padded batch with BatchNorm statistics over the real sections "
                                   "(SimpleDecoder_TransformerOnly.Decoder has forward_training_ragged)")
+
+    # ---- training on a padded batch: BatchNorm statistics over the real sections ---------------------------------------------------
+    def forward_training_ragged_bn(self, content_emb, class_emb, y, n_sections):
+        """The teacher-forced training pass on a zero-padded batch of clips of different lengths, with the BatchNorm statistics of
+        both CNN halves taken over the real sections only.  Arguments and contract as DecoderTrunk.forward_training_ragged:
+        content_emb (B, S, d), class_emb (B, d), y (B, S, 2, 287, 513), n_sections an int32 (B,) device tensor, clip b holding
+        n_b = clamp(n_sections[b], 1, S) real sections (clamped and counted on the device: one captured graph serves every mix of
+        lengths); training mode only; at most WIDE_MAX_ROWS token rows; output sections s >= n_b exactly 0; padded sections of y
+        may hold anything (NaN included); padded rows of content_emb must be finite; the loss must give rows s >= n_b no gradient
+        (ast_amd.ragged_reconstruction_loss).
+
+        The semantics DIFFER from the simple decoder's forward_training_ragged.  BatchNorm couples the clips of a batch, so the
+        result is NOT what the clips give one by one.  It is what the reference decoder gives when its two CNN halves see the
+        concatenation of the real sections of all clips as their image batch (sum_b n_b images: batch statistics, running
+        statistics and gradients over exactly those) and the transformer sees each clip alone.  For B = 1, and for a batch at full
+        lengths, that is the reference's forward_training.
+
+        Dead images are not zero everywhere inside the pass (see the note above _bn_layers): correctness rests on every BatchNorm
+        and the bilinear storing exact 0 for them in both directions, and on what they hold staying finite.
+
+        Every BatchNorm runs ops.BatchNormActLenFn, which takes the separate per-image statistics passes whatever config says and
+        raises ValueError under sync-BN and in deterministic mode."""
+        n = self._ragged_args("forward_training_ragged_bn", content_emb, y, n_sections,
+                              lambda: ops.check_bn_len_supported("forward_training_ragged_bn"))
+        self._prepare()
+        B, S = y.shape[:2]
+        live = (n, S)
+        memory = self._memory(content_emb, class_emb)
+        emb = self._encode_nhwc(ops.nchw_to_nhwc_len(y.view(B * S, *y.shape[2:]), L.img_dtype(), n, S), live)
+        return self._generate(self._shifted_stack(emb.view(B, S, self.d_model), memory, n), live=live)
 
     def generate_output(self, decoder_outputs):
         """new_decoder.py:170-193."""

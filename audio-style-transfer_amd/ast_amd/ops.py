@@ -944,6 +944,82 @@ class BatchNormActFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
+def _check_image_lengths(who, N, n_sections, S):
+    """(B, n_sections) for the N = B * S images of a padded batch; n_sections an int32 (B,) device tensor (len_tensor)."""
+    S = int(S)
+    if S < 1 or N % S:
+        raise ValueError(f"{who}: {N} images are not a whole number of clips of S = {S} sections")
+    if n_sections is None:
+        raise ValueError(f"{who}: n_sections must be an int32 device tensor of shape ({N // S},), got None")
+    return N // S, len_tensor(n_sections, N // S, "n_sections", device=True, contiguous=True)
+
+
+def check_bn_len_supported(who):
+    """ValueError where the BatchNorm over live images has no form: sync-BN and deterministic mode (before anything is launched)."""
+    if _SyncBN.active:
+        raise ValueError(f"{who}: sync-BN is active, and the cross-rank count of live images is not implemented")
+    if config.deterministic:
+        raise ValueError(f"{who}: deterministic mode is on, and the masked statistics passes add with atomics (no deterministic form)")
+
+
+class BatchNormActLenFn(torch.autograd.Function):
+    """relu?(BatchNorm2d(x)) in training mode over the LIVE images of a padded batch: x (B * S, H, W, C) NHWC holds the sections of
+    B clips, image b * S + s is live iff s < clamp(n_sections[b], 1, S) (int32 (B,) device tensor, clamped and counted on the
+    device: no host read).  Batch statistics, running statistics, the backward sums and the pixel count cover live images only;
+    y and dx of a dead image are exact zeros and nothing of a dead image (x, dy) is loaded.
+
+    Always the separate per-image statistics passes (ast_*_len): the GEMM-epilogue slot tables (config.fused_bn_stats), the
+    producer-side backward sums (BNLink, config.fused_bn_bwd) and ast_bn_apply_fwd / _bwd (config.fused_finalize) are indexed by
+    slot, not by image, and cannot be masked -- so none of them is used here whatever config says, and the output carries no
+    _bn_link.  No cross-rank (sync-BN) and no deterministic form: both raise ValueError; eval mode needs no lengths (running
+    statistics are per pixel) and raises too."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, relu, n_sections, S):
+        if not bn.training:
+            raise ValueError("BatchNormActLenFn is the training-mode BatchNorm over live images: in eval mode the running statistics "
+                             "apply per pixel and need no lengths (ops.BatchNormActFn)")
+        check_bn_len_supported("BatchNormActLenFn")
+        N, H, W, C = x.shape
+        B, n = _check_image_lengths("BatchNormActLenFn", N, n_sections, S)
+        x = x.contiguous()
+        dt, HW, L = dcode(x.dtype), H * W, lib()
+        sums = stat_table(N * C * 2, x.device)
+        check(L.ast_chan_stats_len(ptr(x), ptr(sums), B, S, HW, C, dt, ptr(n), stream()), "ast_chan_stats_len")
+        out = torch.empty((4, C), dtype=torch.float32, device=x.device)
+        mean, rstd, scale, shift = out[0], out[1], out[2], out[3]
+        check(L.ast_norm_finalize_len(ptr(sums), ptr(bn.num_batches_tracked), B, S, HW, C, gamma.numel(), ptr(gamma), ptr(beta),
+                                      ptr(bn.running_mean), ptr(bn.running_var), bn.eps, ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
+                                      ptr(n), stream()), "ast_norm_finalize_len")
+        y = torch.empty_like(x)
+        check(L.ast_affine_act_len(ptr(x), ptr(scale), ptr(shift), ptr(y), B, S, HW, C, int(relu), dt, ptr(n), stream()),
+              "ast_affine_act_len")
+        ctx.save_for_backward(x, y, mean, rstd, scale, shift, n)
+        ctx.gamma, ctx.beta, ctx.relu, ctx.S = gamma, beta, bool(relu), S
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, mean, rstd, scale, shift, n = ctx.saved_tensors
+        check_bn_len_supported("BatchNormActLenFn.backward")
+        pre = config.bn_mask_from_preact and ctx.relu          # as BatchNormActFn: the ReLU mask recomputed from x, y is not read
+        dy = dy.contiguous()
+        N, H, W, C = x.shape
+        S, B, HW, dt, L = ctx.S, N // ctx.S, H * W, dcode(x.dtype), lib()
+        gamma, beta = ctx.gamma, ctx.beta
+        sc, sf = (ptr(scale), ptr(shift)) if pre else (None, None)
+        sums3 = _clean_scratch(N * C * 3, x.device)
+        check(L.ast_norm_bwd_sums_len(ptr(dy), ptr(y), ptr(x), ptr(sums3), B, S, HW, C, int(ctx.relu), dt, sc, sf, ptr(n), stream()),
+              "ast_norm_bwd_sums_len")
+        k1 = torch.empty((C, 3), dtype=torch.float32, device=x.device)
+        check(L.ast_norm_bwd_finalize_len(ptr(sums3), B, S, HW, C, gamma.numel(), ptr(gamma), ptr(mean), ptr(rstd), ptr(acc_grad(gamma)),
+                                          ptr(acc_grad(beta)), ptr(k1), ptr(n), stream()), "ast_norm_bwd_finalize_len")
+        dx = torch.empty_like(x)
+        check(L.ast_norm_bwd_apply_len(ptr(dy), ptr(y), ptr(x), ptr(k1), ptr(dx), B, S, HW, C, int(ctx.relu), dt, sc, sf, ptr(n),
+                                       stream()), "ast_norm_bwd_apply_len")
+        return dx, None, None, None, None, None, None
+
+
 class ResTailFn(torch.autograd.Function):
     """relu(BatchNorm2d(c2) + InstanceNorm2d(ds)) -- the ResBlock tail
     (style_encoder.py:76-83) as one elementwise pass over both branches."""
@@ -1246,6 +1322,45 @@ def nchw_to_nhwc(x4, dtype, Cp=None):
     y = torch.empty((N, H, W, Cp), dtype=dtype, device=x4.device)
     check(lib().ast_nchw_to_nhwc(ptr(x4), ptr(y), N, Cc, H, W, x4.stride(0), x4.stride(1), x4.stride(2), Cp, dcode(dtype),
                                  stream()), "ast_nchw_to_nhwc")
+    return y
+
+
+class BilinearToNCHWLenFn(torch.autograd.Function):
+    """BilinearToNCHWFn on the N = B * S images of a padded batch (n_sections: see BatchNormActLenFn): output sections of dead
+    images are exact 0; in the backward their dx is exact 0 and their dy is never read."""
+
+    @staticmethod
+    def forward(ctx, x, C, Ho, Wo, n_sections, S):
+        N, H, W, Cp = x.shape
+        B, n = _check_image_lengths("BilinearToNCHWLenFn", N, n_sections, S)
+        x = x.contiguous()
+        y = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=x.device)
+        check(lib().ast_bilinear_fwd_len(ptr(x), ptr(y), B, S, C, Cp, H, W, Ho, Wo, dcode(x.dtype), ptr(n), stream()), "ast_bilinear_fwd_len")
+        ctx.dims, ctx.dtype = (B, S, C, Cp, H, W, Ho, Wo), x.dtype
+        ctx.save_for_backward(n)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, S, C, Cp, H, W, Ho, Wo = ctx.dims
+        n, = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty((B * S, H, W, Cp), dtype=ctx.dtype, device=dy.device)
+        check(lib().ast_bilinear_bwd_len(ptr(dy), ptr(dx), B, S, C, Cp, H, W, Ho, Wo, dcode(ctx.dtype), ptr(n), stream()),
+              "ast_bilinear_bwd_len")
+        return dx, None, None, None, None, None
+
+
+def nchw_to_nhwc_len(x4, dtype, n_sections, S, Cp=None):
+    """nchw_to_nhwc on the N = B * S images of a padded batch (n_sections: see BatchNormActLenFn): dead images come out as zeros
+    and are never read, so padded sections may hold anything, NaN included (no grad: model inputs)."""
+    N, Cc, H, W = x4.shape
+    assert x4.dtype == torch.float32 and x4.stride(3) == 1, "expects f32 with contiguous last dim"
+    B, n = _check_image_lengths("nchw_to_nhwc_len", N, n_sections, S)
+    Cp = Cp or pad8(Cc)
+    y = torch.empty((N, H, W, Cp), dtype=dtype, device=x4.device)
+    check(lib().ast_nchw_to_nhwc_len(ptr(x4), ptr(y), B, S, Cc, H, W, x4.stride(0), x4.stride(1), x4.stride(2), Cp, dcode(dtype),
+                                     ptr(n), stream()), "ast_nchw_to_nhwc_len")
     return y
 
 

@@ -36,6 +36,12 @@ __host__ __device__ inline AstClipLen ast_clip_len(int ns_raw, int nsamp, int wi
   return L;
 }
 
+// ---- sections of a padded batch of B clips x S sections (the image and token kernels that take n_sections): clip b holds
+// n_b = clamp(n_sections[b], 1, S) real sections, clamped where it is read and never on the host; section s of clip b is live iff s < n_b
+__host__ __device__ inline int ast_live_sections(int n_raw, int S) { return n_raw < 1 ? 1 : (n_raw > S ? S : n_raw); }
+// the most images (B * S) an entry that takes n_sections accepts: counts stay exact in f32 and image indices stay ints
+#define AST_LEN_MAX_IMAGES (1 << 24)
+
 // samples of the clip after o ceil-halvings (librosa's audio.resample(2 -> 1) between octaves): ceil(ns / 2^o)
 __host__ __device__ inline int ast_halved(int ns, int o) { return (int)(((long long)ns + (1ll << o) - 1) >> o); }
 

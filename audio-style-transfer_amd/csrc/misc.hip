@@ -1,6 +1,7 @@
 // Layout conversion at the module boundary, pooling / resampling with the exact
 // torch index rules, the tiny-sequence attention core and elementwise helpers.
 #include "ast_common.h"
+#include "ast_lengths.h"
 #include "../../include/ast_hip.h"
 
 namespace {
@@ -107,85 +108,154 @@ __device__ __forceinline__ void bil_src(int o, float scale, int in, int& i0, int
   lam = s - (float)i0;
 }
 
+// one output pixel (n, ho, wo), all C planes; shared by the plain and the length-aware kernel
+template <typename T>
+__device__ __forceinline__ void bilinear_fwd_pixel(const T* __restrict__ x, float* __restrict__ y, int C, int Cp, int H, int W, int Ho, int Wo,
+                                                   const float sh, const float sw, const int n, const int ho, const int wo) {
+  int h0, h1, w0, w1; float lh, lw;
+  bil_src(ho, sh, H, h0, h1, lh);
+  bil_src(wo, sw, W, w0, w1, lw);
+  const T* b = x + (size_t)n * H * W * Cp;
+  for (int c = 0; c < C; ++c) {
+    const float v00 = (float)b[((size_t)h0 * W + w0) * Cp + c], v01 = (float)b[((size_t)h0 * W + w1) * Cp + c];
+    const float v10 = (float)b[((size_t)h1 * W + w0) * Cp + c], v11 = (float)b[((size_t)h1 * W + w1) * Cp + c];
+    y[((size_t)n * C + c) * Ho * Wo + (size_t)ho * Wo + wo] =
+        (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
+  }
+}
+
 template <typename T>
 __global__ void bilinear_fwd_kernel(const T* __restrict__ x, float* __restrict__ y, int C, int Cp, int H, int W, int Ho, int Wo, size_t npix) {
   const float sh = (float)H / Ho, sw = (float)W / Wo;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
     const int wo = (int)(i % Wo);
     const size_t t = i / Wo;
-    const int ho = (int)(t % Ho);
-    const int n = (int)(t / Ho);
-    int h0, h1, w0, w1; float lh, lw;
-    bil_src(ho, sh, H, h0, h1, lh);
-    bil_src(wo, sw, W, w0, w1, lw);
-    const T* b = x + (size_t)n * H * W * Cp;
-    for (int c = 0; c < C; ++c) {
-      const float v00 = (float)b[((size_t)h0 * W + w0) * Cp + c], v01 = (float)b[((size_t)h0 * W + w1) * Cp + c];
-      const float v10 = (float)b[((size_t)h1 * W + w0) * Cp + c], v11 = (float)b[((size_t)h1 * W + w1) * Cp + c];
-      y[((size_t)n * C + c) * Ho * Wo + (size_t)ho * Wo + wo] =
-          (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
-    }
+    bilinear_fwd_pixel<T>(x, y, C, Cp, H, W, Ho, Wo, sh, sw, (int)(t / Ho), (int)(t % Ho), wo);
   }
 }
 
 // gather form of the backward: every input pixel sums the output pixels that tap it
+template <typename T>
+__device__ __forceinline__ void bilinear_bwd_pixel(const float* __restrict__ dy, T* __restrict__ dx, int C, int Cp, int H, int W, int Ho, int Wo,
+                                                   const float sh, const float sw, const int n, const int h, const int w) {
+  const size_t i = ((size_t)n * H + h) * W + w;
+  const int olo_h = max(0, (int)floorf((h - 1 + 0.5f) / sh - 0.5f) - 1), ohi_h = min(Ho - 1, (int)ceilf((h + 1 + 0.5f) / sh - 0.5f) + 1);
+  const int olo_w = max(0, (int)floorf((w - 1 + 0.5f) / sw - 0.5f) - 1), ohi_w = min(Wo - 1, (int)ceilf((w + 1 + 0.5f) / sw - 0.5f) + 1);
+  float a0 = 0.f, a1 = 0.f;   // C <= 2 (real / imaginary planes)
+  // the column weights do not depend on the output row: computed once per pixel (up to 10 candidate columns in registers; the
+  // 5 x 5 candidate window used to evaluate bil_src 30 times per pixel -- 32 us on the step's chain for a 1:1 resize)
+  constexpr int MAXC = 10;
+  const int ncw = ohi_w - olo_w + 1;
+  float cwv[MAXC];
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) {
+    cwv[k] = 0.f;
+    if (k < ncw) {
+      int w0, w1; float lw;
+      bil_src(olo_w + k, sw, W, w0, w1, lw);
+      cwv[k] = (w0 == w ? 1.f - lw : 0.f) + (w1 == w ? lw : 0.f);
+    }
+  }
+  for (int oh = olo_h; oh <= ohi_h; ++oh) {
+    int h0, h1; float lh;
+    bil_src(oh, sh, H, h0, h1, lh);
+    const float ch = (h0 == h ? 1.f - lh : 0.f) + (h1 == h ? lh : 0.f);
+    if (ch == 0.f) continue;
+    const float* r0 = dy + ((size_t)n * C + 0) * Ho * Wo + (size_t)oh * Wo + olo_w;
+    const float* r1 = r0 + (size_t)Ho * Wo;
+    if (ncw <= MAXC) {
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k) {
+        if (k < ncw && cwv[k] != 0.f) {
+          a0 += ch * cwv[k] * r0[k];
+          if (C > 1) a1 += ch * cwv[k] * r1[k];
+        }
+      }
+    } else {
+      for (int ow = olo_w; ow <= ohi_w; ++ow) {
+        int w0, w1; float lw;
+        bil_src(ow, sw, W, w0, w1, lw);
+        const float cw = (w0 == w ? 1.f - lw : 0.f) + (w1 == w ? lw : 0.f);
+        if (cw == 0.f) continue;
+        a0 += ch * cw * r0[ow - olo_w];
+        if (C > 1) a1 += ch * cw * r1[ow - olo_w];
+      }
+    }
+  }
+  for (int u = 0; u < Cp; u += 8) {
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = 0.f;
+    if (u == 0) { v[0] = a0; if (C > 1) v[1] = a1; }
+    U8<T>::store(dx + i * Cp + u, v);
+  }
+}
+
 template <typename T>
 __global__ void bilinear_bwd_kernel(const float* __restrict__ dy, T* __restrict__ dx, int C, int Cp, int H, int W, int Ho, int Wo, size_t npix) {
   const float sh = (float)H / Ho, sw = (float)W / Wo;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
     const int w = (int)(i % W);
     const size_t t = i / W;
-    const int h = (int)(t % H);
-    const int n = (int)(t / H);
-    const int olo_h = max(0, (int)floorf((h - 1 + 0.5f) / sh - 0.5f) - 1), ohi_h = min(Ho - 1, (int)ceilf((h + 1 + 0.5f) / sh - 0.5f) + 1);
-    const int olo_w = max(0, (int)floorf((w - 1 + 0.5f) / sw - 0.5f) - 1), ohi_w = min(Wo - 1, (int)ceilf((w + 1 + 0.5f) / sw - 0.5f) + 1);
-    float a0 = 0.f, a1 = 0.f;   // C <= 2 (real / imaginary planes)
-    // the column weights do not depend on the output row: computed once per pixel (up to 10 candidate columns in registers; the
-    // 5 x 5 candidate window used to evaluate bil_src 30 times per pixel -- 32 us on the step's chain for a 1:1 resize)
-    constexpr int MAXC = 10;
-    const int ncw = ohi_w - olo_w + 1;
-    float cwv[MAXC];
-#pragma unroll
-    for (int k = 0; k < MAXC; ++k) {
-      cwv[k] = 0.f;
-      if (k < ncw) {
-        int w0, w1; float lw;
-        bil_src(olo_w + k, sw, W, w0, w1, lw);
-        cwv[k] = (w0 == w ? 1.f - lw : 0.f) + (w1 == w ? lw : 0.f);
-      }
-    }
-    for (int oh = olo_h; oh <= ohi_h; ++oh) {
-      int h0, h1; float lh;
-      bil_src(oh, sh, H, h0, h1, lh);
-      const float ch = (h0 == h ? 1.f - lh : 0.f) + (h1 == h ? lh : 0.f);
-      if (ch == 0.f) continue;
-      const float* r0 = dy + ((size_t)n * C + 0) * Ho * Wo + (size_t)oh * Wo + olo_w;
-      const float* r1 = r0 + (size_t)Ho * Wo;
-      if (ncw <= MAXC) {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) {
-          if (k < ncw && cwv[k] != 0.f) {
-            a0 += ch * cwv[k] * r0[k];
-            if (C > 1) a1 += ch * cwv[k] * r1[k];
-          }
-        }
-      } else {
-        for (int ow = olo_w; ow <= ohi_w; ++ow) {
-          int w0, w1; float lw;
-          bil_src(ow, sw, W, w0, w1, lw);
-          const float cw = (w0 == w ? 1.f - lw : 0.f) + (w1 == w ? lw : 0.f);
-          if (cw == 0.f) continue;
-          a0 += ch * cw * r0[ow - olo_w];
-          if (C > 1) a1 += ch * cw * r1[ow - olo_w];
-        }
-      }
-    }
+    bilinear_bwd_pixel<T>(dy, dx, C, Cp, H, W, Ho, Wo, sh, sw, (int)(t / H), (int)(t % H), w);
+  }
+}
+
+// ---- the two layout ops on a padded batch of B clips x S sections (ast_nchw_to_nhwc_len, ast_bilinear_fwd_len / _bwd_len) ----
+// Grid = (blocks per image, S, B): image n = b * S + s is live iff s < clamp(n_sections[b], 1, S) (int32 (B,) device array), one
+// compare per workgroup.  A dead image's workgroups store zeros over its output and load nothing.
+__device__ __forceinline__ bool section_live(const int32_t* __restrict__ n_sections, const int S) {
+  return (int)blockIdx.y < ast_live_sections(n_sections[blockIdx.z], S);
+}
+
+template <typename T>
+__global__ void nchw_to_nhwc_len_kernel(const float* __restrict__ x, T* __restrict__ y, int C, int H, int W, int64_t sn, int64_t sc,
+                                        int64_t sh, int Cp, const int32_t* __restrict__ n_sections, int S) {
+  const bool live = section_live(n_sections, S);
+  const size_t n = (size_t)blockIdx.z * S + blockIdx.y;
+  const int HW = H * W;
+  T* yn = y + n * HW * Cp;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int h = p / W, w = p - h * W;
+    const float* px = x + n * sn + h * sh + w;
     for (int u = 0; u < Cp; u += 8) {
       float v[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = 0.f;
-      if (u == 0) { v[0] = a0; if (C > 1) v[1] = a1; }
-      U8<T>::store(dx + i * Cp + u, v);
+      for (int k = 0; k < 8; ++k) v[k] = (live && (u + k) < C) ? px[(u + k) * sc] : 0.f;
+      U8<T>::store(yn + (size_t)p * Cp + u, v);
+    }
+  }
+}
+
+template <typename T>
+__global__ void bilinear_fwd_len_kernel(const T* __restrict__ x, float* __restrict__ y, int C, int Cp, int H, int W, int Ho, int Wo,
+                                        const int32_t* __restrict__ n_sections, int S) {
+  const bool live = section_live(n_sections, S);
+  const int n = blockIdx.z * S + blockIdx.y;
+  const float sh = (float)H / Ho, sw = (float)W / Wo;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < Ho * Wo; p += gridDim.x * blockDim.x) {
+    const int ho = p / Wo, wo = p - ho * Wo;
+    if (live) {
+      bilinear_fwd_pixel<T>(x, y, C, Cp, H, W, Ho, Wo, sh, sw, n, ho, wo);
+    } else {
+      for (int c = 0; c < C; ++c) y[((size_t)n * C + c) * Ho * Wo + p] = 0.f;
+    }
+  }
+}
+
+template <typename T>
+__global__ void bilinear_bwd_len_kernel(const float* __restrict__ dy, T* __restrict__ dx, int C, int Cp, int H, int W, int Ho, int Wo,
+                                        const int32_t* __restrict__ n_sections, int S) {
+  const bool live = section_live(n_sections, S);
+  const int n = blockIdx.z * S + blockIdx.y;
+  const float sh = (float)H / Ho, sw = (float)W / Wo;
+  const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < H * W; p += gridDim.x * blockDim.x) {
+    const int h = p / W, w = p - h * W;
+    if (live) {
+      bilinear_bwd_pixel<T>(dy, dx, C, Cp, H, W, Ho, Wo, sh, sw, n, h, w);
+    } else {
+      for (int u = 0; u < Cp; u += 8) U8<T>::store(dx + (((size_t)n * H + h) * W + w) * Cp + u, z);
     }
   }
 }
@@ -614,6 +684,48 @@ extern "C" int ast_bilinear_bwd(const float* dy, void* dx, int N, int C, int Cp,
   const size_t npix = (size_t)N * H * W;
   AST_DISPATCH_T(dtype, hipLaunchKernelGGL((bilinear_bwd_kernel<T>), dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, dy,
                                             (T*)dx, C, Cp, H, W, Ho, Wo, npix));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the layout ops on a padded batch (include/ast_hip.h): N = B * S images, dead ones written as zeros and never read
+namespace {
+int layout_len_check(const char* name, int B, int S, long in_pix, long out_pix, const void* n_sections) {
+  if (!n_sections) AST_FAIL("%s: n_sections is NULL (an int32 (B,) device array)", name);
+  if (B < 1 || B > 65535 || S < 1 || S > 65535 || (long)B * S > AST_LEN_MAX_IMAGES || in_pix < 1 || out_pix < 1 || in_pix > 0x7fffffffL ||
+      out_pix > 0x7fffffffL)
+    AST_FAIL("%s: bad args B=%d S=%d (1 <= B, S <= 65535, B * S <= 2^24; an image holds 1 .. 2^31 - 1 pixels)", name, B, S);
+  return 0;
+}
+int blocks_per_image(long pix, int N) { return (int)std::max<long>(1, std::min<long>((pix + 255) / 256, std::max(1, 4096 / N))); }
+}  // namespace
+
+extern "C" int ast_nchw_to_nhwc_len(const float* x, void* y, int B, int S, int C, int H, int W, int64_t sn, int64_t sc, int64_t sh, int Cp,
+                                    int dtype, const int32_t* n_sections, void* stream) {
+  if (!x || !y || C < 1 || C > Cp || (Cp & 7) || H <= 0 || W <= 0) AST_FAIL("ast_nchw_to_nhwc_len: bad args");
+  if (layout_len_check("ast_nchw_to_nhwc_len", B, S, (long)H * W, (long)H * W, n_sections)) return -1;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((nchw_to_nhwc_len_kernel<T>), dim3(blocks_per_image((long)H * W, B * S), S, B), dim3(256), 0,
+                                            (hipStream_t)stream, x, (T*)y, C, H, W, sn, sc, sh, Cp, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_bilinear_fwd_len(const void* x, float* y, int B, int S, int C, int Cp, int H, int W, int Ho, int Wo, int dtype,
+                                    const int32_t* n_sections, void* stream) {
+  if (!x || !y || C < 1 || C > Cp || C > 8 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) AST_FAIL("ast_bilinear_fwd_len: bad args");
+  if (layout_len_check("ast_bilinear_fwd_len", B, S, (long)H * W, (long)Ho * Wo, n_sections)) return -1;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((bilinear_fwd_len_kernel<T>), dim3(blocks_per_image((long)Ho * Wo, B * S), S, B), dim3(256), 0,
+                                            (hipStream_t)stream, (const T*)x, y, C, Cp, H, W, Ho, Wo, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_bilinear_bwd_len(const float* dy, void* dx, int B, int S, int C, int Cp, int H, int W, int Ho, int Wo, int dtype,
+                                    const int32_t* n_sections, void* stream) {
+  if (!dy || !dx || C < 1 || C > Cp || C > 2 || (Cp & 7) || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) AST_FAIL("ast_bilinear_bwd_len: bad args (C<=2)");
+  if (layout_len_check("ast_bilinear_bwd_len", B, S, (long)H * W, (long)Ho * Wo, n_sections)) return -1;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((bilinear_bwd_len_kernel<T>), dim3(blocks_per_image((long)H * W, B * S), S, B), dim3(256), 0,
+                                            (hipStream_t)stream, dy, (T*)dx, C, Cp, H, W, Ho, Wo, n_sections, S));
   AST_CHECK_LAUNCH();
   return 0;
 }

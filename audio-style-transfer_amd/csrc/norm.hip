@@ -5,6 +5,7 @@
 //   backward: norm_bwd_sums -> norm_bwd_finalize -> norm_bwd_apply (one reduce
 //   pass + one elementwise pass for both branches together)
 #include "ast_common.h"
+#include "ast_lengths.h"
 #include "../../include/ast_hip.h"
 
 namespace {
@@ -14,12 +15,13 @@ namespace {
 // MODE 1: {dz, dz*x, dz*r}   (K=3)   inputs: a=dy, b=y (relu mask), c=x, d=r (may be null)
 // DET (deterministic mode): the workgroup STORES its sums into slot row blockIdx.x of its image -- sums is then the
 // [N][gridDim.x][C][K] slot table that ast_ordered_sum reduces in slot order -- instead of adding them with atomics.
+// The body takes its image n from the caller: blockIdx.y in the plain kernels, b * S + s in the length-aware ones.
 template <typename T, int MODE, bool DET = false>
-__global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b,
-                                                           const T* __restrict__ c, const T* __restrict__ d,
-                                                           float* __restrict__ sums, int HW, int C, int ppb, int relu,
-                                                           const float* __restrict__ sc1, const float* __restrict__ sf1,
-                                                           const float* __restrict__ sc2, const float* __restrict__ sf2) {
+__device__ __forceinline__ void chan_reduce_body(const T* __restrict__ a, const T* __restrict__ b,
+                                                 const T* __restrict__ c, const T* __restrict__ d,
+                                                 float* __restrict__ sums, int HW, int C, int ppb, int relu,
+                                                 const float* __restrict__ sc1, const float* __restrict__ sf1,
+                                                 const float* __restrict__ sc2, const float* __restrict__ sf2, const int n) {
   // MODE 1 with sc1 != null: the ReLU mask is recomputed from the pre-activation fma(x, sc1, sf1) [+ fma(r, sc2[n], sf2[n])]
   // exactly as affine_act_kernel formed it, so the activation output `b` is not read at all (one third of the traffic)
   constexpr int K = MODE == 0 ? 2 : 3;
@@ -28,7 +30,6 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ 
   const int PL = 256 / U;                 // pixel lanes per block (host guarantees U <= 256)
   const int tid = threadIdx.x;
   const int u = tid % U, pl = tid / U;
-  const int n = blockIdx.y;
   const int p0 = blockIdx.x * ppb, p1 = min(HW, p0 + ppb);
   float s[K][8];
 #pragma unroll
@@ -99,6 +100,15 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ 
   }
 }
 
+template <typename T, int MODE, bool DET = false>
+__global__ __launch_bounds__(256) void chan_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b,
+                                                           const T* __restrict__ c, const T* __restrict__ d,
+                                                           float* __restrict__ sums, int HW, int C, int ppb, int relu,
+                                                           const float* __restrict__ sc1, const float* __restrict__ sf1,
+                                                           const float* __restrict__ sc2, const float* __restrict__ sf2) {
+  chan_reduce_body<T, MODE, DET>(a, b, c, d, sums, HW, C, ppb, relu, sc1, sf1, sc2, sf2, blockIdx.y);
+}
+
 // one wave per output statistic (channel for batch norm, (n,c) for instance norm); lanes stride over images
 __global__ __launch_bounds__(256) void norm_finalize_kernel(float* __restrict__ sums, int zero_sums, int64_t* nbt, int N, int HW, int C, int Creal, int instance,
                                      const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -153,12 +163,11 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(float* __restrict__ 
 // stride is a multiple of U whenever U divides 256), so every per-channel coefficient is loaded ONCE; with the
 // coefficient loads inside the loop these passes issued ~10 loads per 16 bytes of payload.
 template <typename T>
-__global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, const T* __restrict__ r,
-                                                          const float* __restrict__ scale2, const float* __restrict__ shift2,
-                                                          T* __restrict__ y, int HW, int C, size_t units, int s1_per_n, int relu) {
+__device__ __forceinline__ void affine_act_body(const T* __restrict__ x, const float* __restrict__ scale,
+                                                const float* __restrict__ shift, const T* __restrict__ r,
+                                                const float* __restrict__ scale2, const float* __restrict__ shift2,
+                                                T* __restrict__ y, int HW, int C, int s1_per_n, int relu, const int n) {
   const int U = C >> 3;
-  const int n = blockIdx.y;
   const size_t per_img = (size_t)HW * U, base = (size_t)n * per_img;
   const size_t stride = (size_t)gridDim.x * 256;
   const bool hoist = (256 % U) == 0;
@@ -193,6 +202,14 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x
     }
     U8<T>::store(y + i * 8, v);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, const T* __restrict__ r,
+                                                          const float* __restrict__ scale2, const float* __restrict__ shift2,
+                                                          T* __restrict__ y, int HW, int C, size_t units, int s1_per_n, int relu) {
+  affine_act_body<T>(x, scale, shift, r, scale2, shift2, y, HW, C, s1_per_n, relu, blockIdx.y);
 }
 
 // k1[c][3] for the batch branch, k2[n][c][3] for the instance branch; one wave per channel, lanes over images
@@ -241,15 +258,13 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_kernel(float* __restric
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y,
-                                                              const T* __restrict__ x, const T* __restrict__ r,
-                                                              const float* __restrict__ k1, const float* __restrict__ k2,
-                                                              T* __restrict__ dx, T* __restrict__ dr, int HW, int C,
-                                                              size_t units, int relu, const float* __restrict__ sc1,
-                                                              const float* __restrict__ sf1, const float* __restrict__ sc2,
-                                                              const float* __restrict__ sf2) {
-  const int U = C >> 3;
-  const int n = blockIdx.y;                       // grid = (blocks per image, N): see affine_act_kernel
+__device__ __forceinline__ void norm_bwd_apply_body(const T* __restrict__ dy, const T* __restrict__ y,
+                                                    const T* __restrict__ x, const T* __restrict__ r,
+                                                    const float* __restrict__ k1, const float* __restrict__ k2,
+                                                    T* __restrict__ dx, T* __restrict__ dr, int HW, int C, int relu,
+                                                    const float* __restrict__ sc1, const float* __restrict__ sf1,
+                                                    const float* __restrict__ sc2, const float* __restrict__ sf2, const int n) {
+  const int U = C >> 3;                           // grid = (blocks per image, N): see affine_act_kernel
   const size_t per_img = (size_t)HW * U, base = (size_t)n * per_img;
   const size_t stride = (size_t)gridDim.x * 256;
   const bool hoist = (256 % U) == 0;
@@ -316,6 +331,139 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict
       U8<T>::store(dr + i * 8, o);
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y,
+                                                              const T* __restrict__ x, const T* __restrict__ r,
+                                                              const float* __restrict__ k1, const float* __restrict__ k2,
+                                                              T* __restrict__ dx, T* __restrict__ dr, int HW, int C,
+                                                              size_t units, int relu, const float* __restrict__ sc1,
+                                                              const float* __restrict__ sf1, const float* __restrict__ sc2,
+                                                              const float* __restrict__ sf2) {
+  norm_bwd_apply_body<T>(dy, y, x, r, k1, k2, dx, dr, HW, C, relu, sc1, sf1, sc2, sf2, blockIdx.y);
+}
+
+// ---- BatchNorm over the live images of a padded batch (ast_*_len) ----------------------------------------------------------
+// The N = B * S images are the sections of B clips; image b * S + s is live iff s < clamp(n_sections[b], 1, S), n_sections an
+// int32 (B,) DEVICE array (the convention of ast_lengths.h: clamped here, never read on the host).  Grid = (blocks per image,
+// S, B), so a workgroup knows its clip and section without a division and decides with one compare: a dead image's workgroups
+// leave before any load (reductions) or store zeros without loading (apply passes).  Live images run the bodies above.
+struct LiveImage { int n; bool live; };
+__device__ __forceinline__ LiveImage live_image(const int32_t* __restrict__ n_sections, const int S) {
+  return {(int)(blockIdx.z * S + blockIdx.y), (int)blockIdx.y < ast_live_sections(n_sections[blockIdx.z], S)};
+}
+
+template <typename T>
+__device__ __forceinline__ void zero_image(T* __restrict__ y, const int HW, const int C, const int n) {
+  const size_t per_img = (size_t)HW * (C >> 3), base = (size_t)n * per_img;
+  const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < per_img; j += (size_t)gridDim.x * 256) U8<T>::store(y + (base + j) * 8, z);
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void chan_reduce_len_kernel(const T* __restrict__ a, const T* __restrict__ b, const T* __restrict__ c,
+                                                               float* __restrict__ sums, int HW, int C, int ppb, int relu,
+                                                               const float* __restrict__ sc1, const float* __restrict__ sf1,
+                                                               const int32_t* __restrict__ n_sections, int S) {
+  const LiveImage im = live_image(n_sections, S);
+  if (!im.live) return;                            // the whole workgroup: its table row is never read
+  chan_reduce_body<T, MODE, false>(a, b, c, (const T*)nullptr, sums, HW, C, ppb, relu, sc1, sf1, nullptr, nullptr, im.n);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void affine_act_len_kernel(const T* __restrict__ x, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, T* __restrict__ y, int HW, int C, int relu,
+                                                              const int32_t* __restrict__ n_sections, int S) {
+  const LiveImage im = live_image(n_sections, S);
+  if (!im.live) { zero_image<T>(y, HW, C, im.n); return; }
+  affine_act_body<T>(x, scale, shift, (const T*)nullptr, nullptr, nullptr, y, HW, C, 0, relu, im.n);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void norm_bwd_apply_len_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
+                                                                  const float* __restrict__ k1, T* __restrict__ dx, int HW, int C, int relu,
+                                                                  const float* __restrict__ sc1, const float* __restrict__ sf1,
+                                                                  const int32_t* __restrict__ n_sections, int S) {
+  const LiveImage im = live_image(n_sections, S);
+  if (!im.live) { zero_image<T>(dx, HW, C, im.n); return; }
+  norm_bwd_apply_body<T>(dy, y, x, (const T*)nullptr, k1, nullptr, dx, (T*)nullptr, HW, C, relu, sc1, sf1, nullptr, nullptr, im.n);
+}
+
+// What a finalize wave needs of the lengths: row n = b * S + s of the table counts iff s < n_b; the live images number sum_b n_b.
+// One division per table row (N of them per wave), none per pixel.
+__device__ __forceinline__ bool live_row(const int32_t* __restrict__ n_sections, const int S, const int n) {
+  const int b = n / S;
+  return n - b * S < ast_live_sections(n_sections[b], S);
+}
+__device__ __forceinline__ double live_pixels(const int32_t* __restrict__ n_sections, const int B, const int S, const int HW, const int lane) {
+  float live = 0.f;                                // at most B * S <= AST_LEN_MAX_IMAGES = 2^24 images (the host checks): exact in f32
+  for (int b = lane; b < B; b += 64) live += (float)ast_live_sections(n_sections[b], S);
+  return (double)wave_sum(live) * (double)HW;
+}
+
+// norm_finalize_kernel's BatchNorm branch over the live rows of sums[B * S][C][2]; every row is handed back zero (dead rows are
+// cleared without being read), the pixel count is HW * sum_b n_b.
+__global__ __launch_bounds__(256) void norm_finalize_len_kernel(float* __restrict__ sums, int64_t* nbt, int B, int S, int HW, int C, int Creal,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float* running_mean, float* running_var, float eps,
+                                                                 float* __restrict__ mean, float* __restrict__ rstd,
+                                                                 float* __restrict__ scale, float* __restrict__ shift,
+                                                                 const int32_t* __restrict__ n_sections) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;
+  const bool real_c = c < Creal;
+  const float gmm = real_c ? gamma[c] : 0.f, bt = real_c ? beta[c] : 0.f;
+  const bool upd = running_mean && real_c;
+  const float rm_old = upd ? running_mean[c] : 0.f, rv_old = upd ? running_var[c] : 1.f;
+  if (nbt && c == 0 && lane == 0) nbt[0] += 1;
+  const double cnt = live_pixels(n_sections, B, S, HW, lane);
+  float s0 = 0.f, s1 = 0.f;
+  for (int n = lane; n < B * S; n += 64) {
+    float* q = sums + ((size_t)n * C + c) * 2;
+    if (live_row(n_sections, S, n)) { s0 += q[0]; s1 += q[1]; }
+    q[0] = 0.f; q[1] = 0.f;
+  }
+  s0 = wave_sum(s0); s1 = wave_sum(s1);
+  if (lane != 0) return;
+  const double md = (double)s0 / cnt;
+  const double vd = fmax((double)s1 / cnt - md * md, 0.0);
+  const float m = (float)md, var = (float)vd;
+  if (upd) {
+    running_mean[c] = 0.9f * rm_old + 0.1f * m;
+    running_var[c] = 0.9f * rv_old + 0.1f * (float)(vd * cnt / fmax(cnt - 1.0, 1.0));
+  }
+  const float r = rsqrtf(var + eps);
+  mean[c] = m; rstd[c] = r;
+  scale[c] = gmm * r;
+  shift[c] = bt - m * gmm * r;
+}
+
+// norm_bwd_finalize_kernel's batch branch over the live rows of sums3[B * S][C][3]
+__global__ __launch_bounds__(256) void norm_bwd_finalize_len_kernel(float* __restrict__ sums3, int B, int S, int HW, int C, int Creal,
+                                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                                     const float* __restrict__ rstd, float* dgamma, float* dbeta,
+                                                                     float* __restrict__ k1, const int32_t* __restrict__ n_sections) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;
+  const double P = live_pixels(n_sections, B, S, HW, lane);
+  float s0 = 0.f, s1 = 0.f;
+  for (int n = lane; n < B * S; n += 64) {
+    float* q = sums3 + ((size_t)n * C + c) * 3;
+    if (live_row(n_sections, S, n)) { s0 += q[0]; s1 += q[1]; }
+    q[0] = 0.f; q[1] = 0.f; q[2] = 0.f;
+  }
+  const double S0 = wave_sum(s0), S1 = wave_sum(s1);
+  if (lane != 0) return;
+  if (c < Creal) {
+    const double g = gamma[c], m = mean[c], r = rstd[c];
+    const double Q = r * (S1 - m * S0);
+    if (dgamma) dgamma[c] += (float)Q;
+    if (dbeta) dbeta[c] += (float)S0;
+    k1[c * 3 + 0] = (float)(g * r);
+    k1[c * 3 + 1] = (float)(-g * r * r * Q / P);
+    k1[c * 3 + 2] = (float)(-g * r * S0 / P + g * r * r * m * Q / P);
+  } else { k1[c * 3] = k1[c * 3 + 1] = k1[c * 3 + 2] = 0.f; }
 }
 
 // ---- statistics finalize folded into the apply passes ---------------------------------------------------------------------
@@ -867,6 +1015,95 @@ extern "C" int ast_norm_bwd_apply(const void* dy, const void* y, const void* x, 
                                   const float* k2, void* dx, void* dr, int N, int HW, int C, int relu, int dtype,
                                   void* stream) {
   return ast_norm_bwd_apply_pre(dy, y, x, r, k1, k2, dx, dr, N, HW, C, relu, dtype, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// ---- BatchNorm over the live images of a padded batch (include/ast_hip.h) ---------------------------------------------------
+namespace {
+// what every _len entry checks of (B, S, HW, C, n_sections) before it launches; 0, or -1 with the message of entry `name` set
+int len_args_check(const char* name, int B, int S, int HW, int C, const void* n_sections) {
+  if (!n_sections) AST_FAIL("%s: n_sections is NULL (an int32 (B,) device array)", name);
+  if (B < 1 || B > 65535 || S < 1 || S > 65535 || (long)B * S > AST_LEN_MAX_IMAGES || HW < 1 || C < 8 || (C & 7) || C > 2048)
+    AST_FAIL("%s: bad args B=%d S=%d HW=%d C=%d (1 <= B, S <= 65535, B * S <= 2^24; C a multiple of 8, <= 2048)", name, B, S, HW, C);
+  return 0;
+}
+int reduce_len_blocks(int N, int HW, int C, int* ppb) {
+  const int PL = 256 / (C >> 3);
+  const int nblk = max(1, min((HW + PL - 1) / PL, max(1, reduce_blocks() / N)));
+  *ppb = (HW + nblk - 1) / nblk;
+  return (HW + *ppb - 1) / *ppb;
+}
+int elem_len_blocks(int N, int HW, int C) {
+  return std::max(1, std::min<int>((int)(((size_t)HW * (C >> 3) + 255) / 256), std::max(1, elem_blocks() / N)));
+}
+}  // namespace
+
+extern "C" int ast_chan_stats_len(const void* x, float* sums, int B, int S, int HW, int C, int dtype, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_chan_stats_len", B, S, HW, C, n_sections)) return -1;
+  if (!x || !sums) AST_FAIL("ast_chan_stats_len: null pointer");
+  int ppb;
+  const int gx = reduce_len_blocks(B * S, HW, C, &ppb);
+  const float* nf = nullptr;
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((chan_reduce_len_kernel<T, 0>), dim3(gx, S, B), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                                            (const T*)nullptr, (const T*)nullptr, sums, HW, C, ppb, 0, nf, nf, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_norm_finalize_len(float* sums, int64_t* num_batches_tracked, int B, int S, int HW, int C, int Creal, const float* gamma,
+                                     const float* beta, float* running_mean, float* running_var, float eps, float* mean, float* rstd,
+                                     float* scale, float* shift, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_norm_finalize_len", B, S, HW, C, n_sections)) return -1;
+  if (!sums || !gamma || !beta || !mean || !rstd || !scale || !shift || Creal < 0 || Creal > C || (!running_mean) != (!running_var))
+    AST_FAIL("ast_norm_finalize_len: null pointer, Creal %d outside [0, %d], or one running statistic without the other", Creal, C);
+  hipLaunchKernelGGL(norm_finalize_len_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, sums, num_batches_tracked, B, S, HW, C,
+                     Creal, gamma, beta, running_mean, running_var, eps, mean, rstd, scale, shift, n_sections);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_affine_act_len(const void* x, const float* scale, const float* shift, void* y, int B, int S, int HW, int C, int relu,
+                                  int dtype, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_affine_act_len", B, S, HW, C, n_sections)) return -1;
+  if (!x || !scale || !shift || !y) AST_FAIL("ast_affine_act_len: null pointer");
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((affine_act_len_kernel<T>), dim3(elem_len_blocks(B * S, HW, C), S, B), dim3(256), 0,
+                                            (hipStream_t)stream, (const T*)x, scale, shift, (T*)y, HW, C, relu & 1, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_norm_bwd_sums_len(const void* dy, const void* y, const void* x, float* sums3, int B, int S, int HW, int C, int relu,
+                                     int dtype, const float* scale1, const float* shift1, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_norm_bwd_sums_len", B, S, HW, C, n_sections)) return -1;
+  if (!dy || !x || !sums3 || (relu && !y && !scale1) || (!scale1) != (!shift1))
+    AST_FAIL("ast_norm_bwd_sums_len: null pointer (the ReLU mask needs y, or scale1 and shift1)");
+  int ppb;
+  const int gx = reduce_len_blocks(B * S, HW, C, &ppb);
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((chan_reduce_len_kernel<T, 1>), dim3(gx, S, B), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                                            (const T*)y, (const T*)x, sums3, HW, C, ppb, relu & 1, scale1, shift1, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_norm_bwd_finalize_len(float* sums3, int B, int S, int HW, int C, int Creal, const float* gamma, const float* mean,
+                                         const float* rstd, float* dgamma, float* dbeta, float* k1, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_norm_bwd_finalize_len", B, S, HW, C, n_sections)) return -1;
+  if (!sums3 || !gamma || !mean || !rstd || !k1 || Creal < 0 || Creal > C) AST_FAIL("ast_norm_bwd_finalize_len: null pointer or Creal %d outside [0, %d]", Creal, C);
+  hipLaunchKernelGGL(norm_bwd_finalize_len_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, sums3, B, S, HW, C, Creal, gamma, mean,
+                     rstd, dgamma, dbeta, k1, n_sections);
+  AST_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ast_norm_bwd_apply_len(const void* dy, const void* y, const void* x, const float* k1, void* dx, int B, int S, int HW, int C,
+                                      int relu, int dtype, const float* scale1, const float* shift1, const int32_t* n_sections, void* stream) {
+  if (len_args_check("ast_norm_bwd_apply_len", B, S, HW, C, n_sections)) return -1;
+  if (!dy || !x || !k1 || !dx || (relu && !y && !scale1) || (!scale1) != (!shift1))
+    AST_FAIL("ast_norm_bwd_apply_len: null pointer (the ReLU mask needs y, or scale1 and shift1)");
+  AST_DISPATCH_T(dtype, hipLaunchKernelGGL((norm_bwd_apply_len_kernel<T>), dim3(elem_len_blocks(B * S, HW, C), S, B), dim3(256), 0,
+                                            (hipStream_t)stream, (const T*)dy, (const T*)y, (const T*)x, k1, (T*)dx, HW, C, relu & 1,
+                                            scale1, shift1, n_sections, S));
+  AST_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int ast_bn_apply_fwd(const void* x, const void* r, void* y, const float* tab1, int rows1, long count1, const float* tab2,

@@ -817,6 +817,49 @@ int ast_bign_dgrad_len_det(const float* dy, const float* w, float* dx, int M, in
 int ast_linear_wgrad_len(const float* dy, const float* x, float* dW, float* db, int M, int N, int K, int lddy, int ldw, int S,
                          const int32_t* n_valid /* (M/S,) device, or NULL */, void* stream);
 
+/* ---- BatchNorm(+ReLU) over the live images of a padded batch: the CNN halves of new_decoder.py in ragged training -----------
+ * The N = B * S NHWC images are the sections of B clips, image n = b * S + s; n_sections is an int32 (B,) DEVICE array, clamped
+ * by the kernels to n_b = clamp(n_sections[b], 1, S) and never read on the host (one captured graph serves every mix of
+ * lengths).  Image n is LIVE iff s < n_b.  1 <= B, S <= 65535 and B * S <= 2^24 images.  These are the separate-pass chain above (ast_chan_stats -> ast_norm_finalize ->
+ * ast_affine_act; ast_norm_bwd_sums_pre -> ast_norm_bwd_finalize -> ast_norm_bwd_apply_pre) with batch statistics, backward sums
+ * and the pixel count HW * sum_b n_b (formed on the device) taken over the live images only.  The launch grid is (blocks per
+ * image, S, B), so liveness is one compare per workgroup; the pixel loops of live images are the bodies of the plain kernels.
+ *   ast_chan_stats_len        adds {sum x, sum x^2} into the rows of live images of sums[N][C][2] (zeroed by the caller: the
+ *                             shared scratch); workgroups of dead images leave before any load, and their rows are not read again.
+ *   ast_norm_finalize_len     one wave per channel over the live rows: mean, rstd, scale = gamma rstd, shift = beta - mean scale
+ *                             (padded channels c >= Creal: scale = shift = 0), running statistics (momentum 0.1, unbiased factor
+ *                             cnt / max(cnt - 1, 1); either both or neither), *num_batches_tracked += 1 when not NULL.  EVERY row of
+ *                             sums is left zero, dead ones without being read.
+ *   ast_affine_act_len        live images: ast_affine_act (relu bit 0).  Dead images: zeros stored, x not loaded.
+ *   ast_norm_bwd_sums_len     {sum dz, sum dz x} of the live images into sums3[N][C][3] (zeroed by the caller), dz = dy under the
+ *                             ReLU mask: from y, or recomputed from fma(x, scale1, shift1) when scale1 != NULL (y may be NULL then).
+ *   ast_norm_bwd_finalize_len dgamma[c] += Q, dbeta[c] += sum dz (either may be NULL), k1[C][3] the dx coefficients, all from
+ *                             the live sums and the device count; every row of sums3 is left zero.
+ *   ast_norm_bwd_apply_len    live images: ast_norm_bwd_apply_pre's dx = k1 (dz, x, 1).  Dead images: dx stored as exact 0, dy, y
+ *                             and x not loaded (NaN there reaches nothing).
+ * Atomic (default-mode) reductions only: no deterministic and no cross-rank form. */
+int ast_chan_stats_len(const void* x, float* sums, int B, int S, int HW, int C, int dtype, const int32_t* n_sections, void* stream);
+int ast_norm_finalize_len(float* sums, int64_t* num_batches_tracked, int B, int S, int HW, int C, int Creal, const float* gamma,
+                          const float* beta, float* running_mean, float* running_var, float eps, float* mean, float* rstd,
+                          float* scale, float* shift, const int32_t* n_sections, void* stream);
+int ast_affine_act_len(const void* x, const float* scale, const float* shift, void* y, int B, int S, int HW, int C, int relu,
+                       int dtype, const int32_t* n_sections, void* stream);
+int ast_norm_bwd_sums_len(const void* dy, const void* y, const void* x, float* sums3, int B, int S, int HW, int C, int relu, int dtype,
+                          const float* scale1, const float* shift1, const int32_t* n_sections, void* stream);
+int ast_norm_bwd_finalize_len(float* sums3, int B, int S, int HW, int C, int Creal, const float* gamma, const float* mean,
+                              const float* rstd, float* dgamma, float* dbeta, float* k1, const int32_t* n_sections, void* stream);
+int ast_norm_bwd_apply_len(const void* dy, const void* y, const void* x, const float* k1, void* dx, int B, int S, int HW, int C,
+                           int relu, int dtype, const float* scale1, const float* shift1, const int32_t* n_sections, void* stream);
+/* The two layout ops at the decoder's ends under the same mask: ast_nchw_to_nhwc / ast_bilinear_fwd / ast_bilinear_bwd on live
+ * images; a dead image's output (y, resp. dx) is exact 0 and its input is never read, so padded target sections and the
+ * gradient of padded output sections may hold anything, NaN included. */
+int ast_nchw_to_nhwc_len(const float* x, void* y, int B, int S, int C, int H, int W, int64_t sn, int64_t sc, int64_t sh, int Cp,
+                         int dtype, const int32_t* n_sections, void* stream);
+int ast_bilinear_fwd_len(const void* x, float* y, int B, int S, int C, int Cp, int H, int W, int Ho, int Wo, int dtype,
+                         const int32_t* n_sections, void* stream);
+int ast_bilinear_bwd_len(const float* dy, void* dx, int B, int S, int C, int Cp, int H, int W, int Ho, int Wo, int dtype,
+                         const int32_t* n_sections, void* stream);
+
 /* ---- token programs: transformer layers in one launch (csrc/tokprog.hip) ------------------------------------------------
  * Replaces, for the <= 64 token rows of the transformer stacks (style_encoder.py:181-191, content_encoder.py:24-26,
  * new_decoder.py:49-51,111-119), the per-operator launches above (ast_skinny_gemm*, ast_attn_fwd_p / ast_attn_bwd_p,
