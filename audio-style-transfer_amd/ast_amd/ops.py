@@ -543,6 +543,40 @@ class LinearFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+def _whole_clips(who, n, S, noun="rows"):
+    """Clips in the n rows (token rows of sections) or images of a padded batch of S sections each; ValueError unless a whole number."""
+    if S is None or S < 1 or n % S:
+        raise ValueError(f"{who}: {n} {noun} are not a whole number of clips of {'S = ' if noun == 'images' else ''}{S} sections")
+    return n // S
+
+
+def _bign_gemm_len(who, x, weight, bias, S, lengths, cap, device_lengths, inference_only=False):
+    """The forward of the length-masked huge-output linear (ast_bign_gemm_len) for big_out_linear and BigOutLinearLenFn: the checks
+    in their order (nothing is allocated before the last of them), then (x contiguous, y, lengths as the kernel read them).
+    cap: (most rows, what the refusal calls them, where the cap comes from)."""
+    if inference_only and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        raise RuntimeError(f"the length-masked output linear ({who}) is inference only: it has no backward; "
+                           "run it under torch.no_grad()")
+    rows, K = x.shape
+    N = weight.shape[0]
+    if rows > cap[0]:
+        raise RuntimeError(f"{who}: {rows} {cap[1]} > {cap[0]} ({cap[2]})")
+    lengths = len_tensor(lengths, _whole_clips(who, rows, S), "lengths", device=device_lengths, contiguous=True)
+    assert weight.shape[1] == K and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.is_contiguous()
+    x = x.contiguous()
+    y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+    check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
+          "ast_bign_gemm_len")
+    return x, y, lengths
+
+
+def _linear_wgrad_len(dy, x, gw, gb, N, S, lengths):
+    """dW (and db) of a linear on the rows of a padded batch into the gradients at gw / gb: rows of sections s >= lengths[b] are read
+    from neither dy nor x (ast_linear_wgrad_len)."""
+    rows, K = x.shape
+    check(lib().ast_linear_wgrad_len(ptr(dy), ptr(x), gw, gb, rows, N, K, N, K, S, ptr(lengths), stream()), "ast_linear_wgrad_len")
+
+
 class BigLinearFn(torch.autograd.Function):
     """nn.Linear with one HUGE dimension on <= 1024 token rows (above 64: the row-blocked ast_*_wide entries), straight on the f32 parameter (no packed copies: the
     weight is 301 MB) -- SimpleDecoder_TransformerOnly.py:16-17.  in_features huge: ast_bigk_gemm (the input is data,
@@ -564,9 +598,8 @@ class BigLinearFn(torch.autograd.Function):
         if lengths is not None:
             if not ctx.big_in:
                 raise ValueError("BigLinearFn: lengths belong to the huge-input linear; the huge-output one is BigOutLinearLenFn")
-            if S is None or S < 1 or rows % S:
-                raise ValueError(f"BigLinearFn: {rows} rows are not a whole number of clips of {S} sections")
-            ctx.mask = (int(S), len_tensor(lengths, rows // S, "lengths", device=True, contiguous=True))
+            lengths = len_tensor(lengths, _whole_clips("BigLinearFn", rows, S), "lengths", device=True, contiguous=True)
+            ctx.mask = (int(S), lengths)
         stem, tail = ("bigk_gemm", "_det" if config.deterministic else "") if ctx.big_in else ("skinny_gemm", "")
         _token_entry("BigLinearFn", stem, rows, tail)      # more than WIDE_MAX_ROWS rows raise before anything is allocated
         y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
@@ -590,8 +623,7 @@ class BigLinearFn(torch.autograd.Function):
         N = w.shape[0]
         gb = ptr(acc_grad(b)) if b is not None else None
         if ctx.mask is not None:
-            S, lengths = ctx.mask
-            check(lib().ast_linear_wgrad_len(ptr(dy), ptr(x), ptr(acc_grad(w)), gb, rows, N, K, N, K, S, ptr(lengths), stream()), "ast_linear_wgrad_len")
+            _linear_wgrad_len(dy, x, ptr(acc_grad(w)), gb, N, *ctx.mask)
         else:
             _token_call("BigLinearFn", "linear_wgrad", rows, "", ptr(dy), ptr(x), ptr(acc_grad(w)), gb, rows, N, K, N, K)
         dx = None
@@ -617,18 +649,8 @@ class BigOutLinearLenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, S, lengths):
-        rows, K = x.shape
-        N = weight.shape[0]
-        if rows > WIDE_MAX_ROWS:                    # before anything is allocated
-            raise RuntimeError(f"BigOutLinearLenFn: {rows} token rows > {WIDE_MAX_ROWS} (the cap of the wide token path, AST_WIDE_MAX_ROWS)")
-        if S < 1 or rows % S:
-            raise ValueError(f"BigOutLinearLenFn: {rows} rows are not a whole number of clips of {S} sections")
-        lengths = len_tensor(lengths, rows // S, "lengths", device=True, contiguous=True)
-        assert weight.shape[1] == K and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.is_contiguous()
-        x = x.contiguous()
-        y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
-        check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
-              "ast_bign_gemm_len")
+        x, y, lengths = _bign_gemm_len("BigOutLinearLenFn", x, weight, bias, S, lengths,
+                                       (WIDE_MAX_ROWS, "token rows", "the cap of the wide token path, AST_WIDE_MAX_ROWS"), device_lengths=True)
         ctx.save_for_backward(x)
         ctx.weight, ctx.bias, ctx.mask = weight, bias, (int(S), lengths)
         return y
@@ -642,8 +664,7 @@ class BigOutLinearLenFn(torch.autograd.Function):
         rows, K = x.shape
         N = w.shape[0]
         L = lib()
-        check(L.ast_linear_wgrad_len(ptr(dy), ptr(x), ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, rows, N, K, N, K, S,
-                                     ptr(lengths), stream()), "ast_linear_wgrad_len")
+        _linear_wgrad_len(dy, x, ptr(acc_grad(w)), ptr(acc_grad(b)) if b is not None else None, N, S, lengths)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -663,22 +684,8 @@ def big_out_linear(x, weight, bias, S, lengths=None):
     """nn.Linear with a huge out_features on the (B*S, K) f32 rows of a padded batch, at inference (ast_bign_gemm_len): up to
     BIGN_MAX_ROWS rows; lengths (int32 (B,) device tensor, clamped to [1, S] on the device) -- rows of sections s >= lengths[b]
     come back as exactly 0 and their inputs are never read.  No backward exists: an input that autograd would track raises."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
-        raise RuntimeError("the length-masked output linear (big_out_linear) is inference only: it has no backward; "
-                           "run it under torch.no_grad()")
-    x = x.contiguous()
-    rows, K = x.shape
-    N = weight.shape[0]
-    assert weight.shape[1] == K and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.is_contiguous()
-    if rows > BIGN_MAX_ROWS:
-        raise RuntimeError(f"big_out_linear: {rows} rows > {BIGN_MAX_ROWS} (AST_BIGN_MAX_ROWS)")
-    if S < 1 or rows % S:
-        raise ValueError(f"big_out_linear: {rows} rows are not a whole number of clips of {S} sections")
-    lengths = len_tensor(lengths, rows // S, "lengths", contiguous=True)
-    y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
-    check(lib().ast_bign_gemm_len(ptr(x), ptr(weight), ptr(bias), ptr(y), rows, N, K, K, N, int(S), ptr(lengths), stream()),
-          "ast_bign_gemm_len")
-    return y
+    return _bign_gemm_len("big_out_linear", x, weight, bias, S, lengths, (BIGN_MAX_ROWS, "rows", "AST_BIGN_MAX_ROWS"), device_lengths=False,
+                          inference_only=True)[1]
 
 
 class FFNFn(torch.autograd.Function):
@@ -695,10 +702,7 @@ class FFNFn(torch.autograd.Function):
         y = torch.empty((rows, pw2.Cop), dtype=x.dtype, device=x.device)
         mask, seed, ctr = None, 0, None
         if p > 0.0:
-            if _DropState.counter is None or _DropState.counter.device != x.device:
-                _DropState.counter = torch.zeros(1, dtype=torch.int64, device=x.device)
-            _DropState.calls += 1
-            seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
+            seed, ctr = _DropState.draw(x.device)
             mask = torch.empty_like(h)
         _token_call("FFNFn", "skinny_gemm", rows, "_ex", ptr(x), pw1.weight.data_ptr() + 4 * pw1.w_off, pw1.bias.data_ptr() + 4 * pw1.b_off, ptr(h),
                                                  rows, pw1.Co, pw1.Ci, pw1.s_co, pw1.Cop, 1, None, ptr(mask), float(p), seed, ptr(ctr))
@@ -946,12 +950,10 @@ class BatchNormActFn(torch.autograd.Function):
 
 def _check_image_lengths(who, N, n_sections, S):
     """(B, n_sections) for the N = B * S images of a padded batch; n_sections an int32 (B,) device tensor (len_tensor)."""
-    S = int(S)
-    if S < 1 or N % S:
-        raise ValueError(f"{who}: {N} images are not a whole number of clips of S = {S} sections")
+    B = _whole_clips(who, N, int(S), "images")
     if n_sections is None:
-        raise ValueError(f"{who}: n_sections must be an int32 device tensor of shape ({N // S},), got None")
-    return N // S, len_tensor(n_sections, N // S, "n_sections", device=True, contiguous=True)
+        raise ValueError(f"{who}: n_sections must be an int32 device tensor of shape ({B},), got None")
+    return B, len_tensor(n_sections, B, "n_sections", device=True, contiguous=True)
 
 
 def check_bn_len_supported(who):
@@ -1143,12 +1145,7 @@ class AddDropLNFn(torch.autograd.Function):
         rows = sub2.shape[0]
         s = torch.empty_like(sub2)
         mask = torch.empty_like(sub2) if p > 0.0 else None
-        seed = 0
-        if p > 0.0:
-            if _DropState.counter is None or _DropState.counter.device != sub.device:
-                _DropState.counter = torch.zeros(1, dtype=torch.int64, device=sub.device)
-            _DropState.calls += 1
-            seed = _DropState.seed + 7919 * _DropState.calls
+        seed, ctr = _DropState.draw(sub.device) if p > 0.0 else (0, None)
         y = mean = rstd = None
         if ln is not None:
             y = torch.empty_like(sub2)
@@ -1156,8 +1153,8 @@ class AddDropLNFn(torch.autograd.Function):
             rstd = torch.empty_like(mean)
         check(lib().ast_add_drop_ln_fwd(ptr(x2), ptr(sub2), ptr(mask), ptr(s), ptr(ln.weight) if ln is not None else None,
                                         ptr(ln.bias) if ln is not None else None, ptr(y), ptr(mean), ptr(rstd), rows, D,
-                                        float(ln.eps) if ln is not None else 0.0, float(p), seed,
-                                        ptr(_DropState.counter) if p > 0.0 else None, stream()), "ast_add_drop_ln_fwd")
+                                        float(ln.eps) if ln is not None else 0.0, float(p), seed, ptr(ctr),
+                                        stream()), "ast_add_drop_ln_fwd")
         ctx.save_for_backward(s, mean, rstd, mask)
         ctx.ln, ctx.shape, ctx.has_x = ln, shape, x is not None
         if ln is None:
@@ -1427,6 +1424,46 @@ class CastFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # attention core + dropout
 # ---------------------------------------------------------------------------
+def _attn_out(q, B, H, Lq, Lk, d):
+    """(o, probs) of the attention core, uninitialised."""
+    return (torch.empty((B * Lq, d), dtype=torch.float32, device=q.device),
+            torch.empty((B, H, Lq, Lk), dtype=torch.float32, device=q.device))
+
+
+def _attn_train_fwd(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop, key_len=None, key_period=0):
+    """The forward that has a backward, of AttnCoreFn (key_len None: ast_attn_fwd_p) and MaskedAttnFn (ast_attn_fwd_len_p, which takes
+    the two mask arguments after `causal`)."""
+    d = H * dh
+    o, probs = _attn_out(q, B, H, Lq, Lk, d)
+    seed, ctr = _DropState.draw(q.device) if p_drop > 0.0 else (0, None)
+    entry, what, mask = ("ast_attn_fwd_p", "ast_attn_fwd", ()) if key_len is None else \
+        ("ast_attn_fwd_len_p", "ast_attn_fwd_len_p", (ptr(key_len), int(key_period)))
+    check(getattr(lib(), entry)(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
+                                B, H, Lq, Lk, dh, q.stride(0), kv.stride(0), d, int(causal), *mask, None, float(p_drop), seed, ptr(ctr),
+                                stream()), what)
+    ctx.save_for_backward(q, kv, probs, key_len)
+    ctx.dims = (B, H, Lq, Lk, dh, k_off, v_off, int(key_period))
+    ctx.drop = (float(p_drop), seed, ctr)
+    ctx.same = q.data_ptr() == kv.data_ptr()
+    return o
+
+
+def _attn_train_bwd(ctx, do):
+    """AttnCoreFn.backward and MaskedAttnFn.backward (this one function): ast_attn_bwd_p, or with a saved key_len ast_attn_bwd_len_p."""
+    q, kv, probs, key_len = ctx.saved_tensors
+    B, H, Lq, Lk, dh, k_off, v_off, key_period = ctx.dims
+    p_drop, seed, ctr = ctx.drop
+    do = do.contiguous()
+    dq = torch.empty_like(q)                    # the kernel writes every q / k / v column of every row, masked keys as 0
+    dkv = dq if ctx.same else torch.empty_like(kv)
+    entry, what, mask = ("ast_attn_bwd_p", "ast_attn_bwd", ()) if key_len is None else \
+        ("ast_attn_bwd_len_p", "ast_attn_bwd_len_p", (ptr(key_len), key_period))
+    check(getattr(lib(), entry)(ptr(do), q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(probs),
+                                dq.data_ptr(), dkv.data_ptr() + 4 * k_off, dkv.data_ptr() + 4 * v_off, B, H, Lq, Lk, dh,
+                                q.stride(0), kv.stride(0), H * dh, *mask, None, p_drop, seed, ptr(ctr), stream()), what)
+    return (dq, None if ctx.same else dkv) + (None,) * 11
+
+
 class AttnCoreFn(torch.autograd.Function):
     """softmax(QK^T/sqrt(dh) + causal) V for up to ATTN_MAX_L query and key tokens (one wave per (batch, head) up to 16 x 16,
     tiles of 16 queries x 16 keys on f32 MFMA past that; no float atomics either way).  q:(B*Lq, ldq) k,v views of (B*Lk, ldk).
@@ -1437,46 +1474,20 @@ class AttnCoreFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop, key_len=None, key_period=0):
+        if key_len is None:
+            return _attn_train_fwd(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop)
         d = H * dh
-        o = torch.empty((B * Lq, d), dtype=torch.float32, device=q.device)
-        probs = torch.empty((B, H, Lq, Lk), dtype=torch.float32, device=q.device)
-        ldq, ldk = q.stride(0), kv.stride(0)
-        if key_len is not None:
-            if p_drop > 0.0:
-                raise RuntimeError("the key-masked attention core (key_len) has no dropout: p_drop must be 0")
-            key_len = len_tensor(key_len, B, "key_len", contiguous=True)
-            check(lib().ast_attn_fwd_len(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
-                                         B, H, Lq, Lk, dh, ldq, ldk, d, int(causal), ptr(key_len), int(key_period), stream()),
-                  "ast_attn_fwd_len")
-            ctx.mark_non_differentiable(o)
-            return o
-        seed, ctr = 0, None
+        o, probs = _attn_out(q, B, H, Lq, Lk, d)
         if p_drop > 0.0:
-            if _DropState.counter is None or _DropState.counter.device != q.device:
-                _DropState.counter = torch.zeros(1, dtype=torch.int64, device=q.device)
-            _DropState.calls += 1
-            seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
-        check(lib().ast_attn_fwd_p(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
-                                   B, H, Lq, Lk, dh, ldq, ldk, d, int(causal), None, float(p_drop), seed, ptr(ctr), stream()), "ast_attn_fwd")
-        ctx.save_for_backward(q, kv, probs)
-        ctx.dims = (B, H, Lq, Lk, dh, k_off, v_off)
-        ctx.drop = (float(p_drop), seed, ctr)
-        ctx.same = q.data_ptr() == kv.data_ptr()
+            raise RuntimeError("the key-masked attention core (key_len) has no dropout: p_drop must be 0")
+        key_len = len_tensor(key_len, B, "key_len", contiguous=True)
+        check(lib().ast_attn_fwd_len(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
+                                     B, H, Lq, Lk, dh, q.stride(0), kv.stride(0), d, int(causal), ptr(key_len), int(key_period), stream()),
+              "ast_attn_fwd_len")
+        ctx.mark_non_differentiable(o)
         return o
 
-    @staticmethod
-    def backward(ctx, do):
-        q, kv, probs = ctx.saved_tensors
-        B, H, Lq, Lk, dh, k_off, v_off = ctx.dims
-        p_drop, seed, ctr = ctx.drop
-        do = do.contiguous()
-        d = H * dh
-        dq = torch.empty_like(q)                    # the kernel writes every q / k / v column of every row
-        dkv = dq if ctx.same else torch.empty_like(kv)
-        check(lib().ast_attn_bwd_p(ptr(do), q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(probs),
-                                   dq.data_ptr(), dkv.data_ptr() + 4 * k_off, dkv.data_ptr() + 4 * v_off, B, H, Lq, Lk, dh,
-                                   q.stride(0), kv.stride(0), d, None, p_drop, seed, ptr(ctr), stream()), "ast_attn_bwd")
-        return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None, None, None
+    backward = staticmethod(_attn_train_bwd)
 
 
 class MaskedAttnFn(torch.autograd.Function):
@@ -1490,37 +1501,9 @@ class MaskedAttnFn(torch.autograd.Function):
         if key_len is None:
             raise ValueError("MaskedAttnFn needs key_len (the unmasked core is AttnCoreFn)")
         key_len = len_tensor(key_len, B, "key_len", device=True, contiguous=True)
-        d = H * dh
-        o = torch.empty((B * Lq, d), dtype=torch.float32, device=q.device)
-        probs = torch.empty((B, H, Lq, Lk), dtype=torch.float32, device=q.device)
-        seed, ctr = 0, None
-        if p_drop > 0.0:
-            if _DropState.counter is None or _DropState.counter.device != q.device:
-                _DropState.counter = torch.zeros(1, dtype=torch.int64, device=q.device)
-            _DropState.calls += 1
-            seed, ctr = _DropState.seed + 7919 * _DropState.calls, _DropState.counter
-        check(lib().ast_attn_fwd_len_p(q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(o), ptr(probs),
-                                       B, H, Lq, Lk, dh, q.stride(0), kv.stride(0), d, int(causal), ptr(key_len), int(key_period),
-                                       None, float(p_drop), seed, ptr(ctr), stream()), "ast_attn_fwd_len_p")
-        ctx.save_for_backward(q, kv, probs, key_len)
-        ctx.dims = (B, H, Lq, Lk, dh, k_off, v_off, int(key_period))
-        ctx.drop = (float(p_drop), seed, ctr)
-        ctx.same = q.data_ptr() == kv.data_ptr()
-        return o
+        return _attn_train_fwd(ctx, q, kv, B, H, Lq, Lk, dh, k_off, v_off, causal, p_drop, key_len, key_period)
 
-    @staticmethod
-    def backward(ctx, do):
-        q, kv, probs, key_len = ctx.saved_tensors
-        B, H, Lq, Lk, dh, k_off, v_off, key_period = ctx.dims
-        p_drop, seed, ctr = ctx.drop
-        do = do.contiguous()
-        dq = torch.empty_like(q)                    # the kernel writes every q / k / v column of every row, masked keys as 0
-        dkv = dq if ctx.same else torch.empty_like(kv)
-        check(lib().ast_attn_bwd_len_p(ptr(do), q.data_ptr(), kv.data_ptr() + 4 * k_off, kv.data_ptr() + 4 * v_off, ptr(probs),
-                                       dq.data_ptr(), dkv.data_ptr() + 4 * k_off, dkv.data_ptr() + 4 * v_off, B, H, Lq, Lk, dh,
-                                       q.stride(0), kv.stride(0), H * dh, ptr(key_len), key_period, None, p_drop, seed, ptr(ctr),
-                                       stream()), "ast_attn_bwd_len_p")
-        return dq, (None if ctx.same else dkv), None, None, None, None, None, None, None, None, None, None, None
+    backward = staticmethod(_attn_train_bwd)
 
 
 def require_inference(*tensors):
@@ -1532,18 +1515,31 @@ def require_inference(*tensors):
 
 
 class _DropState:
+    """The process's dropout stream.  Every site that draws takes its (seed, counter) from draw(), once per forward and only when
+    its p > 0: deterministic mode, bit-exact resume and one-graph capture rest on the sites consuming `calls` in the same order."""
     seed = 0x5EED
     counter = None   # device int64, bumped once per training step by the trainer (hipGraph-replay safe)
     calls = 0
 
+    @classmethod
+    def counter_on(cls, device):
+        """The counter, created on first use and anew when the device changes.  Consumes no call."""
+        if cls.counter is None or cls.counter.device != device:
+            cls.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        return cls.counter
+
+    @classmethod
+    def draw(cls, device):
+        """(seed, counter) for one dropout site: consumes one call."""
+        ctr = cls.counter_on(device)
+        cls.calls += 1
+        return cls.seed + 7919 * cls.calls, ctr
+
 
 def dropout_mask(shape, p, device):
-    if _DropState.counter is None or _DropState.counter.device != device:
-        _DropState.counter = torch.zeros(1, dtype=torch.int64, device=device)
-    _DropState.calls += 1
+    seed, ctr = _DropState.draw(device)
     m = torch.empty(shape, dtype=torch.float32, device=device)
-    check(lib().ast_dropout_mask(ptr(m), m.numel(), p, _DropState.seed + 7919 * _DropState.calls, ptr(_DropState.counter),
-                                 stream()), "ast_dropout_mask")
+    check(lib().ast_dropout_mask(ptr(m), m.numel(), p, seed, ptr(ctr), stream()), "ast_dropout_mask")
     return m
 
 
@@ -1571,12 +1567,9 @@ class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
         x = x.contiguous()
-        if _DropState.counter is None or _DropState.counter.device != x.device:
-            _DropState.counter = torch.zeros(1, dtype=torch.int64, device=x.device)
-        _DropState.calls += 1
+        seed, ctr = _DropState.draw(x.device)
         y, mask = torch.empty_like(x), torch.empty_like(x)
-        check(lib().ast_dropout_fwd(ptr(x), ptr(y), ptr(mask), x.numel(), p, _DropState.seed + 7919 * _DropState.calls,
-                                    ptr(_DropState.counter), stream()), "ast_dropout_fwd")
+        check(lib().ast_dropout_fwd(ptr(x), ptr(y), ptr(mask), x.numel(), p, seed, ptr(ctr), stream()), "ast_dropout_fwd")
         ctx.save_for_backward(mask)
         return y
 
@@ -1606,6 +1599,33 @@ def _scaled(grad_saved, gout):
     return y
 
 
+def _scaled_grads(ctx, g, *_):
+    """The backward of every Function below whose forward computed the gradients with the loss and saved them: each of them times
+    the upstream gradient g of the scalar (one ast_scale per differentiable input, in input order), and None for the ctx.n_rest
+    inputs after those."""
+    return tuple(_scaled(d, g) for d in ctx.saved_tensors) + (None,) * ctx.n_rest
+
+
+def _scalar_loss(name, entry, n_diff, n_ptr=0, ws_floats=None):
+    """The Function of a scalar loss that one library entry computes together with its gradients:
+    entry(x_1 .. x_n_diff, the next n_ptr inputs as pointers, R, D, the remaining inputs as they are, loss[1], dx_1 .. dx_n_diff,
+    then ws[ws_floats(R, D)] if it has a workspace, stream), (R, D) the shape of x_1.  apply() takes the inputs in that order."""
+
+    def forward(ctx, *inputs):
+        xs = [x.contiguous() for x in inputs[:n_diff]]
+        R, D = xs[0].shape
+        loss = torch.empty(1, dtype=torch.float32, device=xs[0].device)
+        grads = [torch.empty_like(x) for x in xs]
+        ws = () if ws_floats is None else (torch.empty(ws_floats(R, D), dtype=torch.float32, device=xs[0].device),)
+        check(getattr(lib(), entry)(*map(ptr, xs), *map(ptr, inputs[n_diff:n_diff + n_ptr]), R, D, *inputs[n_diff + n_ptr:], ptr(loss),
+                                    *map(ptr, grads), *map(ptr, ws), stream()), entry)
+        ctx.save_for_backward(*grads)
+        ctx.n_rest = len(inputs) - n_diff
+        return loss[0]
+
+    return type(name, (torch.autograd.Function,), {"forward": staticmethod(forward), "backward": staticmethod(_scaled_grads)})
+
+
 class WeightedSumFn(torch.autograd.Function):
     """total = sum_i weights[widx_i] * term_i for scalar loss terms, the weights read from DEVICE memory at run time
     (ast_weighted_sum): one launch forward, one backward, and a captured hipGraph follows a ramped loss weight without being
@@ -1613,23 +1633,21 @@ class WeightedSumFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weights, widx, *terms):
-        import ctypes as C
         n = len(terms)
         ts = [t.detach().reshape(1) for t in terms]
         assert all(t.dtype == torch.float32 and t.is_cuda for t in ts) and len(widx) == n
         out = torch.empty(1, dtype=torch.float32, device=weights.device)
-        parr = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-        iarr = (C.c_int32 * n)(*[int(i) for i in widx])
+        parr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        iarr = (ctypes.c_int32 * n)(*[int(i) for i in widx])
         check(lib().ast_weighted_sum(parr, iarr, n, ptr(weights), ptr(out), stream()), "ast_weighted_sum")
         ctx.weights, ctx.widx, ctx.shapes = weights, tuple(int(i) for i in widx), [t.shape for t in terms]
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         n = len(ctx.widx)
         grads = torch.empty(n, dtype=torch.float32, device=g.device)
-        iarr = (C.c_int32 * n)(*ctx.widx)
+        iarr = (ctypes.c_int32 * n)(*ctx.widx)
         check(lib().ast_weighted_sum_bwd(ptr(g.contiguous().reshape(1)), iarr, n, ptr(ctx.weights), ptr(grads), stream()), "ast_weighted_sum_bwd")
         return (None, None) + tuple(grads[i].view(shp) for i, shp in enumerate(ctx.shapes))
 
@@ -1645,7 +1663,6 @@ class ReconTotalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out, tgt, coefs, inv):
-        import ctypes as C
         B, S, Cc, T, Fq = out.shape
         assert Cc == 2 and out.is_contiguous() and out.dtype == torch.float32
         assert tgt.shape == out.shape and tgt.dtype == torch.float32 and tgt.stride(4) == 1
@@ -1654,7 +1671,7 @@ class ReconTotalFn(torch.autograd.Function):
             "target must be a [..., :F] slice of a contiguous tensor"
         res = torch.empty(11, dtype=torch.float32, device=out.device)
         grad = torch.empty_like(out)
-        c5, i5 = (C.c_float * 5)(*[float(c) for c in coefs]), (C.c_float * 5)(*[float(c) for c in inv])
+        c5, i5 = (ctypes.c_float * 5)(*[float(c) for c in coefs]), (ctypes.c_float * 5)(*[float(c) for c in inv])
         if config.deterministic:                   # one slot of partial sums per 256-bin workgroup, reduced in slot order
             n = 5 * ((B * T * Fq + 255) // 256)
             check(lib().ast_recon_loss_total_det(ptr(out), ptr(tgt), ld, B, S, T, Fq, c5, i5, ptr(det_ws(n, out.device)), n, ptr(res),
@@ -1664,14 +1681,12 @@ class ReconTotalFn(torch.autograd.Function):
             check(lib().ast_recon_loss_total(ptr(out), ptr(tgt), ld, B, S, T, Fq, c5, i5, ptr(ws), ptr(res), ptr(grad), stream()),
                   "ast_recon_loss_total")
         ctx.save_for_backward(grad)
+        ctx.n_rest = 3
         total, sums, parts = res[5], res[:5], res[6:]
         ctx.mark_non_differentiable(sums, parts)
         return total, sums, parts
 
-    @staticmethod
-    def backward(ctx, gtotal, gsums, gparts):
-        (grad,) = ctx.saved_tensors
-        return _scaled(grad, gtotal), None, None, None
+    backward = staticmethod(_scaled_grads)
 
 
 class ReconLenGradFn(torch.autograd.Function):
@@ -1683,127 +1698,27 @@ class ReconLenGradFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out, tgt, ld, n_sections, clip_weights, weights):
-        import ctypes as C
         B, S, _, T, Fq = out.shape
         need = int(lib().ast_recon_loss_len_grad_ws_floats(B, S, T, Fq))
         ws = torch.empty(need, dtype=torch.float32, device=out.device)
         res = torch.empty((B, 11), dtype=torch.float32, device=out.device)
         loss = torch.empty(1, dtype=torch.float32, device=out.device)
         grad = torch.empty_like(out)
-        c5 = (C.c_float * 5)(*[float(c) for c in weights])
+        c5 = (ctypes.c_float * 5)(*[float(c) for c in weights])
         check(lib().ast_recon_loss_len_grad(ptr(out), ptr(tgt), ld, B, S, T, Fq, ptr(n_sections), ptr(clip_weights), c5, ptr(ws), need,
                                             ptr(res), ptr(loss), ptr(grad), stream()), "ast_recon_loss_len_grad")
         ctx.save_for_backward(grad)
+        ctx.n_rest = 5
         ctx.mark_non_differentiable(res)
         return loss[0], res
 
-    @staticmethod
-    def backward(ctx, gloss, gres):
-        (grad,) = ctx.saved_tensors
-        return _scaled(grad, gloss), None, None, None, None, None
+    backward = staticmethod(_scaled_grads)
 
 
-class InfoNCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, emb, labels32, temperature):
-        emb = emb.contiguous()
-        B, D = emb.shape
-        loss = torch.empty(1, dtype=torch.float32, device=emb.device)
-        demb = torch.empty_like(emb)
-        ws = torch.empty(2 * B * B + B, dtype=torch.float32, device=emb.device)
-        check(lib().ast_infonce(ptr(emb), ptr(labels32), B, D, temperature, ptr(loss), ptr(demb), ptr(ws), stream()),
-              "ast_infonce")
-        ctx.save_for_backward(demb)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (demb,) = ctx.saved_tensors
-        return _scaled(demb, g), None, None
-
-
-class MarginFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cls, margin):
-        cls = cls.contiguous()
-        Cn, D = cls.shape
-        loss = torch.empty(1, dtype=torch.float32, device=cls.device)
-        dcls = torch.empty_like(cls)
-        check(lib().ast_margin(ptr(cls), Cn, D, margin, ptr(loss), ptr(dcls), stream()), "ast_margin")
-        ctx.save_for_backward(dcls)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        return _scaled(d, g), None
-
-
-class HSICFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, s, c):
-        s, c = s.contiguous(), c.contiguous()
-        B, D = s.shape
-        loss = torch.empty(1, dtype=torch.float32, device=s.device)
-        ds, dc = torch.empty_like(s), torch.empty_like(c)
-        ws = torch.empty(6 * B * B + 2 * B + 8, dtype=torch.float32, device=s.device)
-        check(lib().ast_hsic(ptr(s), ptr(c), B, D, ptr(loss), ptr(ds), ptr(dc), ptr(ws), stream()), "ast_hsic")
-        ctx.save_for_backward(ds, dc)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        ds, dc = ctx.saved_tensors
-        return _scaled(ds, g), _scaled(dc, g)
-
-
-class CrossCovFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, s, c):
-        s, c = s.contiguous(), c.contiguous()
-        B, D = s.shape
-        loss = torch.empty(1, dtype=torch.float32, device=s.device)
-        ds, dc = torch.empty_like(s), torch.empty_like(c)
-        ws = torch.empty(2 * D + 2 * B * B, dtype=torch.float32, device=s.device)
-        check(lib().ast_crosscov(ptr(s), ptr(c), B, D, ptr(loss), ptr(ds), ptr(dc), ptr(ws), stream()), "ast_crosscov")
-        ctx.save_for_backward(ds, dc)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        ds, dc = ctx.saved_tensors
-        return _scaled(ds, g), _scaled(dc, g)
-
-
-class CrossEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target32):
-        logits = logits.contiguous()
-        R, Cn = logits.shape
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        dl = torch.empty_like(logits)
-        check(lib().ast_cross_entropy(ptr(logits), ptr(target32), R, Cn, ptr(loss), ptr(dl), stream()), "ast_cross_entropy")
-        ctx.save_for_backward(dl)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        return _scaled(dl, g), None
-
-
-class SoftmaxEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits):
-        logits = logits.contiguous()
-        R, Cn = logits.shape
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        dl = torch.empty_like(logits)
-        check(lib().ast_softmax_entropy(ptr(logits), R, Cn, ptr(loss), ptr(dl), stream()), "ast_softmax_entropy")
-        ctx.save_for_backward(dl)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        return _scaled(dl, g)
+# apply(emb, labels32, temperature), (cls, margin), (s, c), (s, c), (logits, target32), (logits)
+InfoNCEFn = _scalar_loss("InfoNCEFn", "ast_infonce", 1, n_ptr=1, ws_floats=lambda B, D: 2 * B * B + B)
+MarginFn = _scalar_loss("MarginFn", "ast_margin", 1)
+HSICFn = _scalar_loss("HSICFn", "ast_hsic", 2, ws_floats=lambda B, D: 6 * B * B + 2 * B + 8)
+CrossCovFn = _scalar_loss("CrossCovFn", "ast_crosscov", 2, ws_floats=lambda B, D: 2 * D + 2 * B * B)
+CrossEntropyFn = _scalar_loss("CrossEntropyFn", "ast_cross_entropy", 1, n_ptr=1)
+SoftmaxEntropyFn = _scalar_loss("SoftmaxEntropyFn", "ast_softmax_entropy", 1)

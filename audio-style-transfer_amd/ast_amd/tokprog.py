@@ -58,9 +58,8 @@ def gemm(x, w, bias, y, M, N, K, ldx, ldw, ldy, relu=False, mul_mask=None, adden
     return _op(GEMM, flags | (RELU if relu else 0), (M, N, K, ldx, ldw, ldy), (x, w, bias, mul_mask, addend), (y, drop_mask), p=p, seed=seed)
 
 
-def _next_seed():
-    ops._DropState.calls += 1
-    return ops._DropState.seed + 7919 * ops._DropState.calls
+def _next_seed(device):
+    return ops._DropState.draw(device)[0]
 
 
 _sync = {}
@@ -93,9 +92,7 @@ def run(oplist, device, xcd, chunk_ends=None, persistent=None):
     from . import config
     if persistent is None:
         persistent = config.tok_programs == 2
-    ctr = ops._DropState.counter
-    if ctr is None or ctr.device != device:
-        ctr = ops._DropState.counter = torch.zeros(1, dtype=torch.int64, device=device)
+    ctr = ops._DropState.counter_on(device)
     if not persistent:
         cap = lib().ast_tok_max_ops()
         for start in range(0, len(oplist), cap):
@@ -197,7 +194,7 @@ class EncoderStackFn(torch.autograd.Function):
             a, l = lyr.attn, lyr.l
             dh = d // a.h
             p_attn, p1, pf, p2 = s["p"]
-            sd = [_next_seed() if pp > 0 else 0 for pp in (p_attn, p1, pf, p2)]
+            sd = [_next_seed(dev) if pp > 0 else 0 for pp in (p_attn, p1, pf, p2)]
             seeds.append(sd)
             qkv, o, aa, x1, h, f, y = v[s["qkv"]], v[s["o"]], v[s["a"]], v[s["x1"]], v[s["h"]], v[s["f"]], v[s["y"]]
             W = lambda pw: pw.weight.data_ptr() + 4 * pw.w_off
@@ -334,7 +331,7 @@ class DecoderStackFn(torch.autograd.Function):
         for lyr, s in zip(layers, slots):
             l, sa, ca = lyr.l, lyr.sa, lyr.ca
             ps = s["p"]
-            sd = [_next_seed() if pp > 0 else 0 for pp in ps]
+            sd = [_next_seed(dev) if pp > 0 else 0 for pp in ps]
             seeds.append(sd)
             V = lambda k: v[s[k]] if s[k] is not None else None
             st0, st1, st2 = V("st0"), V("st1"), V("st2")

@@ -262,9 +262,7 @@ class Trainer:
         else:
             self.G.zero_grad()
             self.D.zero_grad()
-        if ops._DropState.counter is None or ops._DropState.counter.device != self.device:
-            ops._DropState.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-        check(lib().ast_counter_incr(ptr(ops._DropState.counter), stream()), "ast_counter_incr")
+        check(lib().ast_counter_incr(ptr(ops._DropState.counter_on(self.device)), stream()), "ast_counter_incr")
         y = x[..., :513]
         with ops.shared_nhwc(x, config.compute_dtype):      # one input conversion for both encoders, inside this step
             style_emb, class_emb, content_emb, y_emb = self._encoders(x, y, labels_host)
@@ -1005,8 +1003,7 @@ class Trainer:
     def _capture(self, key, x, labels_host, segmented=False):
         """Warm-up (allocations, weight banks, constants) + capture.  Warm-up steps are real steps, so every
         piece of mutable training state is snapshotted first and restored afterwards: capturing is side-effect free."""
-        if ops._DropState.counter is None or ops._DropState.counter.device != self.device:
-            ops._DropState.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ops._DropState.counter_on(self.device)
         state = self._mutable_state()
         saved = [t.clone() for t in state]
         static_x = x.clone()
@@ -1018,7 +1015,7 @@ class Trainer:
                 self._step_body(static_x, labels_host)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        # The dropout seeds baked below are seed + 7919 * (_drop_calls + 1, + 2, ...).  A Trainer's first capture takes the value the
+        # The dropout seeds baked below are those of calls _drop_calls + 1, + 2, ... (ops._DropState.draw).  A Trainer's first capture takes the value the
         # two warm-up steps leave behind (what the first capture of a fresh process has always baked); every later capture, and one
         # made after load_state, starts from the same value again.
         if self._drop_calls is None:
