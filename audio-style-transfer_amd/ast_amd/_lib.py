@@ -119,6 +119,7 @@ _SIGS = {
     "ast_wgrad_rep": ([vp, vp, vp, C.POINTER(Gather), i32, i32, vp], i32),
     "ast_wgrad_slab": ([vp, vp, vp, C.POINTER(Gather), i32, i32, C.POINTER(i32), vp], i32),
     "ast_slab_sum": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), i32, vp], i32),
+    "ast_wgrad_plan": ([C.POINTER(Gather), i32, i32, C.POINTER(i32 * 6)], i32),
     # deterministic forms (include/ast_hip.h)
     "ast_ordered_sum": ([vp, i64, i32, i32, vp, i32, vp], i32),
     "ast_igemm_ws_floats_det": ([C.POINTER(Gather), i32], C.c_long),

@@ -120,6 +120,19 @@ inline PixelSlices plan_pixel_slices(int P, int k_unit, int min_trips, int tiles
   nsplit = (P + pps - 1) / pps;
   return {nsplit, pps, (tiles * nsplit + 7) / 8 * 8};
 }
+// What a launch will be.  plan_wgrad decides it (kernel family, template arguments, grid), the launchers carry it out and
+// ast_wgrad_plan reports it: a launcher takes nothing about its grid or its instantiation from anywhere else.
+constexpr int WH_TH = 8, WH_TW = 16, WH_MAXPL = 10;
+struct WHaloPlan { int PH, PW, dhmin, dwmin, tiles_h, tiles_w, ntiles, lds; };
+struct WgradPlan {
+  enum Family { None = -1, Coop = 0, Halo = 1, Rows = 2, Tap = 3 };
+  int family;                      // None: a geometry without taps, nothing is launched
+  int bmw, nct;                    // the workgroup's tile: output channels x 16-column tiles (rows kernel: 64 x 12, tap kernel: 64 x 4)
+  int pg;                          // pixel groups of the cooperative and halo kernels; ring stages of the rows kernel; 1 for the tap kernel
+  int gx, gy;                      // row tiles, column tiles
+  int slices, pps, grid;           // pixel slices, pixels per slice, 1-D grid (halo kernel: gz, tiles in the layer, unused)
+  WHaloPlan hp;                    // halo kernel only
+};
 template <typename T> struct WgradCfg;
 template <> struct WgradCfg<bf16_t> { static constexpr int BKP = 64, PAD = 16; };   // elements: row pitch = 32 B x odd for rows that are multiples of 64 B (see SWZ)
 template <> struct WgradCfg<float> { static constexpr int BKP = 32, PAD = 16; };
@@ -349,27 +362,35 @@ extern "C" int ast_debug_read_wg_phases(long long* host, int n) {
 }
 #endif
 
+// The cooperative kernel's launch: pixel groups, tiles and pixel slices (bkp: WgradCfg<T>::BKP of the dtype)
+inline void plan_wgrad_coop(const ast_gather_t& g, int P, int bkp, const WgradFlush& f, WgradPlan& p) {
+  // two pixel groups for the pixel-rich layers only: measured 172 800 pixels -11 % (51 -> 45 us), 43 200 pixels +20 %
+  // (54 -> 65 us: their slices are a few K tiles long, halving them leaves the groups idle at the barriers)
+  p.pg = wg_pg_knob(2) >= 2 && P >= env_int("AST_WGRAD_PG_MINP", 100000) ? 2 : 1;
+  p.gx = (g.Cd + p.bmw - 1) / p.bmw; p.gy = (g.ntaps * g.Cs + p.nct * 16 - 1) / (p.nct * 16);
+  const int tiles = p.gx * p.gy;
+  // see plan_wgrad_halo_launch; the single-group 64 x 192 tiles (23 launches of a step) take 384: 29.5-29.8 -> 28.1-28.3 us on
+  // average in the replayed step (tools/knob_ab.sh; 320: 29.1, 448: 30.5), the two-group and the narrow ones do not (32.7 -> 43.3)
+  const int wg_target = wg_target_knob(P >= 1500000 ? 768 : (p.pg == 1 && p.nct >= 12 ? 384 : 256));
+  // at least 4 K trips per slice; slab mode: one copy of dW per pixel slice
+  const PixelSlices ps = plan_pixel_slices(P, bkp, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
+  p.slices = ps.nsplit; p.pps = ps.pps; p.grid = ps.grid;
+}
+
 template <typename T, int BMW, int NCT, int PG>
-int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
+int launch_wgrad_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradPlan& p, const WgradFlush& f, hipStream_t s) {
   constexpr int BKP = WgradCfg<T>::BKP, PAD = WgradCfg<T>::PAD;
   constexpr int GROUP = (int)sizeof(T) * BKP * ((BMW + PAD) + (NCT * 16 + PAD));
   constexpr int RED = PG > 1 ? (BMW / 16) * ((NCT + 3) / 4) * 256 * 16 : 0;
   constexpr int LDS = std::max(std::max(PG * GROUP, RED), BMW * NCT * 16 * 4) + 64;
   static LdsAttrOnce attr;
   if (int rc = attr.set(LDS, {(const void*)wgrad_kernel<T, BMW, NCT, PG, false>, (const void*)wgrad_kernel<T, BMW, NCT, PG, true>})) return rc;
-  const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
-  const int tiles = gx * gy;
-  // see launch_wgrad_halo; the single-group 64 x 192 tiles (23 launches of a step) take 384: 29.5-29.8 -> 28.1-28.3 us on
-  // average in the replayed step (tools/knob_ab.sh; 320: 29.1, 448: 30.5), the two-group and the narrow ones do not (32.7 -> 43.3)
-  const int wg_target = wg_target_knob(P >= 1500000 ? 768 : (PG == 1 && NCT >= 12 ? 384 : 256));
-  // at least 4 K trips per slice; slab mode: one copy of dW per pixel slice
-  const PixelSlices ps = plan_pixel_slices(P, BKP, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  wg_report_slices(f, ps.nsplit);
+  wg_report_slices(f, p.slices);
   const auto k = f.mode == WgradFlush::Slab ? wgrad_kernel<T, BMW, NCT, PG, true> : wgrad_kernel<T, BMW, NCT, PG, false>;
-  hipLaunchKernelGGL(k, dim3(ps.grid), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
-                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, wg_flush_arg(f), f.stride);
+  hipLaunchKernelGGL(k, dim3(p.grid), dim3(256 * PG), LDS, s, (const T*)dy, (const T*)src, dw, g, P, p.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, p.gx, p.gy, p.slices, wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
 }
@@ -628,32 +649,32 @@ bool wgrad_rows_eligible(const ast_gather_t& g, int dtype) {
   return true;
 }
 
+// The rows kernel's launch: ring depth (4 stages = 71 KB of LDS, two workgroups per CU; 3 = 53 KB, three), tiles and pixel slices
+inline void plan_wgrad_rows(const ast_gather_t& g, int P, const WgradFlush& f, WgradPlan& p) {
+  const int nst = env_int("AST_WGRAD_ROWS_STAGES", 4);
+  p.bmw = 64; p.nct = 12;
+  p.pg = nst == 2 || nst == 3 ? nst : 4;
+  p.gx = g.Cd / 64; p.gy = 3 * (g.Cs / 64);
+  const int tiles = p.gx * p.gy;
+  const int wg_target = wg_target_knob(384);            // 1.5 workgroups per CU (71 KB of LDS each); 256 and 512 measured slower (profiles/r03/wg_rows_layers.txt)
+  const PixelSlices ps = plan_pixel_slices(P, 64, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
+  p.slices = ps.nsplit; p.pps = ps.pps; p.grid = ps.grid;
+}
+
 template <int NST>
-int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
+int launch_wgrad_rows(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradPlan& p, const WgradFlush& f, hipStream_t s) {
   constexpr int STAGE = 64 * 128 + 72 * 128 + 384;
   constexpr int LDS = (NST * STAGE > 64 * 192 * 4 ? NST * STAGE : 64 * 192 * 4) + 64;
   static LdsAttrOnce attr;
   if (int rc = attr.set(LDS, {(const void*)wgrad_rows_kernel<NST, false>, (const void*)wgrad_rows_kernel<NST, true>})) return rc;
-  const int gx = g.Cd / 64, gy = 3 * (g.Cs / 64);
-  const int tiles = gx * gy;
-  const int wg_target = wg_target_knob(384);            // 1.5 workgroups per CU (71 KB of LDS each); 256 and 512 measured slower (profiles/r03/wg_rows_layers.txt)
-  const PixelSlices ps = plan_pixel_slices(P, 64, 4, tiles, (wg_target + tiles - 1) / tiles, wg_slice_cap(f));
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * 2);
   const unsigned src_bytes = (unsigned)((size_t)P * g.Cs * 2);
-  wg_report_slices(f, ps.nsplit);
+  wg_report_slices(f, p.slices);
   const auto k = f.mode == WgradFlush::Slab ? wgrad_rows_kernel<NST, true> : wgrad_rows_kernel<NST, false>;
-  hipLaunchKernelGGL(k, dim3(ps.grid), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
-                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, wg_flush_arg(f), f.stride);
+  hipLaunchKernelGGL(k, dim3(p.grid), dim3(256), LDS, s, (const bf16_t*)dy, (const bf16_t*)src, dw, g, P, p.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, p.gx, p.gy, p.slices, wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
-}
-
-template <typename T, int BMW, int NCT>
-int launch_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
-  // two pixel groups for the pixel-rich layers only: measured 172 800 pixels -11 % (51 -> 45 us), 43 200 pixels +20 %
-  // (54 -> 65 us: their slices are a few K tiles long, halving them leaves the groups idle at the barriers)
-  if (wg_pg_knob(2) >= 2 && P >= env_int("AST_WGRAD_PG_MINP", 100000)) return launch_wgrad_pg<T, BMW, NCT, 2>(dy, src, dw, g, P, f, s);
-  return launch_wgrad_pg<T, BMW, NCT, 1>(dy, src, dw, g, P, f, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -665,8 +686,7 @@ int launch_wgrad(const void* dy, const void* src, float* dw, const ast_gather_t&
 // is a transposed read of the patch at a shifted address.  Accumulators stay in registers across
 // all tiles of the workgroup; one atomic flush at the end.
 // ---------------------------------------------------------------------------
-constexpr int WH_TH = 8, WH_TW = 16, WH_MAXPL = 10;
-struct WHaloPlan { int PH, PW, dhmin, dwmin, tiles_h, tiles_w, ntiles, lds; };
+// (WHaloPlan and the tile constants WH_TH x WH_TW, WH_MAXPL: beside WgradPlan above)
 
 // PG: pixel groups.  The workgroup has PG groups of 4 waves; group pg streams tiles blockIdx.z*PG + pg, + gridDim.z*PG, ...
 // through its OWN LDS staging and accumulators, and the groups' partial tiles are summed through LDS before ONE atomic flush per
@@ -894,36 +914,36 @@ bool plan_wgrad_halo(const ast_gather_t& g, int dtype, int nct, int bmw, WHaloPl
   return eff >= 0.6 && hp.ntiles >= 256;
 }
 
+// The halo kernel's launch (p.hp from plan_wgrad_halo): pixel groups, tiles and the z extent of the grid
+inline void plan_wgrad_halo_launch(const ast_gather_t& g, const WgradFlush& f, WgradPlan& p) {
+  // pixel groups: as many as the LDS holds (<= 4), when every group gets several tiles
+  // (four groups need <= 128 VGPRs per thread; the kernel uses 130-200 and spills: 50 -> 105 us on the 32-channel layer)
+  int pg = wg_pg_knob(2);
+  while (pg > 1 && (pg * p.hp.lds > 150 * 1024 || p.hp.ntiles < 256 * pg * 2)) pg >>= 1;
+  p.pg = pg >= 4 ? 4 : (pg == 2 ? 2 : 1);
+  p.gx = (g.Cd + p.bmw - 1) / p.bmw; p.gy = (g.ntaps * g.Cs + p.nct * 16 - 1) / (p.nct * 16);
+  // every workgroup adds its whole dW tile into the same few KB: same-address atomics serialise, so the workgroup count
+  // stays at about one per CU and the waves come from the pixel groups (sweep in profiles/r01 and r02)
+  const int wg_target = wg_target_knob(p.pg > 1 ? 256 : ((long)g.N * g.Hm * g.Wm >= 1500000 ? 768 : 256));
+  p.slices = std::min(std::max(1, std::min((p.hp.ntiles + p.pg - 1) / p.pg, wg_target / (p.gx * p.gy))), wg_slice_cap(f));
+  p.pps = p.hp.ntiles; p.grid = 0;
+}
+
 template <typename T, int BMW, int NCT, int PG>
-int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, const WgradFlush& f, hipStream_t s) {
+int launch_wgrad_halo_pg(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WgradPlan& p, const WgradFlush& f, hipStream_t s) {
+  const WHaloPlan& hp = p.hp;
   constexpr int RED = (BMW / 16) * ((NCT + 3) / 4) * 256 * 16;          // bytes of one group's partial tile in the LDS reduction
   const int lds = std::max(std::max(PG * hp.lds, PG > 1 ? RED : 0), BMW * NCT * 16 * 4) + 160;
   static LdsAttrOnce attr;
   if (int rc = attr.set(160 * 1024, {(const void*)wgrad_halo_kernel<T, BMW, NCT, PG, false>, (const void*)wgrad_halo_kernel<T, BMW, NCT, PG, true>})) return rc;
-  const int gx = (g.Cd + BMW - 1) / BMW, gy = (g.ntaps * g.Cs + NCT * 16 - 1) / (NCT * 16);
-  // every workgroup adds its whole dW tile into the same few KB: same-address atomics serialise, so the workgroup count
-  // stays at about one per CU and the waves come from the pixel groups (sweep in profiles/r01 and r02)
-  const int wg_target = wg_target_knob(PG > 1 ? 256 : ((long)g.N * g.Hm * g.Wm >= 1500000 ? 768 : 256));
-  const int gz = std::min(std::max(1, std::min((hp.ntiles + PG - 1) / PG, wg_target / (gx * gy))), wg_slice_cap(f));
-  wg_report_slices(f, gz);
+  wg_report_slices(f, p.slices);
   const unsigned dy_bytes = (unsigned)((size_t)g.N * g.Hm * g.Wm * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
   const auto k = f.mode == WgradFlush::Slab ? wgrad_halo_kernel<T, BMW, NCT, PG, true> : wgrad_halo_kernel<T, BMW, NCT, PG, false>;
-  hipLaunchKernelGGL(k, dim3(gx, gy, gz), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp, dy_bytes, src_bytes,
+  hipLaunchKernelGGL(k, dim3(p.gx, p.gy, p.slices), dim3(256 * PG), lds, s, (const T*)dy, (const T*)src, dw, g, hp, dy_bytes, src_bytes,
                      wg_flush_arg(f), f.stride);
   AST_CHECK_LAUNCH();
   return 0;
-}
-
-template <typename T, int BMW, int NCT>
-int launch_wgrad_halo(const void* dy, const void* src, float* dw, const ast_gather_t& g, const WHaloPlan& hp, const WgradFlush& f, hipStream_t s) {
-  // pixel groups: as many as the LDS holds (<= 4), when every group gets several tiles
-  // (four groups need <= 128 VGPRs per thread; the kernel uses 130-200 and spills: 50 -> 105 us on the 32-channel layer)
-  int pg = wg_pg_knob(2);
-  while (pg > 1 && (pg * hp.lds > 150 * 1024 || hp.ntiles < 256 * pg * 2)) pg >>= 1;
-  if (pg >= 4) return launch_wgrad_halo_pg<T, BMW, NCT, 4>(dy, src, dw, g, hp, f, s);
-  if (pg == 2) return launch_wgrad_halo_pg<T, BMW, NCT, 2>(dy, src, dw, g, hp, f, s);
-  return launch_wgrad_halo_pg<T, BMW, NCT, 1>(dy, src, dw, g, hp, f, s);
 }
 
 
@@ -1124,42 +1144,45 @@ __global__ __launch_bounds__(64 * NW) void wgrad_tap_kernel(const T* __restrict_
   }
 }
 
-template <typename T>
-int launch_wgrad_tap(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradFlush& f, hipStream_t s) {
-  constexpr int NW = 8, KPX = WtCfg<T>::KPX;
-  constexpr int LDS = NW * 64 * 64 * 4 + 64;
-  static LdsAttrOnce attr;
-  if (int rc = attr.set(LDS, {(const void*)wgrad_tap_kernel<T, NW>})) return rc;
-  const int gx = (g.Cd + 63) / 64, gy = (g.ntaps * g.Cs + 63) / 64, tiles = gx * gy;
+// The tap kernel's launch (kpx: WtCfg<T>::KPX of the dtype)
+inline void plan_wgrad_tap(const ast_gather_t& g, int P, int kpx, const WgradFlush& f, WgradPlan& p) {
+  constexpr int NW = 8;
+  p.bmw = 64; p.nct = 4; p.pg = 1;
+  p.gx = (g.Cd + 63) / 64; p.gy = (g.ntaps * g.Cs + 63) / 64;
+  const int tiles = p.gx * p.gy;
   // pixel slices: about one workgroup (8 waves) per CU.  More slices = more flush bytes (slices x |dW| of f32 atomics at the chip's
   // ~1.3 TB/s), fewer = idle CUs; a slice keeps at least two K steps per wave.
   const int wg_target = env_int("AST_WGRAD_TAP_WGS", 256);
-  const PixelSlices ps = plan_pixel_slices(P, KPX, 2 * NW, tiles, (wg_target + tiles / 2) / tiles, wg_slice_cap(f));
+  const PixelSlices ps = plan_pixel_slices(P, kpx, 2 * NW, tiles, (wg_target + tiles / 2) / tiles, wg_slice_cap(f));
+  p.slices = ps.nsplit; p.pps = ps.pps; p.grid = ps.grid;
+}
+
+template <typename T>
+int launch_wgrad_tap(const void* dy, const void* src, float* dw, const ast_gather_t& g, int P, const WgradPlan& p, const WgradFlush& f, hipStream_t s) {
+  constexpr int NW = 8;
+  constexpr int LDS = NW * 64 * 64 * 4 + 64;
+  static LdsAttrOnce attr;
+  if (int rc = attr.set(LDS, {(const void*)wgrad_tap_kernel<T, NW>})) return rc;
   const unsigned dy_bytes = (unsigned)((size_t)P * g.Cd * sizeof(T));
   const unsigned src_bytes = (unsigned)((size_t)g.N * g.Hs * g.Ws * g.Cs * sizeof(T));
-  wg_report_slices(f, ps.nsplit);
+  wg_report_slices(f, p.slices);
   // (no flush mode to pass: this kernel has the atomic flush only, the dispatcher keeps it out of slab mode)
-  hipLaunchKernelGGL((wgrad_tap_kernel<T, NW>), dim3(ps.grid), dim3(64 * NW), LDS, s, (const T*)dy, (const T*)src, dw, g, P, ps.pps, dy_bytes, src_bytes,
-                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, gx, gy, ps.nsplit, f.copies, f.stride, ps.nsplit == 1 ? 1 : 0);
+  hipLaunchKernelGGL((wgrad_tap_kernel<T, NW>), dim3(p.grid), dim3(64 * NW), LDS, s, (const T*)dy, (const T*)src, dw, g, P, p.pps, dy_bytes, src_bytes,
+                     1.0f / (float)(g.Hm * g.Wm), 1.0f / (float)g.Wm, p.gx, p.gy, p.slices, f.copies, f.stride, p.slices == 1 ? 1 : 0);
   AST_CHECK_LAUNCH();
   return 0;
 }
 
-// The one dispatcher behind ast_wgrad / ast_wgrad_rep / ast_wgrad_slab: picks the kernel family and tile shape for the layer
-// and hands the flush descriptor to its launcher.  (The messages keep the name of the entry point all three share.)
-int wgrad_dispatch(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, const WgradFlush& f, hipStream_t s) {
-  if (int rc = check_gather(gp, "ast_wgrad")) return rc;
-  if (!dy || !src || !dw) AST_FAIL("ast_wgrad: null pointer");
-  const ast_gather_t g = *gp;
+// The one decision behind ast_wgrad / ast_wgrad_rep / ast_wgrad_slab and ast_wgrad_plan: the kernel family, its template arguments
+// and its grid for the layer (g checked by check_gather).  Host side only.  (The messages keep the name of the entry point all share.)
+int plan_wgrad(const ast_gather_t& g, int dtype, const WgradFlush& f, WgradPlan& p) {
+  p = WgradPlan{};
+  p.family = WgradPlan::None;
   if (g.ntaps == 0) return 0;
   const int P = g.N * g.Hm * g.Wm;
   if ((long)P * g.Cd * 4 >= (1L << 31)) AST_FAIL("ast_wgrad: dy exceeds the 2 GiB buffer-addressing range");
-  const int nct_all = (g.ntaps * g.Cs + 15) / 16;          // column tiles of the whole (tap, channel) space
-  const int bmw = g.Cd > 32 ? 64 : (g.Cd > 16 ? 32 : 16);
-  // all columns in one workgroup when the accumulators fit (<= 20 tiles x BMW/16 row tiles <= 20 per wave)
-  int nct;
-  if (bmw == 64) nct = nct_all <= 8 ? (nct_all <= 4 ? 4 : 8) : 12;
-  else nct = nct_all <= 4 ? 4 : (nct_all <= 8 ? 8 : (nct_all <= 12 ? 12 : 20));
+  if (dtype != AST_F32 && dtype != AST_BF16) AST_FAIL("ast_wgrad: bad dtype %d", dtype);
+  const bool bf = dtype == AST_BF16;
   // >= 64 output channels: the wave-autonomous tap-tile kernel (AST_WGRAD_TAP=0: the cooperative kernels below, for A/B)
   // Opt-in (AST_WGRAD_TAP=1): measured SLOWER than the cooperative kernels below -- isolated 44.4 vs 39.4 us on the 64-channel
   // layer, 71.8 vs 41.3 (256 channels), 67.2 vs 39.6 (512); only the stride-2 layers gain (24.9 vs 30.9) -- and the whole step
@@ -1167,19 +1190,55 @@ int wgrad_dispatch(const void* dy, const void* src, float* dw, const ast_gather_
   // fabric, not the MFMAs), and a workgroup takes a whole CU (128 KB of LDS) away from the other streams' kernels.  DESIGN 9.3.
   // (the knobs here are read per call, host side only: tests toggle them at run time; the tap kernel has no slab form)
   if (env_flag("AST_WGRAD_TAP", false) && f.mode != WgradFlush::Slab && g.Cd >= 64) {
-    AST_DISPATCH_T(dtype, { return launch_wgrad_tap<T>(dy, src, dw, g, P, f, s); });
+    p.family = WgradPlan::Tap;
+    plan_wgrad_tap(g, P, bf ? WtCfg<bf16_t>::KPX : WtCfg<float>::KPX, f, p);
+    return 0;
   }
   if (env_flag("AST_WGRAD_ROWS", true) && wgrad_rows_eligible(g, dtype)) {
     if ((long)P * g.Cs * 2 >= (1L << 31)) AST_FAIL("ast_wgrad: source exceeds the 2 GiB buffer-addressing range");
-    const int nst = env_int("AST_WGRAD_ROWS_STAGES", 4);    // ring depth: 4 stages = 71 KB of LDS (two workgroups per CU), 3 = 53 KB (three)
-    if (nst == 2) return launch_wgrad_rows<2>(dy, src, dw, g, P, f, s);
-    if (nst == 3) return launch_wgrad_rows<3>(dy, src, dw, g, P, f, s);
-    return launch_wgrad_rows<4>(dy, src, dw, g, P, f, s);
+    p.family = WgradPlan::Rows;
+    plan_wgrad_rows(g, P, f, p);
+    return 0;
   }
-  WHaloPlan whp;
-  const bool halo = plan_wgrad_halo(g, dtype, nct, bmw, whp);
-#define AST_WG(B_, N_) do { if (halo) return launch_wgrad_halo<T, B_, N_>(dy, src, dw, g, whp, f, s); \
-                            return launch_wgrad<T, B_, N_>(dy, src, dw, g, P, f, s); } while (0)
+  const int nct_all = (g.ntaps * g.Cs + 15) / 16;          // column tiles of the whole (tap, channel) space
+  p.bmw = g.Cd > 32 ? 64 : (g.Cd > 16 ? 32 : 16);
+  // all columns in one workgroup when the accumulators fit (<= 20 tiles x BMW/16 row tiles <= 20 per wave)
+  if (p.bmw == 64) p.nct = nct_all <= 8 ? (nct_all <= 4 ? 4 : 8) : 12;
+  else p.nct = nct_all <= 4 ? 4 : (nct_all <= 8 ? 8 : (nct_all <= 12 ? 12 : 20));
+  if (plan_wgrad_halo(g, dtype, p.nct, p.bmw, p.hp)) {
+    p.family = WgradPlan::Halo;
+    plan_wgrad_halo_launch(g, f, p);
+  } else {
+    p.family = WgradPlan::Coop;
+    plan_wgrad_coop(g, P, bf ? WgradCfg<bf16_t>::BKP : WgradCfg<float>::BKP, f, p);
+  }
+  return 0;
+}
+
+// The one dispatcher behind ast_wgrad / ast_wgrad_rep / ast_wgrad_slab: launches the instantiation plan_wgrad names, on its grid.
+int wgrad_dispatch(const void* dy, const void* src, float* dw, const ast_gather_t* gp, int dtype, const WgradFlush& f, hipStream_t s) {
+  if (int rc = check_gather(gp, "ast_wgrad")) return rc;
+  if (!dy || !src || !dw) AST_FAIL("ast_wgrad: null pointer");
+  const ast_gather_t g = *gp;
+  WgradPlan p;
+  if (int rc = plan_wgrad(g, dtype, f, p)) return rc;
+  if (p.family == WgradPlan::None) return 0;
+  const int P = g.N * g.Hm * g.Wm;
+  if (p.family == WgradPlan::Tap) AST_DISPATCH_T(dtype, { return launch_wgrad_tap<T>(dy, src, dw, g, P, p, f, s); });
+  if (p.family == WgradPlan::Rows) {
+    if (p.pg == 2) return launch_wgrad_rows<2>(dy, src, dw, g, P, p, f, s);
+    if (p.pg == 3) return launch_wgrad_rows<3>(dy, src, dw, g, P, p, f, s);
+    return launch_wgrad_rows<4>(dy, src, dw, g, P, p, f, s);
+  }
+#define AST_WG(B_, N_) do { \
+    if (p.family == WgradPlan::Halo) { \
+      if (p.pg == 4) return launch_wgrad_halo_pg<T, B_, N_, 4>(dy, src, dw, g, p, f, s); \
+      if (p.pg == 2) return launch_wgrad_halo_pg<T, B_, N_, 2>(dy, src, dw, g, p, f, s); \
+      return launch_wgrad_halo_pg<T, B_, N_, 1>(dy, src, dw, g, p, f, s); \
+    } \
+    if (p.pg == 2) return launch_wgrad_pg<T, B_, N_, 2>(dy, src, dw, g, P, p, f, s); \
+    return launch_wgrad_pg<T, B_, N_, 1>(dy, src, dw, g, P, p, f, s); } while (0)
+  const int bmw = p.bmw, nct = p.nct;
   AST_DISPATCH_T(dtype, {
     if (bmw == 64) { if (nct == 4) AST_WG(64, 4); if (nct == 8) AST_WG(64, 8); AST_WG(64, 12); }
     if (bmw == 32) { if (nct == 4) AST_WG(32, 4); if (nct == 8) AST_WG(32, 8); if (nct == 12) AST_WG(32, 12); AST_WG(32, 20); }
@@ -1237,6 +1296,18 @@ extern "C" int ast_wgrad_slab(const void* dy, const void* src, float* slabs, con
   if (nslabs < 1 || nslabs > 4096 || !gp || !slices_out) AST_FAIL("ast_wgrad_slab: 1..4096 slabs and a slices output");
   *slices_out = 0;                                       // stays 0 when nothing was launched
   return wgrad_dispatch(dy, src, slabs, gp, dtype, WgradFlush{WgradFlush::Slab, nslabs, (long)gp->Cd * gp->wtaps * gp->Cs, slices_out}, (hipStream_t)stream);
+}
+
+extern "C" int ast_wgrad_plan(const ast_gather_t* gp, int dtype, int slab_cap, int* out6) {
+  if (int rc = check_gather(gp, "ast_wgrad_plan")) return rc;
+  if (!out6) AST_FAIL("ast_wgrad_plan: null result array");
+  if (slab_cap < 0 || slab_cap > 4096) AST_FAIL("ast_wgrad_plan: slab cap %d (0: the atomic entries, 1..4096: ast_wgrad_slab)", slab_cap);
+  const WgradFlush f = slab_cap ? WgradFlush{WgradFlush::Slab, slab_cap, 0, nullptr} : WgradFlush{wg_atomic_mode(), 1, 0, nullptr};
+  WgradPlan p;
+  if (int rc = plan_wgrad(*gp, dtype, f, p)) return rc;
+  const int out[6] = {p.family, p.bmw, p.nct, p.pg, p.slices, p.pps};
+  for (int i = 0; i < 6; ++i) out6[i] = out[i];
+  return 0;
 }
 
 extern "C" int ast_slab_sum(float* const* bases, const int64_t* floats_per_copy, const int* slabs, int nrec, void* stream) {

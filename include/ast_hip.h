@@ -116,6 +116,16 @@ int ast_wgrad_rep(const void* dy, const void* src, float* dw, const ast_gather_t
 int ast_wgrad_slab(const void* dy, const void* src, float* slabs, const ast_gather_t* g, int dtype, int nslabs, int* slices_out,
                    void* stream);
 int ast_slab_sum(float* const* bases, const int64_t* floats_per_copy, const int* slabs, int nrec, void* stream);
+/* Query (host side, no launch; <0 with ast_last_error on a bad geometry, dtype or cap), answered by the one decision the three
+ * entries above launch from, with the same environment knobs read per call.  slab_cap = 0: what ast_wgrad / ast_wgrad_rep launch;
+ * 1..4096: what ast_wgrad_slab launches with that many slabs.  out6 = {kernel family (0 cooperative wgrad_kernel, 1 wgrad_halo_kernel,
+ * 2 wgrad_rows_kernel, 3 wgrad_tap_kernel; -1 for a geometry without taps: nothing is launched), BMW (output channels of a
+ * workgroup's tile), NCT (its 16-column tiles of the (tap, channel) space; rows kernel: 64 x 12, tap kernel: 64 x 4), pixel groups
+ * PG (rows kernel: ring stages; tap kernel: 1), pixel slices (what ast_wgrad_slab reports in *slices_out; pixel slice z uses copy
+ * z % nrep of ast_wgrad_rep), pixels per slice (halo kernel: 8x16-pixel tiles in the layer)}.
+ * With ntaps < wtaps (a parity class of a strided data gradient used as a weight-gradient geometry) no entry touches the dW slices of
+ * the taps the geometry does not list: in slab form those slices of every copy keep what they held. */
+int ast_wgrad_plan(const ast_gather_t* g, int dtype, int slab_cap, int* out6);
 
 /* Token-sized nn.Linear (M <= 64 rows, f32): y = act(x W^T + b), W row pitch ldw (W may be a row slice
  * of in_proj_weight or the transposed pack for the data gradient).  One wave per output column. */
